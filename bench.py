@@ -12,7 +12,9 @@ forward with quantisation noise, R-D loss, backward, in-place RCCL all-reduce of
 overlapped with the backward pass), Adam, aux-loss backward, aux all-reduce, aux Adam (ywz/mywork/newtrain1.py:74-111) --
 replayed from one HIP graph per rank (``--eager`` issues it from Python).  Weak scaling: global batch = 8 N.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times ``--steps`` steps, writes the last timed step's results if ``--dump-outputs DIR`` is given and
+prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step).  ``--full`` then
+measures and checks the rest after the timed region and adds it to the line, among it
   roofline      dominant kernel (implicit-GEMM conv, bf16 MFMA): achieved TFLOP/s = algorithmic conv FLOPs of its
                 launches / their summed HIP-event durations, measured live on the launch stream
   cpu_baseline  the CPU oracle (a port of the reference's forward, oracle/hesic_oracle.py) timed on this box's host
@@ -588,7 +590,7 @@ def secondary_train_rccl(dev, size=512, lmbda=0.0067):
     env = dict(os.environ, HESIC_FORCE_COLLECTIVES="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.abspath(__file__), "--mode", "train", "--steps", "12", "--warmup", "6", "--no-cpu-baseline", "--lmbda", str(lmbda), "--size", str(size)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--mode", "train", "--steps", "12", "--warmup", "6", "--full", "--no-cpu-baseline", "--lmbda", str(lmbda), "--size", str(size)]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
         lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -792,6 +794,48 @@ def emit_line(obj):
     sys.stdout.write(json.dumps(obj) + "\n")
     sys.stdout.flush()
 
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6        # --dump-outputs: under 64 MB in all
+
+
+def flat_outputs(out, rd=None):
+    """The arrays a caller of the forward receives (reconstructions, rounded latents, likelihoods) and, if given, the bits / squared-error
+    sums of ``models.rate_distortion``, as one flat {name: tensor}."""
+    arrays = {}
+    for k, v in out.items():
+        if isinstance(v, dict):
+            arrays.update({f"{k}_{kk}": vv for kk, vv in v.items()})
+        elif torch.is_tensor(v):
+            arrays[k] = v
+    for k, v in (rd or {}).items():
+        if torch.is_tensor(v):
+            arrays["rd_" + k] = v
+    return arrays
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: write every array as ``path/<name>.npy`` -- float64 where the path computes fp64 (the rate / distortion sums), float32
+    otherwise.  The arrays share DUMP_BUDGET_BYTES: the small ones are written whole, an array larger than its share is replaced by the 1-D
+    sample of its flattened elements at positions drawn by a generator seeded with ``seed`` (sorted, the same on every run of the same
+    arguments)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    left, budget = len(host), DUMP_BUDGET_BYTES
+    for name in sorted(host, key=lambda k: host[k].nbytes):
+        a = host[name]
+        cap = (budget // left) // a.itemsize
+        if a.size > cap:
+            idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        budget -= a.nbytes
+        left -= 1
+
+
 def sweep_main(args, batch, rank, world, dev, H_img, W_img):
     """--sweep: BASELINE config C5.  Four lambda-models (four independent weight sets; there are no trained checkpoints
     offline, so four deterministic synthetic fills), InStereo2K-size pairs zero-padded to x64, reconstructions cropped, bpp
@@ -805,7 +849,7 @@ def sweep_main(args, batch, rank, world, dev, H_img, W_img):
     acc = sweep.acc
 
     def step(k, record):
-        return sweep.step((rank + k) % 4, x1, x2, x1p, x2p, Hm, record)[1]
+        return sweep.step((rank + k) % 4, x1, x2, x1p, x2p, Hm, record)
 
     for k in range(max(args.warmup, 12)):          # three rounds: every model packs its weights, the allocator pools settle, and the
         step(k, True)                              # accumulation ops are loaded too (their first launches cost ~60 ms in all)
@@ -815,7 +859,7 @@ def sweep_main(args, batch, rank, world, dev, H_img, W_img):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        step(k, True)
+        last = step(k, True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -823,18 +867,21 @@ def sweep_main(args, batch, rank, world, dev, H_img, W_img):
     elapsed, ranks_info = job_time(elapsed, world, dev, args.batch * args.steps)
     if world > 1:
         dist.all_reduce(acc)
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, dict(flat_outputs(*last), lambda_sums=acc))
     if rank == 0:
         pairs = world * args.batch * args.steps
         per = {lam: {"pairs": v["pairs"], "bpp": round(v["bpp"], 5), "psnr": round(v["psnr"], 4)} for lam, v in sweep.summary(H_img, W_img).items()}
         # dominant conv kernel of the sweep's steps, measured live after the timed region (single stream: an event pair brackets ONE kernel)
         from hesic_amd import _lib as L_, models as models_
-        roof = None
-        overlap, models_.OVERLAP_STREAMS = models_.OVERLAP_STREAMS, False
-        with KernelMeter(L_) as km:
-            for k in range(4):
-                step(k, False)
-            s = km.summary()
-        models_.OVERLAP_STREAMS = overlap
+        roof, s = None, None
+        if args.full:
+            overlap, models_.OVERLAP_STREAMS = models_.OVERLAP_STREAMS, False
+            with KernelMeter(L_) as km:
+                for k in range(4):
+                    step(k, False)
+                s = km.summary()
+            models_.OVERLAP_STREAMS = overlap
         if s:
             peak = MFMA_BF16_PEAK_TFLOPS if args.dtype != "f32" else MFMA_F32_PEAK_TFLOPS
             roof = {"kernel": s["kernel"], "bound": "mfma", "achieved": round(s["tflops"], 2), "peak": peak, "unit": "TFLOP/s", "frac": round(s["tflops"] / peak, 4),
@@ -844,7 +891,7 @@ def sweep_main(args, batch, rank, world, dev, H_img, W_img):
             "metric": "stereo-pairs/sec encode+decode @512x512; bpp & PSNR delta vs reference",
             "value": round(pairs / elapsed, 2), "unit": "stereo-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.dtype, "data": "synthetic",
+            "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "config": {"workload": f"BASELINE config C5: {'HESIC' if args.model == 'hsic' else 'HESIC+'} rate-distortion sweep, 4 lambda-models x "
                                    f"{H_img}x{W_img} pairs (zero-padded to {x1p.shape[-2]}x{x1p.shape[-1]}, bpp over the original pixels), batch {args.batch}/GPU",
                        "pairs_per_step": world * args.batch, "sharding": f"one (lambda-model, batch) unit per rank and step over {world} GPU(s), no collective on the path",
@@ -886,26 +933,31 @@ def train_main(args, net, P_cpu, batch, rank, world, dev, H_img, W_img):
     elapsed = time.perf_counter() - t0
     elapsed, ranks_info = job_time(elapsed, world, dev, args.batch * args.steps)
     losses = {k: float(v) for k, v in crit.items()}
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        # what the step hands back (its loss terms) and what it leaves behind (the updated parameters, flattened in named_parameters order)
+        dump_outputs(args.dump_outputs, dict({"loss_" + k: v.reshape(1) for k, v in crit.items() if torch.is_tensor(v)},
+                                             parameters=torch.cat([p.detach().float().reshape(-1) for p in net.parameters()])))
 
     # roofline of the weight-gradient MFMA kernel, measured live (eager steps, events on the launch stream); launch census.
     # EVERY rank runs these extra steps (a step contains the gradient collectives: a rank that skipped them would hang the
     # others); only rank 0's events are reported.
-    roof, census = None, {}
+    roof, census, s = None, {}, None
     eager = Trainer.step          # the un-graphed step of the same trainer object
     orig_call = L_.call
 
     def counting(name, *a):
         census[name] = census.get(name, 0) + 1
         return orig_call(name, *a)
-    L_.call = counting
-    try:
-        eager(tr, x1, x2, Hm)
-    finally:
-        L_.call = orig_call
-    with WgradMeter(L_) as wm:
-        for _ in range(2):
+    if args.full:
+        L_.call = counting
+        try:
             eager(tr, x1, x2, Hm)
-        s = wm.summary()
+        finally:
+            L_.call = orig_call
+        with WgradMeter(L_) as wm:
+            for _ in range(2):
+                eager(tr, x1, x2, Hm)
+            s = wm.summary()
     if s and rank == 0:
         peak = MFMA_BF16_PEAK_TFLOPS if args.dtype != "f32" else MFMA_F32_PEAK_TFLOPS
         # the dominant kernel of the step by time is the weight-gradient family; since round 5 it has two members -- the line's figure is
@@ -924,7 +976,7 @@ def train_main(args, net, P_cpu, batch, rank, world, dev, H_img, W_img):
     # gradient all-reduce, self-diagnosing (N > 1 on RCCL): ONE eager step whose buckets run synchronously on a communication stream
     # between events -- per-bucket duration, bus bandwidth and the share of the communication hidden under the backward pass
     comm = None
-    if tr.main_reducer.active and tr.main_reducer.avg_op:
+    if args.full and tr.main_reducer.active and tr.main_reducer.avg_op:
         from hesic_amd.train import comm_report
         tr.main_reducer.timing = True
         eager(tr, x1, x2, Hm)
@@ -942,7 +994,7 @@ def train_main(args, net, P_cpu, batch, rank, world, dev, H_img, W_img):
 
     # clock / socket power while the timed step repeats (after the timed region; one rank: the sample is the whole board's)
     pstate = None
-    if world == 1 and not getattr(args, "no_power_state", False):
+    if args.full and world == 1 and not getattr(args, "no_power_state", False):
         try:
             n_, wall_, st_ = under_load(lambda: tr.step(x1, x2, Hm), 2.0)
             pstate = dict(st_ or {}, ms_per_step=round(1e3 * wall_ / n_, 3), power_cap_w=1400.0, nominal_sclk_mhz=2400.0,
@@ -956,7 +1008,7 @@ def train_main(args, net, P_cpu, batch, rank, world, dev, H_img, W_img):
             "metric": "stereo-pairs/sec encode+decode @512x512; bpp & PSNR delta vs reference",
             "value": round(pairs / elapsed, 2), "unit": "stereo-pairs/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "config": {"workload": f"{'HESIC' if args.model == 'hsic' else 'HESIC+'} TRAINING step (BASELINE config C3: R-D loss, Adam x2, "
                                    f"gradient all-reduce), {H_img}x{W_img} stereo pairs, batch {args.batch}/GPU, lambda {args.lmbda}",
                        "pairs_per_step": world * args.batch, "global_batch": world * args.batch,
@@ -968,10 +1020,10 @@ def train_main(args, net, P_cpu, batch, rank, world, dev, H_img, W_img):
             "roofline": roof, "power_state_timed_step": pstate,
             "comm": comm,
             "launches_per_step": {"c_abi_calls": sum(census.values()), "note": "C-ABI calls of one eager step (each is 1-2 kernel launches); "
-                                  "ATen launches not included -- see profiles/ for the rocprofv3 count"},
+                                  "ATen launches not included -- see profiles/ for the rocprofv3 count"} if args.full else None,
             "losses_last_step": {k: round(v, 5) for k, v in losses.items()},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base = cpu_train_baseline(args.model, P_cpu, param_names, 512 if (args.height or args.width) else args.size, args.lmbda)
             res["cpu_baseline"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in base.items()}
         else:
@@ -1038,19 +1090,28 @@ def main():
                     help="operand precision of the analysis transforms + hyper-analysis at 16-bit inference: x3 = hi/lo pairs everywhere (three "
                          "products per MAC, fp32-grade latents), x3c2 = pairs except g_a_conv2 (70 %% of g_a's MACs) on single operands, x1 = single "
                          "operands (bf16 / bf16x3: the round-3 names of x1 / x3)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: the roofline of the dominant kernel (and the power state, the "
+                         "launch census, the gradient all-reduce in train mode), the CPU oracle baseline with the parity against it, and the "
+                         "`secondary` block.  A plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB "
+                         "in all; a larger array is written as a fixed, seeded sample of its elements).  Inputs are the same on every run")
     ap.add_argument("--parity-trained", type=int, default=0, metavar="SETS",
-                    help="also report parity at TRAINED operating points: train SETS weight sets for --parity-train-steps steps each on synthetic "
+                    help="with --full: also report parity at TRAINED operating points: train SETS weight sets for --parity-train-steps steps each on synthetic "
                          "pairs (about 25 s per set) and compare bf16x3 / bf16 / fp32 against the CPU oracle on the trained weights")
     ap.add_argument("--parity-train-steps", type=int, default=3000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-power-state", action="store_true", help="skip roofline.power_state (clock / socket power under the timed step and under a matrix-only loop, ~6 s)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` block (HESIC+ B=4 and one training step, ~5 s, after the timed region)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline and the parity block")
+    ap.add_argument("--no-power-state", action="store_true", help="with --full: skip roofline.power_state (clock / socket power under the timed step and under a matrix-only loop, ~6 s)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the `secondary` block (HESIC+ B=4 and one training step, ~5 s, after the timed region)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a HIP graph (models.GraphedForward) instead of issuing it eagerly")
     ap.add_argument("--exec", dest="exec_mode", choices=["auto", "eager", "graph"], default="auto",
                     help="inference: how the step is issued.  Same kernels, same results; eager issue costs the host ~1.3-1.5 ms per forward "
                          "(Python + ctypes per launch), a HIP-graph replay none but the runtime orders parallel branches its own way. "
                          "auto = time a few steps of both during warm-up and keep the faster")
     args = ap.parse_args()
+    if args.parity_trained > 0 and not args.full:
+        ap.error("--parity-trained is part of the parity block: add --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher: start N ranks of this same command under torch.distributed.run (one process per GPU,
         # RCCL over xGMI; 127.0.0.1 rendezvous -- the container hostname may not resolve) and hand their exit code on.  Rank 0 of
@@ -1125,7 +1186,7 @@ def main():
         a, b, ap_, bp_, h = pool[i % NBUF]
         with torch.no_grad():
             out = net(ap_, bp_, h)
-        return metrics_async(out, a, b)
+        return out, metrics_async(out, a, b)
 
     eager_step = step
     exec_mode = "graph" if args.graph else args.exec_mode
@@ -1137,7 +1198,7 @@ def main():
             a, b, ap_, bp_, h = pool[i % NBUF]
             torch.cuda.current_stream().wait_stream(mstream)      # the replay overwrites the static outputs the last reductions read
             out, _ = graphed(ap_, bp_, h)
-            return metrics_async(out, a, b)
+            return out, metrics_async(out, a, b)
 
         if exec_mode == "auto":
             def trial(fn, n=40):
@@ -1158,29 +1219,32 @@ def main():
         if picked["mode"] == "graph":
             step = graph_step
     for i in range(args.warmup):
-        rd = step(i)
+        out, rd = step(i)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        rd = step(i)
+        out, rd = step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     elapsed, ranks_info = job_time(elapsed, world, dev, args.batch * args.steps)
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, flat_outputs(out, rd))          # before anything else runs: a graph replay overwrites `out`
     m_gpu = models.metrics_from(rd)
 
     # roofline of the dominant kernel, measured live with HIP events on the launch stream
-    roof = None
+    roof, s = None, None
     from hesic_amd import _lib as L_
-    overlap, models.OVERLAP_STREAMS = models.OVERLAP_STREAMS, False     # one stream: an event pair brackets ONE kernel
-    with KernelMeter(L_) as km:
-        for _ in range(3):
-            eager_step()
-        s = km.summary()
-    models.OVERLAP_STREAMS = overlap
+    if args.full:
+        overlap, models.OVERLAP_STREAMS = models.OVERLAP_STREAMS, False     # one stream: an event pair brackets ONE kernel
+        with KernelMeter(L_) as km:
+            for _ in range(3):
+                eager_step()
+            s = km.summary()
+        models.OVERLAP_STREAMS = overlap
     if s:
         peak = MFMA_BF16_PEAK_TFLOPS if args.dtype != "f32" else MFMA_F32_PEAK_TFLOPS
         traffic, traffic_src = None, None     # HBM-side bytes per launch from the committed rocprofv3 PMC passes (profiles/make_pmc_json.py)
@@ -1248,7 +1312,7 @@ def main():
             "metric": "stereo-pairs/sec encode+decode @512x512; bpp & PSNR delta vs reference",
             "value": round(pairs / elapsed, 2), "unit": "stereo-pairs/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "config": {"workload": f"{'HESIC' if args.model == 'hsic' else 'HESIC+'} eval forward (encode+decode) + bpp/PSNR, "
                                    f"{H_img}x{W_img} stereo pairs, batch {args.batch}/GPU, random-init-shaped deterministic weights",
                        "pairs_per_step": world * args.batch, "sharding": f"pairs over {world} GPU(s), no collective on the path",
@@ -1260,7 +1324,7 @@ def main():
         }
         if ranks_info is not None:
             res["ranks"] = ranks_info
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             square = not (args.height or args.width)
             npar = min(8, args.batch) if square else 1          # every distinct pair of the timed batch
             base, m_cpu = cpu_baseline(args.model, P_cpu, args.size if square else 512, parity_pairs=npar)
@@ -1318,7 +1382,7 @@ def main():
         else:
             res["cpu_baseline"] = None
         default_workload = args.model == "hsic" and args.batch == 8 and not (args.height or args.width) and args.size == 512
-        if world == 1 and default_workload and not args.no_secondary:
+        if args.full and world == 1 and default_workload and not args.no_secondary:
             res["secondary"] = secondary_block(dev, lmbda=args.lmbda)
             # round 5: the other modes of C2 with their parity, the C5 sweep, path A and the training step with RCCL in the graph (~15 s)
             if not args.no_cpu_baseline and args.dtype != "f32":

@@ -718,6 +718,48 @@ def fx_codec():
     npz("codec.npz", **A)
 
 
+def fx_codec_random():
+    """The randomised cases of tests/test_host_vs_ref_ext.py (same generators, same draws) with the reference extensions' answers:
+    200 pmf -> quantised CDF tables and 40 rANS streams (up to 3000 symbols, bypass escapes included), each stream checked to decode."""
+    from compressai._CXX import pmf_to_quantized_cdf
+    from compressai import ans
+    r = np.random.Generator(np.random.PCG64(5))
+    pmfs, cdfs_out = [], []
+    for trial in range(200):
+        n = int(r.integers(2, 300))
+        p = r.dirichlet(np.full(n, r.choice([0.05, 0.5, 5.0])))
+        if trial % 3 == 0:
+            p[r.integers(0, n, n // 2)] = 0.0
+            if p.sum() == 0:
+                continue
+            p /= p.sum()
+        p = p.astype(np.float32)
+        pmfs.append(p)
+        cdfs_out.append(np.array(pmf_to_quantized_cdf(p.tolist(), 16), dtype=np.int32))
+    r = np.random.Generator(np.random.PCG64(6))
+    R = {k: [] for k in ("ntab", "L", "table", "sizes", "offsets", "n", "idx", "sym", "nbytes", "bytes")}
+    for trial in range(40):
+        ntab = int(r.integers(1, 6))
+        cdfs = [list(pmf_to_quantized_cdf(r.dirichlet(np.ones(int(r.integers(2, 40)))).astype(np.float32).tolist(), 16)) for _ in range(ntab)]
+        sizes = [len(c) for c in cdfs]
+        L = max(sizes)
+        table = [c + [0] * (L - len(c)) for c in cdfs]
+        offsets = [int(r.integers(-20, 5)) for _ in range(ntab)]
+        n = int(r.integers(1, 3000))
+        idx = r.integers(0, ntab, n).tolist()
+        spread = int(r.choice([0, 3, 300]))
+        sym = [int(r.integers(offsets[i] - spread, offsets[i] + sizes[i] + spread + 1)) for i in idx]
+        s = ans.RansEncoder().encode_with_indexes(sym, idx, table, sizes, offsets)
+        assert ans.RansDecoder().decode_with_indexes(s, idx, table, sizes, offsets) == sym
+        for k, v in (("ntab", [ntab]), ("L", [L]), ("table", np.ravel(table)), ("sizes", sizes), ("offsets", offsets), ("n", [n]),
+                     ("idx", idx), ("sym", sym), ("nbytes", [len(s)])):
+            R[k].append(np.asarray(v, dtype=np.int32))
+        R["bytes"].append(np.frombuffer(s, dtype=np.uint8))
+    npz("codec_random.npz", pmf=np.concatenate(pmfs), pmf_len=np.array([len(p) for p in pmfs], dtype=np.int32),
+        cdf=np.concatenate(cdfs_out), cdf_len=np.array([len(c) for c in cdfs_out], dtype=np.int32),
+        **{"rans_" + k: np.concatenate(v) for k, v in R.items()})
+
+
 def fx_codec_model(newnet1):
     """Round 2: the reference's OWN ``HSIC.compress`` (newnet1.py:823-1066) run here at 64 x 64 with a
     recording stand-in for the third-party range coder object it drives (``encoder.encode([symbol], cdf)`` calls are logged, no
@@ -915,6 +957,8 @@ def main():
         fx_warp()
     if "codec" in which:
         fx_codec()
+    if "codec_random" in which:
+        fx_codec_random()
     if "enhance" in which:
         fx_enhance(newnet1)
     if "stage2" in which:

@@ -26,7 +26,7 @@ def _run(port, *flags, env_extra=None):
 def test_two_rank_inference_and_training_bench_lines():
     d = _run(29541, "--batch", "2", "--size", "256")
     assert d["n_gpus"] == 2 and d["config"]["pairs_per_step"] == 4 and d["scaling"] == "weak" and d["value"] > 0
-    t = _run(29542, "--mode", "train", "--batch", "2", "--size", "256")
+    t = _run(29542, "--mode", "train", "--batch", "2", "--size", "256", "--full")         # the roofline is measured with --full
     assert t["n_gpus"] == 2 and t["config"]["global_batch"] == 4 and t["value"] > 0 and t["roofline"]["kernel"].startswith("wgrad_")
     assert all(v == v for v in t["losses_last_step"].values())    # finite
 
@@ -62,7 +62,7 @@ def test_bench_starts_its_own_ranks_when_no_launcher_is_around():
     d = _run_self("--batch", "2", "--size", "256")
     assert d["n_gpus"] == 2 and d["config"]["pairs_per_step"] == 4 and d["value"] > 0
     assert d["ranks"]["nranks"] == 2 and len(d["ranks"]["per_rank_pairs_per_s"]) == 2 and d["ranks"]["backend"] == "gloo"
-    t = _run_self("--mode", "train", "--batch", "2", "--size", "256")
+    t = _run_self("--mode", "train", "--batch", "2", "--size", "256", "--full")
     assert t["n_gpus"] == 2 and t["config"]["global_batch"] == 4 and t["ranks"]["nranks"] == 2 and "comm" in t          # the comm block itself is measured on RCCL only (gloo has no AVG op)
     s = _run_self("--sweep", "--batch", "1", "--height", "128", "--width", "192")
     assert s["n_gpus"] == 2 and s["ranks"]["nranks"] == 2 and len(s["per_lambda"]) >= 2           # two steps x two ranks touch three of the four lambda-models
