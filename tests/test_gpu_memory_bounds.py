@@ -1,0 +1,1058 @@
+"""Bounds sweep: every operator at edge shapes with NaN / 3.4e38-guarded inputs and poisoned allocations (tests/memguard.py).
+
+The kernels address memory through buffer resources with a 2 GiB record count; an address they must not touch gets an offset
+>= 2^31.  A wrongly computed offset for a ragged tail reads whatever lies next to the tensor -- on fresh allocations usually zeros
+that padding taps multiply away.  Each case here runs
+
+1. plain, on fresh tensors, against a float64 reference of the same operation (inputs rounded to the storage dtype first):
+   fp32 storage within 1e-4 of the output scale, 16-bit within 2e-2, integers bit for bit;
+2. guarded, once per fill (0xFF: NaN; 0x7F: 3.4e38 in f32 / bf16): every input inside a poisoned allocation, every
+   ``torch.empty`` / ``empty_like`` of the package poisoned too, packed weights re-made under poison.  The outputs equal the plain
+   run bit for bit (operators documented to use float atomics: the tolerance of their existing test), are finite, and no guard
+   byte moved;
+
+and records the entry points it launched (``_lib.call_hook``): every declared one must have run.  ``test_every_entry_point_is_declared``
+checks the other direction against include/hesic_hip.h.
+"""
+import contextlib
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import memguard as MG
+from hesic_amd import _lib as L
+from hesic_amd import synthetic
+
+DEV = "cuda"
+CL = torch.channels_last
+FILLS = [MG.NAN_FILL, MG.BIG_FILL]
+BF, H16, F32 = torch.bfloat16, torch.float16, torch.float32
+LEAKY = 0.01
+
+
+def _mods():
+    from hesic_amd import functional, homography, models
+    return [functional, models, homography]
+
+
+def rnd(name, shape, lo=-1.0, hi=1.0):
+    return synthetic._uniform("mb." + name, shape, lo, hi)
+
+
+def rounded(t, dt):
+    """``t`` (fp32) rounded to the storage dtype, kept as fp32."""
+    return t.to(dt).float() if dt != F32 else t
+
+
+def rel_err(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
+
+
+class Case:
+    """``make()`` -> dict of device tensors (the inputs, already in their layout); ``run(inp)`` -> dict of output tensors;
+    ``ref(inp)`` -> dict of float64 CPU tensors for some outputs (None: whole-model cases, whose parity lives in test_gpu_models).
+    ``fmt`` is the compute dtype the case runs under; ``tol`` the reference bar (per output name or one number); ``atol_guard`` the
+    bar of guarded vs plain for atomics (0: bit for bit)."""
+
+    def __init__(self, cid, fmt, entries, make, run, ref=None, tol=None, atol_guard=None):
+        self.id, self.fmt, self.entries, self.make, self.run, self.ref = cid, fmt, set(entries), make, run, ref
+        self.tol = tol if tol is not None else (1e-4 if fmt == F32 else 2e-2)
+        self.atol_guard = atol_guard or {}
+
+
+CASES = []
+
+
+def case(*a, **k):
+    CASES.append(Case(*a, **k))
+
+
+def _cpu64(inp):
+    return {k: (v.detach().cpu().double() if torch.is_tensor(v) and v.is_floating_point() else
+                (v.detach().cpu() if torch.is_tensor(v) else v)) for k, v in inp.items()}
+
+
+def _with_grads(out, named):
+    for k, t in named.items():
+        if t.grad is not None:
+            out["d" + k] = t.grad
+    return out
+
+
+def _leaf(inp, *names):
+    return [inp[n].requires_grad_() for n in names]
+
+
+# ------------------------------------------------------------------------------------------------------------- wide convs
+def _conv_ref(x, w, b, s, p, tr, act=0, in_abs=False):
+    if in_abs:
+        x = x.abs()
+    y = F.conv_transpose2d(x, w, b, s, p, output_padding=s - 1) if tr else F.conv2d(x, w, b, s, p)
+    return torch.relu(y) if act == L.ACT_RELU else F.leaky_relu(y, LEAKY) if act == L.ACT_LEAKY else y
+
+
+def _wide(cid, fmt, Cin, Cout, k, s, tr, B, H, W, grad, entries, act=0):
+    p = k // 2
+    wshape = (Cin, Cout, k, k) if tr else (Cout, Cin, k, k)
+    fan = Cin * k * k / (4 if tr and s == 2 else 1)
+
+    def make():
+        x = rounded(rnd(cid + "x", (B, Cin, H, W), -2, 2), fmt)
+        w = rounded(rnd(cid + "w", wshape) * (3.0 / fan) ** 0.5, fmt)
+        d = dict(x=x.to(DEV, fmt).contiguous(memory_format=CL), w=w.to(DEV), b=rnd(cid + "b", (Cout,), -0.1, 0.1).to(DEV))
+        if grad:
+            Ho, Wo = (H * s, W * s) if tr else ((H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1)
+            d["g"] = rounded(rnd(cid + "g", (B, Cout, Ho, Wo)), fmt).to(DEV, fmt)
+        return d
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        if not grad:
+            with torch.no_grad():
+                return {"y": Fn.conv2d(I["x"], I["w"], I["b"], kernel_size=k, stride=s, padding=p, transposed=tr, act=act)}
+        x, w, b = _leaf(I, "x", "w", "b")
+        y = Fn.conv2d(x, w, b, kernel_size=k, stride=s, padding=p, transposed=tr, act=act)
+        y.backward(I["g"])
+        return _with_grads({"y": y.detach()}, {"x": x, "w": w, "b": b})
+
+    def ref(I):
+        if not grad:
+            return {"y": _conv_ref(I["x"], I["w"], I["b"], s, p, tr, act)}
+        x, w, b = (I[n].requires_grad_() for n in ("x", "w", "b"))
+        y = _conv_ref(x, w, b, s, p, tr, act)
+        y.backward(I["g"])
+        return {"y": y.detach(), "dx": x.grad, "dw": w.grad, "db": b.grad}
+
+    wtol = 2e-4 if fmt == F32 else 3e-2
+    case(cid, fmt, entries, make, run, ref, tol={"y": 1e-4 if fmt == F32 else 2e-2, "dx": 1e-4 if fmt == F32 else 2e-2, "dw": wtol, "db": wtol},
+         atol_guard={"dw": 1e-6, "db": 1e-6})      # the bias column sums (and the fp32 weight route) add with float atomics (wgrad.hip)
+
+
+_WIDE = [
+    # tag, Cin, Cout, k, s, transposed, shapes (B, H, W)
+    ("c5s2_128", 128, 128, 5, 2, False, [(1, 1, 1), (3, 2, 3), (1, 7, 13), (3, 13, 21), (1, 33, 47), (3, 2, 2), (1, 6, 10), (3, 14, 22)]),
+    ("c5s2_64_72", 64, 72, 5, 2, False, [(1, 7, 13), (3, 13, 21)]),
+    ("c5s2_128_192", 128, 192, 5, 2, False, [(3, 2, 3), (1, 33, 47)]),
+    ("c5s1_192_128", 192, 128, 5, 1, False, [(1, 1, 1), (3, 7, 13), (1, 13, 21)]),
+    ("c3s1_288_384", 288, 384, 3, 1, False, [(1, 2, 3), (1, 7, 13)]),
+    ("c1_768_640", 768, 640, 1, 1, False, [(3, 2, 3), (1, 7, 13)]),
+    ("d5s2_128", 128, 128, 5, 2, True, [(1, 1, 1), (3, 2, 3), (1, 7, 13), (3, 13, 21)]),
+    ("d5s2_128_288", 128, 288, 5, 2, True, [(1, 7, 13)]),
+]
+for _tag, _ci, _co, _k, _s, _tr, _shapes in _WIDE:
+    for _B, _H, _W in _shapes:
+        for _fmt in (F32, BF):
+            _grad = _H * _W <= 300 and (_s == 1 or _tr or (_H % 2 == 0 and _W % 2 == 0))    # a stride-2 backward needs even sizes
+            _e = {"hesic_pack_conv_weight"} if not _grad else {"hesic_pack_conv_weight", "hesic_conv2d_wgrad_direct"}
+            _wide(f"{_tag}_{_B}x{_H}x{_W}_{'f32' if _fmt == F32 else 'bf16'}{'_grad' if _grad else ''}", _fmt, _ci, _co, _k, _s, _tr,
+                  _B, _H, _W, _grad, _e)
+
+
+def _into_case(cid, fmt, kind):
+    """Write-boundary cases: the destination sits inside a guard and the channels outside the written slice hold a sentinel."""
+    B, H, W, Cin, Cout, Ctot, off = 3, 7, 13, 128, 72, 256, 64
+    sent = -7.0
+
+    def make():
+        x = rounded(rnd(cid + "x", (B, Ctot if kind == "slice" else Cin, H, W), -2, 2), fmt).to(DEV, fmt).contiguous(memory_format=CL)
+        w = rounded(rnd(cid + "w", (Cout, Cin, 5, 5)) * 0.02, fmt).to(DEV)
+        o = torch.full((B, Ctot, H, W), sent, dtype=fmt, device=DEV).contiguous(memory_format=CL)
+        return dict(x=x, w=w, b=rnd(cid + "b", (Cout,), -0.1, 0.1).to(DEV), out=o)
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        with torch.no_grad():
+            if kind == "into":
+                Fn.conv2d_into(I["x"], I["w"], I["b"], I["out"], off, kernel_size=5, stride=1, padding=2, act=L.ACT_RELU)
+            elif kind == "copy":
+                Fn.copy_into(I["x"], I["out"], off)
+            else:
+                y = Fn.conv2d_slice(I["x"], off, I["w"], I["b"], kernel_size=5, stride=1, padding=2)
+                return {"y": y}
+        o = I["out"]
+        n = Cin if kind == "copy" else Cout
+        outside = torch.cat((o[:, :off], o[:, off + n:]), 1)
+        assert bool((outside == sent).all()), f"{cid}: channels outside [{off}, {off + n}) were written"
+        return {"y": o[:, off:off + n]}
+
+    def ref(I):
+        if kind == "copy":
+            return {"y": I["x"]}
+        if kind == "slice":
+            return {"y": _conv_ref(I["x"][:, off:off + Cin], I["w"], I["b"], 1, 2, False)}
+        return {"y": _conv_ref(I["x"], I["w"], I["b"], 1, 2, False, L.ACT_RELU)}
+
+    ent = {"copy": {"hesic_copy_channels"}}.get(kind, {"hesic_pack_conv_weight"})
+    case(cid, fmt, ent, make, run, ref, tol=0 if kind == "copy" else None)
+
+
+for _fmt in (F32, BF):
+    for _kind in ("into", "copy", "slice"):
+        _into_case(f"{_kind}_3x7x13_{'f32' if _fmt == F32 else 'bf16'}", _fmt, _kind)
+
+
+def _split_k_case(cid, Cout):
+    """The split-K launch (low-resolution layers, fp32 partial tiles in a poisoned workspace), written into a channel slice."""
+    B, Cin, H, Ho = 2, 128, 32, 16
+
+    def make():
+        return dict(x=rounded(rnd(cid + "x", (B, Cin, H, H), -2, 2), BF).to(DEV, BF).contiguous(memory_format=CL),
+                    w=rounded(rnd(cid + "w", (Cout, Cin, 5, 5)) * 0.03, BF).to(DEV), b=rnd(cid + "b", (Cout,), -0.1, 0.1).to(DEV))
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        with torch.no_grad():
+            y = Fn.conv2d(I["x"], I["w"], I["b"], kernel_size=5, stride=2, padding=2, act=L.ACT_LEAKY)
+            lo, hi = Fn.conv2d_latent(I["x"], I["w"], I["b"], kernel_size=5, stride=2, padding=2)
+        return {"y": y, "lo": lo, "hi": hi}
+
+    def ref(I):
+        r = _conv_ref(I["x"], I["w"], I["b"], 2, 2, False)
+        return {"y": F.leaky_relu(r, LEAKY), "lo": r, "hi": r}
+
+    case(cid, BF, {"hesic_conv2d_forward_ws", "hesic_conv2d_forward_f32out"}, make, run, ref, tol={"y": 2e-2, "lo": 2e-2, "hi": 1e-4})
+
+
+_split_k_case("splitk_2x32x32_bf16_c128", 128)
+_split_k_case("splitk_2x32x32_bf16_c192", 192)
+
+
+def _grouped_case(cid, tr):
+    B, Cin, H, W = 3, 128, 7, 13
+
+    def make():
+        d = dict(x=rounded(rnd(cid + "x", (B, Cin, H, W), -2, 2), BF).to(DEV, BF).contiguous(memory_format=CL))
+        for i in range(3):
+            d[f"w{i}"] = rounded(rnd(cid + f"w{i}", (Cin, 128, 5, 5) if tr else (128, Cin, 5, 5)) * 0.03, BF).to(DEV)
+            d[f"b{i}"] = rnd(cid + f"b{i}", (128,), -0.1, 0.1).to(DEV)
+        return d
+
+    kw = dict(kernel_size=5, stride=2 if tr else 1, padding=2, transposed=tr)
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        with torch.no_grad():
+            y, _ = Fn.conv2d_grouped(I["x"], [I[f"w{i}"] for i in range(3)], [I[f"b{i}"] for i in range(3)], Fn.PackedGroup(),
+                                     shared_input=True, acts=[L.ACT_RELU, L.ACT_LEAKY, L.ACT_LEAKY], **kw)
+            y2, _ = Fn.conv2d_grouped(y, [I["w0"], I["w1"]], [I["b0"], I["b1"]], Fn.PackedGroup(), shared_input=False,
+                                      acts=[L.ACT_RELU, L.ACT_NONE], f32_out="only", **kw)
+        return {"y": y, "y2": y2}
+
+    def ref(I):
+        s = 2 if tr else 1
+        acts = (L.ACT_RELU, L.ACT_LEAKY, L.ACT_LEAKY)
+        y = torch.cat([_conv_ref(I["x"], I[f"w{i}"], I[f"b{i}"], s, 2, tr, acts[i]) for i in range(3)], 1)
+        return {"y": y}
+
+    case(cid, BF, {"hesic_conv2d_forward_grouped"}, make, run, ref)
+
+
+_grouped_case("grouped_3x7x13_bf16", False)
+_grouped_case("grouped_tr_3x7x13_bf16", True)
+
+
+# ------------------------------------------------------------------------------------------------------------- image side
+def _image_case(cid, fmt, B, H, W):
+    """3 -> 128 (5x5 s2), 128 -> 3 transposed, 6 -> 3 cat convs at odd widths; forward + backward."""
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+
+    def make():
+        return dict(x=rnd(cid + "x", (B, 3, H, W), 0, 1).to(DEV), w1=rounded(rnd(cid + "w1", (128, 3, 5, 5)) * 0.2, fmt).to(DEV),
+                    b1=rnd(cid + "b1", (128,), -0.1, 0.1).to(DEV),
+                    f=rounded(rnd(cid + "f", (B, 128, Ho, Wo)), fmt).to(DEV, fmt).contiguous(memory_format=CL),
+                    wt=rounded(rnd(cid + "wt", (128, 3, 5, 5)) * 0.05, fmt).to(DEV), bt=rnd(cid + "bt", (3,), -0.1, 0.1).to(DEV),
+                    xb=rounded(rnd(cid + "xb", (B, 3, Ho * 2, Wo * 2)), BF).to(DEV, BF),
+                    wc=rnd(cid + "wc", (3, 6, 5, 5)) * 0.1, bc=rnd(cid + "bc", (3,), -0.1, 0.1),
+                    g1=rounded(rnd(cid + "g1", (B, 128, Ho, Wo)), fmt).to(DEV, fmt), gt=rnd(cid + "gt", (B, 3, Ho * 2, Wo * 2)).to(DEV))
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        keep, Fn.SHAPED_WEIGHTS = Fn.SHAPED_WEIGHTS, False
+        try:
+            x, w1, b1 = _leaf(I, "x", "w1", "b1")
+            y1 = Fn.conv2d(x, w1, b1, kernel_size=5, stride=2, padding=2)
+            y1.backward(I["g1"])
+            f, wt, bt = _leaf(I, "f", "wt", "bt")
+            yt = Fn.conv2d(f, wt, bt, kernel_size=5, stride=2, padding=2, transposed=True)
+            yt.backward(I["gt"])
+            with torch.no_grad():
+                yc = Fn.conv2d_cat(yt.detach(), I["xb"], I["wc"].to(DEV), I["bc"].to(DEV), kernel_size=5, stride=1, padding=2)
+        finally:
+            Fn.SHAPED_WEIGHTS = keep
+        return _with_grads({"y1": y1.detach(), "yt": yt.detach(), "yc": yc}, {"x": x, "w1": w1, "b1": b1, "f": f, "wt": wt, "bt": bt})
+
+    def ref(I):
+        xr = rounded(I["x"].float(), fmt).double().requires_grad_()
+        w1, b1 = I["w1"].requires_grad_(), I["b1"].requires_grad_()
+        y1 = F.conv2d(xr, w1, b1, 2, 2)
+        y1.backward(I["g1"])
+        f, wt, bt = I["f"].requires_grad_(), I["wt"].requires_grad_(), I["bt"].requires_grad_()
+        yt = F.conv_transpose2d(f, wt, bt, 2, 2, output_padding=1)
+        yt.backward(I["gt"])
+        yc = F.conv2d(torch.cat((yt.detach(), I["xb"]), 1), I["wc"], I["bc"], 1, 2)
+        return {"y1": y1.detach(), "yt": yt.detach(), "yc": yc, "dw1": w1.grad, "db1": b1.grad, "df": f.grad, "dwt": wt.grad, "dbt": bt.grad}
+
+    tol = 1e-4 if fmt == F32 else 2e-2
+    e = {"hesic_sconv2d_dgrad", "hesic_sconv2d_wgrad"} | ({"hesic_sconv2d_forward_cat"} if W >= 64 else set())
+    case(cid, fmt, e, make, run, ref, atol_guard={k: 1e-6 for k in ("dw1", "db1", "dwt", "dbt")},      # weight gradients: float atomics
+         tol={"y1": 1e-4 if fmt == F32 else 6e-3, "yt": tol, "yc": 1e-4 if fmt == F32 else 2e-2, "dw1": 3e-2 if fmt != F32 else 2e-4,
+              "db1": 3e-2 if fmt != F32 else 2e-4, "df": tol, "dwt": 3e-2 if fmt != F32 else 2e-4, "dbt": 3e-2 if fmt != F32 else 2e-4})
+
+
+for _fmt in (F32, BF):
+    for _B, _H, _W in [(1, 2, 2), (3, 7, 13), (1, 13, 21), (3, 33, 47), (1, 34, 130)]:
+        _image_case(f"image_{_B}x{_H}x{_W}_{'f32' if _fmt == F32 else 'bf16'}", _fmt, _B, _H, _W)
+
+
+def _image_gdn_case(cid, B, H, W, inv):
+    """g_a_conv1 + GDN in one kernel (bf16), the cat conv with the fused three-channel GDN (fp32)."""
+    def make():
+        sd = {"g.beta": torch.zeros(128), "g.gamma": torch.zeros(128, 128)}
+        synthetic.fill_state_dict_(sd, salt=13)
+        return dict(x=rnd(cid + "x", (B, 3, H, W), 0, 1).to(DEV), w=rounded(rnd(cid + "w", (128, 3, 5, 5)) * 0.25, BF).to(DEV),
+                    b=rnd(cid + "b", (128,), -0.1, 0.1).to(DEV), beta=sd["g.beta"].to(DEV), gamma=sd["g.gamma"].to(DEV),
+                    xa=rnd(cid + "xa", (B, 3, H, W)).to(DEV), xb=rnd(cid + "xb", (B, 3, H, W)).to(DEV),
+                    wc=rnd(cid + "wc", (6, 3, 5, 5) if inv else (3, 6, 5, 5)) * 0.1, bc=rnd(cid + "bc", (3,), -0.1, 0.1),
+                    beta3=rnd(cid + "beta3", (3,), 0.0, 1.5), gamma3=rnd(cid + "gamma3", (3, 3), -0.1, 0.6))
+
+    def run(I):
+        from compressai.layers import GDN
+        from hesic_amd import functional as Fn
+        g = GDN(3, inverse=inv)
+        with torch.no_grad():
+            g.beta.copy_(I["beta3"])
+            g.gamma.copy_(I["gamma3"])
+            g = g.to(DEV)
+            y = Fn.conv2d_gdn(I["x"], I["w"], I["b"], I["beta"], I["gamma"], kernel_size=5, stride=2, padding=2, transposed=False,
+                              inverse=inv, beta_min=1e-6, packer=None, gdn_packer=Fn.PackedGdn())
+            Fn.set_compute_dtype(F32)
+            yc = Fn.conv2d_cat(I["xa"], I["xb"], I["wc"].to(DEV), I["bc"].to(DEV), kernel_size=5, stride=1, padding=2, transposed=inv,
+                               gdn=g, gdn_on_input=inv)
+            Fn.set_compute_dtype(BF)
+        return {"y": y, "yc": yc}
+
+    def ref(I):
+        from oracle import hesic_oracle as O
+        y = O.gdn(F.conv2d(rounded(I["x"].float(), BF).double(), I["w"], I["b"], 2, 2), I["beta"], I["gamma"], inv)
+        beta3 = I["beta3"].double()
+        if inv:
+            yc = F.conv_transpose2d(torch.cat((O.gdn(I["xa"], beta3, I["gamma3"], True), I["xb"]), 1), I["wc"], I["bc"], 1, 2)
+        else:
+            yc = O.gdn(F.conv2d(torch.cat((I["xa"], I["xb"]), 1), I["wc"], I["bc"], 1, 2), beta3, I["gamma3"], False)
+        return {"y": y, "yc": yc}
+
+    e = {"hesic_sconv2d_gdn_forward_prepacked", "hesic_sconv2d_forward_cat_gdn" if W >= 128 else "hesic_gdn_forward_planar"}   # wide maps fuse the GDN(3)
+    case(cid, BF, e, make, run, ref, tol={"y": 1.5e-2, "yc": 2e-5})
+
+
+for _B, _H, _W, _inv in [(3, 2, 2, False), (1, 51, 71, True), (3, 13, 22, False), (1, 34, 130, True)]:
+    _image_gdn_case(f"image_gdn_{_B}x{_H}x{_W}_{'igdn' if _inv else 'gdn'}", _B, _H, _W, _inv)
+
+
+# ------------------------------------------------------------------------------------------------------------- GDN
+def _gdn_case(cid, fmt, Cc, B, H, W, inv):
+    def make():
+        sd = {"g.beta": torch.zeros(Cc), "g.gamma": torch.zeros(Cc, Cc)}
+        synthetic.fill_state_dict_(sd, salt=5 + Cc)
+        x = rounded(rnd(cid + "x", (B, Cc, H, W), -2, 2), fmt)
+        x = x.to(DEV, fmt).contiguous(memory_format=CL) if Cc == 128 else x.to(DEV, fmt)
+        return dict(x=x, beta=sd["g.beta"].to(DEV), gamma=sd["g.gamma"].to(DEV), g=rounded(rnd(cid + "g", (B, Cc, H, W)), fmt).to(DEV, fmt))
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        x, beta, gamma = _leaf(I, "x", "beta", "gamma")
+        y = Fn.gdn(x, beta, gamma, inverse=inv)
+        y.backward(I["g"])
+        return _with_grads({"y": y.detach()}, {"x": x, "beta": beta, "gamma": gamma})
+
+    def ref(I):
+        from oracle import hesic_oracle as O
+        x, beta, gamma = (I[n].requires_grad_() for n in ("x", "beta", "gamma"))
+        y = O.gdn(x, beta, gamma, inv)
+        y.backward(I["g"])
+        return {"y": y.detach(), "dx": x.grad, "dbeta": beta.grad, "dgamma": gamma.grad}
+
+    t = 1e-4 if fmt == F32 else 2e-2
+    e = {"hesic_gdn_forward", "hesic_gdn_backward_acc"} if Cc == 128 else {"hesic_gdn_forward_planar", "hesic_gdn_backward_planar_acc"}
+    case(cid, fmt, e, make, run, ref,
+         tol={"y": t, "dx": t, "dbeta": 1e-3 if fmt == F32 else 3e-2, "dgamma": 1e-3 if fmt == F32 else 3e-2},
+         atol_guard={"dbeta": 1e-5, "dgamma": 1e-5})      # parameter gradients: float atomics (wgrad.hip)
+
+
+for _fmt in (F32, BF):
+    for _Cc in (3, 128):
+        for _B, _H, _W, _inv in [(1, 1, 1, False), (3, 7, 13, True), (1, 33, 47, False)]:
+            _gdn_case(f"gdn{_Cc}_{_B}x{_H}x{_W}_{'igdn' if _inv else 'gdn'}_{'f32' if _fmt == F32 else 'bf16'}", _fmt, _Cc, _B, _H, _W, _inv)
+
+
+# ------------------------------------------------------------------------------------------------------------- warp
+def _warp_case(cid, B, Cc, H, W, ac, inv, cl):
+    def make():
+        import numpy as np
+        Hm = torch.from_numpy(np.stack([synthetic.homography(i) for i in range(B)])).float()
+        x = rnd(cid + "x", (B, Cc, H, W), 0, 1)
+        return dict(x=x.to(DEV).contiguous(memory_format=CL) if cl else x.to(DEV), M=Hm.to(DEV), g=rnd(cid + "g", (B, Cc, H, W)).to(DEV))
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        (x,) = _leaf(I, "x")
+        y = Fn.warp_perspective(x, I["M"], (H, W), align_corners=ac, inverse_map=inv)
+        y.backward(I["g"])
+        return {"y": y.detach(), "dx": x.grad}
+
+    def ref(I):
+        from oracle import hesic_oracle as O
+        M = torch.linalg.inv(I["M"]) if inv else I["M"]
+        x = I["x"].requires_grad_()
+        y = O.warp_perspective(x, M, (H, W), align_corners=ac)
+        y.backward(I["g"])
+        return {"y": y.detach(), "dx": x.grad}
+
+    case(cid, F32, {"hesic_warp_perspective_forward", "hesic_warp_perspective_backward"}, make, run, ref,
+         tol={"y": 1e-4, "dx": 1e-3}, atol_guard={"dx": 1e-5})
+
+
+for _B, _C, _H, _W, _ac, _inv, _cl in [(1, 3, 2, 3, True, False, False), (3, 3, 7, 13, False, False, True), (1, 3, 33, 47, True, True, False),
+                                       (3, 8, 13, 21, False, True, True)]:
+    _warp_case(f"warp_{_B}x{_C}x{_H}x{_W}_ac{int(_ac)}_inv{int(_inv)}{'_nhwc' if _cl else ''}", _B, _C, _H, _W, _ac, _inv, _cl)
+
+
+# ------------------------------------------------------------------------------------------------------------- entropy models
+def _eb_params(Cc):
+    from compressai.entropy_models import EntropyBottleneck
+    torch.manual_seed(0)
+    eb = EntropyBottleneck(Cc)
+    sd = eb.state_dict()
+    synthetic.fill_state_dict_(sd, salt=Cc)
+    return eb, sd
+
+
+def _eb_case(cid, fmt, Cc, B, H, W, train):
+    def make():
+        _, sd = _eb_params(Cc)
+        d = {k.replace(".", "_"): v.to(DEV) for k, v in sd.items() if v.is_floating_point()}
+        z = rnd(cid + "z", (B, Cc, H, W), -6, 6)
+        d["z"] = rounded(z, fmt).to(DEV, fmt).contiguous(memory_format=CL)
+        d["g"] = rnd(cid + "g", (B, Cc, H, W)).to(DEV)
+        if train:
+            d["noise"] = rnd(cid + "n", (B, Cc, H, W), -0.5, 0.5).to(DEV, fmt).contiguous()
+        return d
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        m = [I[f"_matrices_{i}"].requires_grad_() for i in range(5)]
+        b = [I[f"_biases_{i}"].requires_grad_() for i in range(5)]
+        f = [I[f"_factors_{i}"].requires_grad_() for i in range(4)]
+        q = I["quantiles"].requires_grad_()
+        (z,) = _leaf(I, "z")
+        zh, lik = Fn.entropy_bottleneck(z, m, b, f, q, noise=I.get("noise"))
+        ((lik * I["g"]).sum() + zh.float().sum()).backward()
+        aux = Fn.eb_aux_loss([t.detach() for t in m], [t.detach() for t in b], [t.detach() for t in f], q.detach().requires_grad_())
+        out = {"zh": zh.detach(), "lik": lik.detach(), "dz": z.grad, "dq": q.grad, "aux": aux.detach().reshape(1)}
+        for i, t in enumerate(m + b + f):
+            out[f"dp{i}"] = t.grad
+        return out
+
+    def ref(I):
+        from oracle import hesic_oracle as O
+        P = {}
+        for i in range(5):
+            P[f"eb._matrices.{i}"], P[f"eb._biases.{i}"] = I[f"_matrices_{i}"], I[f"_biases_{i}"]
+        for i in range(4):
+            P[f"eb._factors.{i}"] = I[f"_factors_{i}"]
+        P["eb.quantiles"] = I["quantiles"]
+        z = I["z"]
+        noise = I.get("noise")
+        r = {"aux": O.eb_aux_loss(P, "eb.").reshape(1)}
+        if not train:          # the training form (noise) is pinned against the golden vectors in test_gpu_ops
+            zh, lik = O.eb_forward(P, "eb.", z)
+            r.update(zh=zh, lik=lik)
+        return r
+
+    e = {"hesic_eb_forward", "hesic_eb_backward", "hesic_eb_aux_loss"}
+    case(cid, fmt, e, make, run, ref, tol={"zh": None, "lik": 2e-4, "aux": 2e-3},      # zh: bit-exact against the golden vectors in test_gpu_ops
+         atol_guard={"dq": 1e-4, "aux": 1e-4, **{f"dp{i}": 1e-4 for i in range(14)}})
+
+
+for _Cc, _B, _H, _W in [(8, 1, 1, 1), (12, 3, 7, 13), (128, 1, 13, 21), (192, 3, 2, 3)]:
+    for _fmt in (F32, BF):
+        _eb_case(f"eb{_Cc}_{_B}x{_H}x{_W}_{'f32' if _fmt == F32 else 'bf16'}", _fmt, _Cc, _B, _H, _W, train=(_B == 3))
+
+
+def _gmm_case(cid, fmt, M, K, B, H, W, train):
+    def make():
+        d = dict(y=rounded(rnd(cid + "y", (B, M, H, W), -8, 8), fmt).to(DEV, fmt).contiguous(memory_format=CL),
+                 sc=rounded(rnd(cid + "s", (B, K * M, H, W), 0.05, 3.0), fmt).to(DEV, fmt).contiguous(memory_format=CL),
+                 mu=rounded(rnd(cid + "m", (B, K * M, H, W), -4, 4), fmt).to(DEV, fmt).contiguous(memory_format=CL),
+                 w=torch.softmax(rnd(cid + "w", (B, K, M), -2, 2), 1).reshape(B, K * M, 1, 1).to(DEV),
+                 g=rnd(cid + "g", (B, M, H, W)).to(DEV))
+        if train:
+            d["noise"] = rnd(cid + "n", (B, M, H, W), -0.5, 0.5).to(DEV, fmt).contiguous()
+        return d
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        y, sc, mu, w = _leaf(I, "y", "sc", "mu", "w")
+        yh, lik = Fn.gaussian_mixture(y, sc, mu, w, K=K, noise=I.get("noise"))
+        ((lik * I["g"]).sum() + yh.float().sum()).backward()
+        out = _with_grads({"yh": yh.detach(), "lik": lik.detach()}, {"y": y, "sc": sc, "mu": mu, "w": w})
+        s1, m1 = sc.detach()[:, :M], mu.detach()[:, :M]
+        y2, s2, m2 = _leaf({"y": I["y"].detach().clone(), "s": s1.clone(), "m": m1.clone()}, "y", "s", "m")
+        yh2, lik2 = Fn.gaussian_conditional(y2, s2, m2, noise=I.get("noise"))
+        ((lik2 * I["g"]).sum()).backward()
+        with torch.no_grad():
+            out.update(yh_gc=yh2.detach(), lik_gc=lik2.detach(), ds_gc=s2.grad, sym=Fn.quantize_symbols(I["y"].detach(), m1),
+                       sym0=Fn.quantize_symbols(I["y"].detach()),
+                       cdf=Fn.gmm_cdf_tables(sc.detach(), mu.detach(), w.detach(), list(range(0, M, 3)), 6, K, b=B - 1))
+        return out
+
+    def ref(I):
+        from oracle import hesic_oracle as O
+        y, sc, mu, w = I["y"], I["sc"], I["mu"], I["w"].reshape(B, K, M, 1, 1)
+        r = {"sym": torch.round(y - mu[:, :M]).int(), "sym0": torch.round(y).int()}
+        if not train:          # the noise forms are pinned against the golden vectors in test_gpu_ops
+            yh, lik = O.gmm_forward(y, sc, mu, I["w"], K)
+            yg, lg = O.gc_forward(y, sc[:, :M], mu[:, :M])
+            r.update(yh=yh, lik=lik, yh_gc=yg, lik_gc=lg)
+        return r
+
+    case(cid, fmt, {"hesic_gmm_forward", "hesic_gmm_backward", "hesic_gmm_cdf"}, make, run, ref,
+         tol={"yh": None, "yh_gc": None, "lik": 1e-3, "lik_gc": 1e-3, "sym": 0, "sym0": 0},      # yh: bit-exact against the golden vectors
+         atol_guard={"dw": 1e-4})
+
+
+for _M, _K, _B, _H, _W in [(8, 5, 1, 1, 1), (20, 5, 3, 7, 13), (12, 1, 1, 13, 21), (192, 5, 3, 2, 3)]:
+    for _fmt in (F32, BF):
+        _gmm_case(f"gmm_M{_M}K{_K}_{_B}x{_H}x{_W}_{'f32' if _fmt == F32 else 'bf16'}", _fmt, _M, _K, _B, _H, _W, train=(_B == 3))
+
+
+# ------------------------------------------------------------------------------------------------------------- hyper glue
+def _glue_case(cid, fmt, cz, cy, B, h, w):
+    def make():
+        return dict(z=rounded(rnd(cid + "z", (B, cz, h, w), -2, 2), fmt).to(DEV, fmt).contiguous(memory_format=CL),
+                    y1=rounded(rnd(cid + "y", (B, cy, 4 * h, 4 * w), -8, 8), fmt).to(DEV, fmt).contiguous(memory_format=CL),
+                    g=rounded(rnd(cid + "g", (B, cz + cy, 4 * h, 4 * w)), fmt).to(DEV, fmt),
+                    p=rnd(cid + "p", (B, 5 * 8, 1, 1), -2, 2).to(DEV), wl=rnd(cid + "wl", (40, 40, 1, 1)).to(DEV) * 0.1,
+                    bl=rnd(cid + "bl", (40,), -0.1, 0.1).to(DEV), gl=rnd(cid + "gl", (B, 40, 1, 1)).to(DEV),
+                    xm=rounded(rnd(cid + "xm", (B, cy, 4 * h, 4 * w), -2, 2), fmt).to(DEV, fmt).contiguous(memory_format=CL))
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        z, y1 = _leaf(I, "z", "y1")
+        cat = Fn.upsample4_cat(z, y1)
+        cat.backward(I["g"])
+        (z2,) = _leaf({"z": I["z"].detach().clone()}, "z")
+        up = Fn.upsample4(z2)
+        up.backward(I["g"][:, :cz])
+        xm = I["xm"].detach().requires_grad_()
+        sm = Fn.spatial_max(xm, leaky=True)
+        sm.backward(I["gl"][:, :1].expand_as(sm).contiguous())
+        p, wl, bl = _leaf(I, "p", "wl", "bl")
+        pl = Fn.pooled_linear(p, wl, bl)
+        lg = pl.detach().reshape(B, 40).clone().requires_grad_()
+        sw = Fn.softmax_k(lg, 5, 8)
+        sw.backward(I["gl"].reshape(sw.shape))
+        (pl * I["gl"]).sum().backward()
+        mw = Fn.mix_weights(I["p"].detach(), I["wl"].detach(), I["bl"].detach(), 5, 8)
+        return {"cat": cat.detach(), "dz": z.grad, "dy1": y1.grad, "up": up.detach(), "dz2": z2.grad, "sm": sm.detach(), "dxm": xm.grad,
+                "pl": pl.detach(), "dp": p.grad, "dwl": wl.grad, "dbl": bl.grad, "sw": sw.detach(), "dlg": lg.grad, "mw": mw}
+
+    def ref(I):
+        from oracle import hesic_oracle as O
+        up = O.upsample_bilinear_x4(I["z"])
+        xm = I["xm"]
+        pl = F.conv2d(I["p"], I["wl"], I["bl"])
+        return {"cat": torch.cat((up, I["y1"]), 1), "up": up, "sm": F.leaky_relu(torch.amax(xm, dim=(2, 3), keepdim=True), LEAKY),
+                "pl": pl, "mw": O._mix_weights(pl, 5, 8).reshape(B, 40)}
+
+    case(cid, fmt, {"hesic_upsample4_forward", "hesic_upsample4_backward", "hesic_spatial_max", "hesic_spatial_max_backward",
+                    "hesic_pooled_linear_forward", "hesic_pooled_linear_backward", "hesic_softmax_k_forward", "hesic_softmax_k_backward",
+                    "hesic_mix_weights_forward"}, make, run, ref,
+         tol={"cat": 1e-5 if fmt == F32 else 4e-3, "up": 1e-5 if fmt == F32 else 4e-3, "sm": 0, "pl": 1e-5, "mw": None},
+         atol_guard={"dwl": 1e-5, "dbl": 1e-5})
+
+
+for _fmt in (F32, BF):
+    for _cz, _cy, _B, _h, _w in [(12, 20, 1, 1, 1), (128, 192, 3, 2, 3), (12, 20, 3, 3, 5)]:
+        _glue_case(f"glue_{_cz}_{_cy}_{_B}x{_h}x{_w}_{'f32' if _fmt == F32 else 'bf16'}", _fmt, _cz, _cy, _B, _h, _w)
+
+
+SENTINEL = -7.25
+
+
+def _slots(n):
+    """``n`` fp64 accumulators at the odd indices of a (2n + 1)-element tensor: zeros (the kernels add into them) between spare slots
+    holding a non-zero sentinel that must come back unchanged."""
+    t = torch.full((2 * n + 1,), SENTINEL, dtype=torch.float64, device=DEV)
+    t[1::2] = 0
+    return t
+
+
+def _reduce_case(cid, shape_l, shape_p, crop):
+    def make():
+        a = rnd(cid + "a", shape_p)
+        b = rnd(cid + "b", shape_p)
+        if crop:
+            a = rnd(cid + "a", shape_p[:3] + (shape_p[3] + 3,))[..., 1:shape_p[3] + 1]
+        return dict(l=rnd(cid + "l", shape_l, 1e-9, 1.0).to(DEV), a=a.to(DEV) if crop else a.to(DEV),
+                    b=b.to(DEV).contiguous(memory_format=CL), l2=rnd(cid + "l2", shape_l, 1e-9, 1.0).to(DEV).contiguous(memory_format=CL),
+                    acc=_slots(2), rd=_slots(4))
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        acc, rd = I["acc"], I["rd"]
+        s1 = Fn.sum_log2(I["l"])
+        s2 = Fn.sum_sq_diff(I["a"], I["b"])
+        Fn.sum_log2(I["l2"], out=acc[1:2])
+        Fn.sum_sq_diff(I["a"], I["b"], out=acc[3:4])
+        Fn.rd_sums([I["l"], I["l2"]], [rd[1:2], rd[3:4]], [(I["a"], I["b"]), (I["b"], I["a"])], [rd[5:6], rd[7:8]])
+        torch.cuda.synchronize()
+        for name, t in (("acc", acc), ("rd", rd)):
+            spare = t[0::2].cpu()
+            assert bool((spare == SENTINEL).all()), f"{cid}: a spare slot of {name} was written: {spare.tolist()}"
+        return {"s1": s1, "s2": s2, "acc": acc[1::2], "rd": rd[1::2]}
+
+    def ref(I):
+        sl = torch.log2(I["l"]).sum().reshape(1)
+        sl2 = torch.log2(I["l2"]).sum().reshape(1)
+        sq = ((I["a"] - I["b"]) ** 2).sum().reshape(1)
+        return {"s1": sl, "s2": sq, "acc": torch.cat((sl2, sq)), "rd": torch.cat((sl, sl2, sq, sq))}
+
+    case(cid, F32, {"hesic_sum_log2", "hesic_sum_sq_diff", "hesic_rd_sums"}, make, run, ref, tol=1e-6,
+         atol_guard={k: 1e-6 for k in ("s1", "s2", "acc", "rd")})
+
+
+_reduce_case("reduce_1x8x1x1", (1, 8, 1, 1), (1, 3, 1, 1), False)
+_reduce_case("reduce_3x20x7x13_crop", (3, 20, 7, 13), (3, 3, 13, 21), True)
+_reduce_case("reduce_2x192x13x21", (2, 192, 13, 21), (2, 3, 33, 47), False)
+
+
+# ------------------------------------------------------------------------------------------------------------- enhancement (c32)
+def _c32_case(cid, fmt, B, H, W):
+    def make():
+        return dict(x=rounded(rnd(cid + "x", (B, 32, H, W), -2, 2), fmt).to(DEV, fmt).contiguous(memory_format=CL),
+                    r1=rounded(rnd(cid + "r1", (B, 32, H, W)), fmt).to(DEV, fmt).contiguous(memory_format=CL),
+                    r2=rounded(rnd(cid + "r2", (B, 32, H, W)), fmt).to(DEV, fmt).contiguous(memory_format=CL),
+                    w=rnd(cid + "w", (32, 32, 3, 3)).to(DEV) * 0.1, b=rnd(cid + "b", (32,), -0.2, 0.2).to(DEV),
+                    w2=rnd(cid + "w2", (32, 32, 3, 3)).to(DEV) * 0.1, b2=rnd(cid + "b2", (32,), -0.2, 0.2).to(DEV),
+                    w3=rnd(cid + "w3", (3, 32, 3, 3)).to(DEV) * 0.1, b3=rnd(cid + "b3", (3,), -0.2, 0.2).to(DEV),
+                    w6=rnd(cid + "w6", (32, 6, 3, 3)).to(DEV) * 0.2, img=rnd(cid + "img", (B, 3, H, W), 0, 1).to(DEV),
+                    img2=rnd(cid + "img2", (B, 3, H, W), 0, 1).to(DEV))
+
+    def run(I):
+        from hesic_amd import functional as Fn
+        with torch.no_grad():
+            out = {"y0": Fn.conv3x3_c32(I["x"], I["w"], I["b"]),
+                   "y2": Fn.conv3x3_c32(I["x"], I["w"], None, act=2, res1=I["r1"], res2=I["r2"]),
+                   "y3": Fn.conv3x3_c32(I["x"], I["w3"], I["b3"], res1=I["img"]),
+                   "y6": Fn.conv3x3_c32_img6(I["img"], I["img2"], I["w6"], I["b"]),
+                   "p6": Fn.pack_images_c32(I["img"], I["img2"]),
+                   "rb": Fn.resblock_c32(I["x"], I["w"], I["b"], I["w2"], I["b2"]),
+                   "rb2": Fn.resblock_c32(I["x"], I["w"], I["b"], I["w2"], I["b2"], res2=I["r2"])}
+        if fmt == BF:
+            dw, db = Fn.conv3x3_c32_wgrad(I["x"], I["r1"], I["w"], I["b"])
+            out.update(dw=dw, db=db)
+        return out
+
+    def ref(I):
+        wr = lambda t: rounded(t.float(), fmt).double()
+        x = I["x"]
+        c = F.conv2d(x, wr(I["w"]), I["b"], 1, 1)
+        h = F.leaky_relu(F.conv2d(x, wr(I["w"]), I["b"], 1, 1), LEAKY)
+        rb = F.leaky_relu(F.conv2d(rounded(h.float(), fmt).double(), wr(I["w2"]), I["b2"], 1, 1), LEAKY) + x
+        r = {"y0": c, "y2": F.leaky_relu(F.conv2d(x, wr(I["w"]), None, 1, 1), LEAKY) + I["r1"] + I["r2"],
+             "y3": F.conv2d(x, wr(I["w3"]), I["b3"], 1, 1) + I["img"],
+             "y6": F.conv2d(rounded(torch.cat((I["img"], I["img2"]), 1).float(), fmt).double(), wr(I["w6"]), I["b"], 1, 1),
+             "rb": rb, "rb2": rb + I["r2"]}
+        if fmt == BF:
+            xg = x.clone().requires_grad_()
+            wg, bg = I["w"].clone().requires_grad_(), I["b"].clone().requires_grad_()
+            F.conv2d(xg, wg, bg, 1, 1).backward(I["r1"])
+            r.update(dw=wg.grad, db=bg.grad)
+        return r
+
+    e = {"hesic_conv3x3_c32_forward", "hesic_conv3x3_c32_forward_img6", "hesic_pack_images_c32", "hesic_resblock_c32_forward"}
+    if fmt == BF:
+        e.add("hesic_conv3x3_c32_wgrad")
+    t = 1e-2 if fmt == BF else 2e-3
+    case(cid, fmt, e, make, run, ref, tol={"y0": t, "y2": t, "y3": 1e-4, "y6": t, "rb": 2 * t, "rb2": 2 * t, "dw": 1e-2, "db": 1e-2})
+
+
+for _fmt in (BF, H16):
+    for _H, _W in [(1, 5), (3, 15), (37, 16), (3, 17), (1, 33)]:
+        _c32_case(f"c32_2x{_H}x{_W}_{'bf16' if _fmt == BF else 'f16'}", _fmt, 2, _H, _W)
+
+
+# entry points (without the "hesic_" prefix) the whole-model / encoder cases launch on the calling thread
+_ENTRIES = {
+    "hilo_encoder_3x64x80_bf16": {"conv2d_forward_hilo", "conv2d_forward_hilo_w1", "conv2d_gdn_forward_hilo_out", "gdn_pack_params", "gdn_pack_params_lo",
+        "pack_conv_weight", "pack_conv_weight_shaped", "sconv2d_gdn_forward_hilo", "sconv2d_gdn_forward_hilo_out1",
+        "sconv_pack_weight_image_hilo", "sconv_pack_weight_image_hilo_out1"},
+    "hilo_encoder_3x64x80_f16": {"conv2d_forward_hilo", "conv2d_forward_hilo_w1", "conv2d_gdn_forward_hilo_out", "gdn_pack_params", "gdn_pack_params_lo",
+        "pack_conv_weight", "pack_conv_weight_shaped", "sconv2d_gdn_forward_hilo", "sconv2d_gdn_forward_hilo_out1",
+        "sconv_pack_weight_image_hilo_out1", "sconv_pack_weight_image_hilo_scaled"},
+    "model_hsic_3x64x192_bf16": {"conv2d_forward", "conv2d_forward_f32out", "conv2d_forward_grouped", "conv2d_forward_hilo",
+        "conv2d_forward_ws", "conv2d_gdn_forward", "copy_channels", "eb_forward_f32in", "eb_pack_table", "eb_prepare_params",
+        "gdn_pack_params", "gdn_pack_params_lo", "gmm_forward_f32in", "mix_weights_forward", "pack_conv_weight",
+        "pack_conv_weight_shaped", "pack_conv_weight_shaped_tr", "pack_conv_weight_slice", "round", "sconv2d_forward_cat_gdn",
+        "sconv2d_forward_prepacked", "sconv2d_gdn_forward_hilo", "sconv2d_gdn_forward_prepacked", "sconv_pack_weight_image",
+        "sconv_pack_weight_image_hilo", "spatial_max", "upsample4_forward", "warp_perspective_forward"},
+    "model_hsic_3x64x192_f16": {"conv2d_forward", "conv2d_forward_f32out", "conv2d_forward_grouped", "conv2d_forward_hilo",
+        "conv2d_forward_ws", "conv2d_gdn_forward", "copy_channels", "eb_forward_f32in", "eb_pack_table", "eb_prepare_params",
+        "gdn_pack_params", "gdn_pack_params_lo", "gmm_forward_f32in", "mix_weights_forward", "pack_conv_weight",
+        "pack_conv_weight_shaped", "pack_conv_weight_shaped_tr", "pack_conv_weight_slice", "round", "sconv2d_forward_cat_gdn",
+        "sconv2d_forward_prepacked", "sconv2d_gdn_forward_hilo", "sconv2d_gdn_forward_prepacked", "sconv_pack_weight_image",
+        "sconv_pack_weight_image_hilo_scaled", "spatial_max", "upsample4_forward", "warp_perspective_forward"},
+    "model_joint_3x64x192_bf16": {"conv2d_forward", "conv2d_forward_f32out", "conv2d_forward_hilo", "conv2d_forward_ws",
+        "conv2d_gdn_forward", "copy_channels", "eb_forward_f32in", "eb_pack_table", "eb_prepare_params", "gdn_pack_params",
+        "gdn_pack_params_lo", "gmm_forward_f32in", "pack_conv_weight", "pack_conv_weight_shaped", "pack_conv_weight_shaped_tr", "round",
+        "sconv2d_forward_cat_gdn", "sconv2d_forward_prepacked", "sconv2d_gdn_forward_hilo", "sconv2d_gdn_forward_prepacked",
+        "sconv_pack_weight_image", "sconv_pack_weight_image_hilo", "warp_perspective_forward"},
+    "model_joint_3x64x192_f16": {"conv2d_forward", "conv2d_forward_f32out", "conv2d_forward_hilo", "conv2d_forward_ws",
+        "conv2d_gdn_forward", "copy_channels", "eb_forward_f32in", "eb_pack_table", "eb_prepare_params", "gdn_pack_params",
+        "gdn_pack_params_lo", "gmm_forward_f32in", "pack_conv_weight", "pack_conv_weight_shaped", "pack_conv_weight_shaped_tr", "round",
+        "sconv2d_forward_cat_gdn", "sconv2d_forward_prepacked", "sconv2d_gdn_forward_hilo", "sconv2d_gdn_forward_prepacked",
+        "sconv_pack_weight_image", "sconv_pack_weight_image_hilo_scaled", "warp_perspective_forward"},
+    "train_hsic_2x64x64_bf16": {"act_backward", "eb_scatter_grads", "gdn_backward_partial", "gdn_backward_planar_acc", "log_backward", "sq_diff_backward",
+        "adam_step", "conv2d_forward", "conv2d_forward_ws", "conv2d_gdn_forward_train", "conv2d_wgrad_finish_batched_n",
+        "conv2d_wgrad_partial_batched", "copy_channels", "eb_aux_loss", "eb_forward", "eb_pack_table", "gdn_forward_planar",
+        "gdn_pack_params", "gdn_pack_params_batched", "gdn_param_finish_batched", "gmm_forward", "pack_conv_weight",
+        "pack_conv_weights_batched", "pooled_linear_forward", "rd_loss_combine", "rd_sums", "sconv2d_forward",
+        "sconv2d_forward_prepacked", "sconv2d_gdn_forward_prepacked", "sconv_pack_weight_image", "softmax_k_forward", "spatial_max",
+        "upsample4_forward", "warp_perspective_forward"},
+}
+
+
+def _ents(cid):
+    return {"hesic_" + n for n in _ENTRIES[cid]}
+
+
+# ------------------------------------------------------------------------------------------------------------- hi/lo analysis
+def _hilo_case(cid, fmt, B, H, W, cl=False, entries=None):
+    def make():
+        x = synthetic.stereo_batch(2, B, H, W)[0].to(DEV)
+        return dict(x=x.contiguous(memory_format=CL) if cl else x)
+
+    def run(I):
+        from hesic_amd import functional as Fn, models
+        enc = models.Encoder1(128, 192)
+        synthetic.fill_state_dict_(enc.state_dict())
+        enc = enc.to(DEV).eval()
+        out = {}
+        with torch.no_grad():
+            for mode in ("x3", "x3c2", "x2"):
+                Fn.set_analysis_precision(mode)
+                lo, y = enc.latent_hilo(I["x"], True, True)
+                out["lo_" + mode], out["y_" + mode] = lo.t, y
+        return out
+
+    def ref(I):
+        from oracle import hesic_oracle as O
+        from hesic_amd import models
+        enc = models.Encoder1(128, 192)
+        synthetic.fill_state_dict_(enc.state_dict())
+        P = {"e." + k: v.double() for k, v in enc.state_dict().items()}
+        y = O.g_a(P, "e.", I["x"])
+        return {"y_x3": y, "y_x2": y}
+
+    case(cid, fmt, entries if entries is not None else _ents(cid), make, run, ref, tol={"y_x3": 2e-3, "y_x2": 2e-2})
+
+
+# even-width planar fp32 images take the fused hi/lo conv1 + GDN kernel; odd widths and channels-last images the im2col form:
+# hesic_im2col_hilo, then conv1 as a 1x1 hi/lo implicit GEMM with the GDN epilogue (models.Encoder1.latent_hilo)
+_IM2COL = {"hesic_im2col_hilo", "hesic_conv2d_forward_hilo"}
+for _fmt in (BF, H16):
+    _t = 'bf16' if _fmt == BF else 'f16'
+    _hilo_case(f"hilo_encoder_3x64x80_{_t}", _fmt, 3, 64, 80)
+    _hilo_case(f"hilo_encoder_im2col_3x64x81_{_t}", _fmt, 3, 64, 81, entries=_IM2COL)
+    _hilo_case(f"hilo_encoder_im2col_nhwc_1x66x96_{_t}", _fmt, 1, 66, 96, cl=True, entries=_IM2COL)
+
+
+# ------------------------------------------------------------------------------------------------------------- homography net, MS-SSIM
+def _homog_case(cid, B, Cc, H, W):
+    def make():
+        corners = torch.tensor([[[0, 0], [W - 1, 0], [0, H - 1], [W - 1, H - 1]]], dtype=torch.float32).repeat(B, 1, 1)
+        return dict(x=rnd(cid + "x", (B, Cc, H, W), -2, 2).to(DEV).contiguous(memory_format=CL),
+                    src=corners.to(DEV), dst=(corners + rnd(cid + "d", (B, 4, 2), -3, 3)).to(DEV),
+                    delta=rnd(cid + "dl", (B, 4, 2), -3, 3).to(DEV))
+
+    def run(I):
+        from hesic_amd import homography as Hg
+        with torch.no_grad():
+            return {"mp": Hg.max_pool2(I["x"]), "H": Hg.get_perspective_transform(I["src"], I["dst"]),
+                    "Hd": Hg.h_matrix_from_delta(I["src"], I["delta"], H, W, 128)}
+
+    def ref(I):
+        from oracle import hesic_oracle as O
+        return {"mp": F.max_pool2d(I["x"], 2), "H": O.get_perspective_transform(I["src"], I["dst"]),
+                "Hd": O.h_matrix_from_delta(I["src"], I["delta"], H, W, 128)}
+
+    case(cid, F32, {"hesic_maxpool2_forward", "hesic_perspective_transform", "hesic_h_from_delta"}, make, run, ref,
+         tol={"mp": 0, "H": 1e-4, "Hd": 1e-4})
+
+
+_homog_case("homography_1x64x7x13", 1, 64, 7, 13)
+_homog_case("homography_3x128x33x47", 3, 128, 33, 47)
+
+
+def _msssim_case(cid, B, H, W):
+    def make():
+        a = rnd(cid + "a", (B, 3, H, W + 5), 0, 1)[..., 2:W + 2]          # a column-cropped view: strided, odd sizes
+        b = rnd(cid + "b", (B, 3, H, W), 0, 1).contiguous(memory_format=CL)
+        return dict(a=a.to(DEV), b=b.to(DEV))
+
+    def run(I):
+        from hesic_amd import models
+        return {"ms": models.ms_ssim(I["a"], I["b"])}
+
+    def ref(I):
+        from oracle import hesic_oracle as O
+        return {"ms": O.ms_ssim(I["a"], I["b"])}
+
+    case(cid, F32, {"hesic_ssim_scale", "hesic_avgpool2_pad"}, make, run, ref, tol={"ms": 1e-4}, atol_guard={"ms": 1e-9})
+
+
+_msssim_case("msssim_2x163x171", 2, 163, 171)
+_msssim_case("msssim_1x177x165", 1, 177, 165)
+
+
+# ------------------------------------------------------------------------------------------------------------- whole models
+def _model_case(cid, kind, fmt, B, H, W):
+    def make():
+        x1, x2, Hm = synthetic.stereo_batch(3, B, H, W)
+        return dict(x1=x1.to(DEV), x2=x2.to(DEV), Hm=Hm.to(DEV))
+
+    def run(I):
+        from hesic_amd import models
+        net = (models.HSIC if kind == "hsic" else models.HSICJoint)()
+        synthetic.fill_state_dict_(net.state_dict())
+        net = net.to(DEV).eval()
+        with torch.no_grad():
+            o = net(I["x1"], I["x2"], I["Hm"])
+        out = {k: o[k] for k in ("x1_hat", "x2_hat", "y1_hat", "y2_hat")}
+        out.update({"lik_" + k: v for k, v in o["likelihoods"].items()})
+        return out
+
+    case(cid, fmt, _ents(cid), make, run, None)
+
+
+def _train_case(cid, B, H, W):
+    def make():
+        x1, x2, Hm = synthetic.stereo_batch(4, B, H, W)
+        return dict(x1=x1.to(DEV), x2=x2.to(DEV), Hm=Hm.to(DEV))
+
+    def run(I):
+        from hesic_amd import models
+        from hesic_amd.train import Trainer
+        torch.manual_seed(0)
+        net = models.HSIC()
+        synthetic.fill_state_dict_(net.state_dict())
+        net = net.to(DEV)
+        tr = Trainer(net, lr=1e-4, aux_lr=1e-3, lmbda=0.0067)
+        crit = tr.step(I["x1"], I["x2"], I["Hm"])
+        out = {k: v.reshape(1) for k, v in crit.items()}
+        out["grads"] = tr.main_group.flat_g.detach().clone()          # this step's gradients (zeroed at its start)
+        out["aux_grads"] = tr.aux_group.flat_g.detach().clone()
+        out["params"] = tr.main_group.flat_p.detach().clone()
+        out["aux_params"] = tr.aux_group.flat_p.detach().clone()
+        return out
+
+    # The weight and GDN-parameter gradients are summed with float atomics, so they vary in the last bits from run to run.  Adam's first
+    # step moves a parameter by ~lr * sign(g): where a gradient is ~0, that last-bit noise flips the sign and the parameter lands 2 * lr
+    # away.  Two plain runs differ by up to 1.4e-5 of the gradient scale and by 2 * lr in ~0.16 % of the parameters.  So the gradients
+    # are held to 5e-5 of their scale, the parameters to the size of such a flip (2 * lr, lr = 1e-4 / aux 1e-3); a read of poison
+    # shows as a non-finite or far-off gradient.
+    case(cid, BF, _ents(cid), make, run, None, atol_guard={"grads": 5e-5, "aux_grads": 5e-5, "params": 2.2e-4, "aux_params": 2.2e-3,
+                                                          "loss": 1e-5, "bpp_loss": 1e-5, "mse_loss": 1e-5, "aux_loss": 1e-5})
+
+
+for _kind in ("hsic", "joint"):
+    for _fmt in (BF, H16):
+        _model_case(f"model_{_kind}_3x64x192_{'bf16' if _fmt == BF else 'f16'}", _kind, _fmt, 3, 64, 192)
+_train_case("train_hsic_2x64x64_bf16", 2, 64, 64)
+
+
+# ------------------------------------------------------------------------------------------------------------- running a case
+def _launch(c, fill=None, offset=0):
+    from hesic_amd import functional as Fn
+    Fn.set_compute_dtype(c.fmt)
+    Fn.invalidate_weight_cache()
+    inp = c.make()
+    if fill is not None:
+        inp = {k: MG.guarded(v, fill=fill, name=f"{c.id}:{k}", offset=offset) if torch.is_tensor(v) else v for k, v in inp.items()}
+    names = set()
+    with _recording(names):
+        if fill is None:
+            out = c.run(inp)
+            torch.cuda.synchronize()
+        else:
+            with MG.poisoned_allocations(_mods(), fill):
+                out = c.run(inp)
+                torch.cuda.synchronize()
+    if fill is not None:
+        MG.check_all([v for v in inp.values() if torch.is_tensor(v)])
+    return inp, {k: v.detach() for k, v in out.items() if v is not None}, names
+
+
+@contextlib.contextmanager
+def _recording(names):
+    """Every entry point launched inside the block, from any thread: ``_lib.call_hook`` sees the calling thread only, and autograd runs
+    the backward pass on a thread of its own."""
+    real = L.call
+
+    def call(name, *args):
+        names.add(name)
+        return real(name, *args)
+
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(L, "call", call)
+        yield
+
+
+def _same(c, k, a, b):
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return False
+    tol = c.atol_guard.get(k, 0)
+    if tol == 0:
+        return torch.equal(a, b)
+    return float((a.double() - b.double()).abs().max()) <= tol * max(1.0, float(b.double().abs().max()))
+
+
+def _diff(a, b):
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return f"{tuple(a.shape)} {a.dtype} vs {tuple(b.shape)} {b.dtype}"
+    d = (a.double() - b.double()).abs()
+    n = int((a != b).sum())
+    return f"{n} of {a.numel()} elements differ, max |diff| {float(d.max()):.3e}, scale {float(b.double().abs().max()):.3e}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", CASES, ids=[c.id for c in CASES])
+def test_case(c):
+    inp, plain, names = _launch(c)
+    missing = c.entries - names
+    assert not missing, f"{c.id}: declared entry points not launched: {sorted(missing)} (launched: {sorted(names)})"
+    if c.ref is not None:
+        want = c.ref(_cpu64(inp))
+        for k, r in want.items():
+            got = plain[k].cpu()
+            tol = c.tol.get(k) if isinstance(c.tol, dict) else c.tol
+            if tol is None:
+                continue
+            if tol == 0 or not r.is_floating_point():
+                assert torch.equal(got.double() if r.is_floating_point() else got.long(), r if r.is_floating_point() else r.long()), \
+                    f"{c.id}: {k} differs from the reference"
+            else:
+                assert rel_err(got, r) < tol, f"{c.id}: {k} rel err {rel_err(got, r):.2e} >= {tol}"
+    for fill in FILLS:
+        _, got, _ = _launch(c, fill)
+        for k, v in plain.items():
+            g = got[k]
+            if g.is_floating_point():
+                assert bool(torch.isfinite(g).all()), f"{c.id} fill 0x{fill:02X}: {k} is not finite"
+            assert _same(c, k, g, v), f"{c.id} fill 0x{fill:02X}: {k} differs from the plain run ({_diff(g, v)})"
+
+
+# ------------------------------------------------------------------------------------------------------------- alignment pass
+_ALIGN_IDS = (
+    "c5s2_128_3x13x21_bf16", "c5s2_128_1x6x10_bf16_grad", "d5s2_128_3x2x3_bf16_grad", "c5s1_192_128_3x7x13_bf16_grad", "gdn128_3x7x13_igdn_bf16",
+    "eb128_1x13x21_bf16", "gmm_M20K5_3x7x13_bf16", "glue_128_192_3x2x3_bf16", "c32_2x3x17_bf16", "c32_2x3x15_f16",
+    "image_3x33x47_f32", "image_3x7x13_bf16", "warp_3x3x7x13_ac0_inv0_nhwc", "reduce_3x20x7x13_crop", "image_gdn_3x13x22_gdn",
+    "into_3x7x13_bf16", "copy_3x7x13_bf16", "hilo_encoder_im2col_3x64x81_bf16")
+ALIGN_CASES = [c for c in CASES if c.id in _ALIGN_IDS]
+assert len(ALIGN_CASES) == len(_ALIGN_IDS), sorted(set(_ALIGN_IDS) - {c.id for c in ALIGN_CASES})
+
+# outputs that may differ from the aligned run in the last bits, and why (every other output must be bit-identical)
+ALIGN_TOL = {
+    # hesic_gmm_forward takes its pair kernel only when the fp32 mixture weights are 8-byte aligned; 4 bytes past a boundary the generic
+    # kernel runs instead (a deliberate dispatch, same formula, another fp32 evaluation order): ~1 ulp of the likelihood
+    ("gmm_M20K5_3x7x13_bf16", "lik"): 1e-6,
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", ALIGN_CASES, ids=[c.id for c in ALIGN_CASES])
+def test_alignment(c):
+    """Views that reach a kernel without a copy: 16-bit NHWC tensors 16 bytes past a 256-byte boundary (a batch slice with C % 8 == 0),
+    fp32 images 4 bytes past one (a batch slice of an image with odd H*W).  The outputs equal the aligned run."""
+    _, plain, _ = _launch(c)
+    from hesic_amd import functional as Fn
+    Fn.set_compute_dtype(c.fmt)
+    Fn.invalidate_weight_cache()
+    inp = c.make()
+    moved = {}
+    for k, v in inp.items():
+        if torch.is_tensor(v) and v.is_floating_point() and v.dim() == 4:
+            off = 16 if v.element_size() == 2 else 4
+            moved[k] = MG.guarded(v, fill=MG.NAN_FILL, name=f"{c.id}:{k}", offset=off)
+        else:
+            moved[k] = v
+    with MG.poisoned_allocations(_mods(), MG.NAN_FILL):
+        out = c.run(moved)
+        torch.cuda.synchronize()
+    MG.check_all([v for v in moved.values() if torch.is_tensor(v)])
+    for k, v in plain.items():
+        g = out[k].detach()
+        if g.is_floating_point():
+            assert bool(torch.isfinite(g).all()), f"{c.id}: {k} is not finite at a 16 / 4-byte offset"
+        tol = ALIGN_TOL.get((c.id, k))
+        ok = _same(c, k, g, v) or (tol is not None and float((g.double() - v.double()).abs().max()) <= tol * float(v.double().abs().max()))
+        assert ok, f"{c.id}: {k} differs at a 16 / 4-byte offset ({_diff(g, v)})"
+
+
+# ------------------------------------------------------------------------------------------------------------- declared coverage
+NOT_LAUNCHING = {
+    "hesic_abi_version": "library query", "hesic_h16_format": "library query", "hesic_last_error": "error string",
+    "hesic_stream_synchronize": "host synchronisation", "hesic_memcpy_async": "a copy engine transfer, no kernel",
+    "hesic_probe_mfma_loop": "a clock / throughput probe for profiling, no operator",
+    "hesic_conv2d_variant": "host query of the kernel variant", "hesic_conv2d_set_phase_fusion": "host switch",
+    "hesic_conv2d_hilo_set_acc_scale": "host setting for the next hi/lo launch", "hesic_conv2d_wgrad_nsplit": "host query",
+    "hesic_gdn_backward_partial_ok": "host query",
+}
+
+# launching entry points that no Python code calls (they appear only in _lib._SIGS): no operator of the package can reach them
+NO_PYTHON_CALLER = {
+    "hesic_cast": "no Python call site",
+    "hesic_conv2d_wgrad": "no Python call site (the wrappers use hesic_conv2d_wgrad_direct)",
+    "hesic_unpack_conv_wgrad": "no Python call site (unpacks hesic_conv2d_wgrad's layout)",
+    "hesic_conv2d_wgrad_finish_batched": "no Python call site (the wrappers use hesic_conv2d_wgrad_finish_batched_n)",
+    "hesic_gdn_backward": "no Python call site (the wrappers use hesic_gdn_backward_acc / _partial)",
+    "hesic_sconv2d_gdn_forward": "no Python call site (the wrappers use hesic_sconv2d_gdn_forward_prepacked)",
+    "hesic_sconv2d_gdn_forward_train": "no Python call site",
+}
+
+# live routes no case reaches yet (a gap of this sweep, listed so it stays visible)
+NOT_YET_COVERED = {
+    "hesic_conv2d_wgrad_partial": "deferred weight-gradient finish with functional.WGRAD_PARTIAL_BATCH = False",
+    "hesic_gmm_cdf_rows": "bit-stream tables of models.HSIC.compress / decompress",
+    "hesic_gmm_cdf_dyn": "bit-stream tables of models.HSIC.compress / decompress",
+    "hesic_joint_step": "joint decoder of the real bit-stream (models.HSICJoint.decompress)",
+    "hesic_joint_decode_groups": "joint decoder of the real bit-stream (models.HSICJoint.decompress)",
+    "hesic_joint_decode_groups_tape": "joint decoder of the real bit-stream (models.HSICJoint.decompress)",
+}
+
+
+def test_every_entry_point_is_declared():
+    """Every launching entry point of include/hesic_hip.h is declared by some case (or excluded above with a reason).  No GPU needed."""
+    declared = set().union(*(c.entries for c in CASES))
+    excluded = {s for s in L.declared_symbols() if s.endswith(("_ws_bytes", "_ws_bytes_n"))} | set(NOT_LAUNCHING) | set(NO_PYTHON_CALLER) \
+        | set(NOT_YET_COVERED)
+    missing = [s for s in L.declared_symbols() if s not in declared and s not in excluded]
+    assert not missing, f"entry points no memory-bounds case declares: {missing}"
+    assert not (declared & excluded), sorted(declared & excluded)
+    assert declared <= set(L.declared_symbols()), sorted(declared - set(L.declared_symbols()))
+
+
+def test_entry_points_without_a_caller_really_have_none():
+    """``NO_PYTHON_CALLER`` stays true: none of its names appears in the package outside the ctypes signature table.  No GPU needed."""
+    import glob
+    import os
+    pkg = os.path.dirname(L.__file__)
+    for path in glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True):
+        if os.path.basename(path) == "_lib.py":
+            continue
+        text = open(path).read()
+        used = [n for n in NO_PYTHON_CALLER if f'"{n}"' in text]
+        assert not used, f"{os.path.relpath(path, pkg)} calls {used}: move them out of NO_PYTHON_CALLER and give them a case"
