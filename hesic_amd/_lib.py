@@ -19,6 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhesic_hip.so")
 LIB_PATH_F16 = os.path.join(_HERE, "libhesic_hip_f16.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_hip.h")
+STEREO_H_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_stereo_h.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -222,6 +223,20 @@ _SIGS = {
     "hesic_im2col_hilo": ([_vp, _P(_i64), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
 }
 
+# include/hesic_stereo_h.h: the stereo homography estimator (hesic_amd.stereo_h), in both libraries
+_u32 = C.c_uint32
+_STEREO_H_SIGS = {
+    "hesic_stereo_h_det_elems": ([_i32, _i32], _i64),
+    "hesic_stereo_h_ws_bytes": ([_i32, _i32, _i32, _i32, _i32], C.c_size_t),
+    "hesic_stereo_h_integral": ([_vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp], _i32),
+    "hesic_stereo_h_hessian": ([_vp, _i32, _i32, _i32, _vp, _vp], _i32),
+    "hesic_stereo_h_keypoints": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp], _i32),
+    "hesic_stereo_h_describe": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp], _i32),
+    "hesic_stereo_h_match": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp], _i32),
+    "hesic_stereo_h_ransac": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _u32, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp],
+                              _i32),
+}
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -230,6 +245,13 @@ _lib = None                     # the active library (None until first use)
 def declared_symbols():
     """Every ``hesic_*`` function declared in include/hesic_hip.h (used by the ABI test)."""
     with open(HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
+def declared_stereo_h_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_stereo_h.h (used by the stereo-homography ABI test)."""
+    with open(STEREO_H_HEADER_PATH) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
@@ -253,7 +275,7 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} exports no hesic_abi_version -- not this package's library; {rebuild}") from None
         if ver != ABI_VERSION:
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
-        for name, (args, res) in _SIGS.items():
+        for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

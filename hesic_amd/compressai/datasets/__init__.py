@@ -8,7 +8,9 @@ compressai/datasets/utils.py:68-214).  CPU-side data prepar
   ``homography(img1, img2) -> 3x3 | None``; a precomputed sidecar ``root/<split>/H/<stem>.{npy,txt}`` holding the 3x3 matrix
   of the FULL images (re-expressed in crop coordinates: both views are cropped at the same offset t, so H_crop = T(-t) H T(t));
   OpenCV's SURF route when ``cv2.xfeatures2d`` exists.  No source -> the item is ``(img1, img2)`` only, which is also what the
-  reference returns when RANSAC fails (utils.py:189-197);
+  reference returns when RANSAC fails (utils.py:189-197).  This package provides the first two sources without OpenCV:
+  ``hesic_amd.stereo_h.HipHomography()`` is such a callable (SURF + ratio matching + RANSAC in HIP, per crop on the GPU), and
+  ``python -m hesic_amd.stereo_h ROOT`` writes the ``H/<stem>.npy`` sidecars of a whole folder once;
 * the HomographyNet inputs of the ``_real`` scripts (utils.py:161-186): both crops resized to 256 x 256, normalised with the
   channel-mean of the ImageNet statistics, averaged to grey, one random 128 x 128 window with its corner coordinates.
 """
