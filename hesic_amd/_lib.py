@@ -233,6 +233,9 @@ _STEREO_H_SIGS = {
     "hesic_stereo_h_keypoints": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp], _i32),
     "hesic_stereo_h_describe": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp], _i32),
     "hesic_stereo_h_match": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp], _i32),
+    "hesic_stereo_h_orient": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
+    "hesic_stereo_h_describe_ex": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp], _i32),
+    "hesic_stereo_h_match_ex": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp], _i32),
     "hesic_stereo_h_ransac": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _u32, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp],
                               _i32),
 }

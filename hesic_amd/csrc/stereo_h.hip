@@ -5,13 +5,17 @@
 //   2. Fast-Hessian              hessian_kernel (20 layers), nms_kernel<false/true> (per-row counts, exclusive scan, ordered writes),
 //                                select_kernel (strongest max_kp by a radix select on the response bits, kept in generation order)
 //   3. U-SURF descriptor         describe_kernel (one wave per keypoint)
-//   4. matching                  match_kernel (f32 MFMA distance tiles, top-2 in registers), compact_matches_kernel
+//      oriented / 128-d SURF     orient_kernel (dominant direction, one wave per keypoint), describe_ex_kernel<64 / 128> (the
+//                                descriptor in the keypoint's frame; (1, 0) reproduces describe_kernel)
+//   4. matching                  match_kernel<64 / 128> (f32 MFMA distance tiles, top-2 in registers), compact_matches_kernel
 //   5. RANSAC                    ransac_kernel (one lane per hypothesis, one wave per block so that B = 1 still fills 32
 //                                blocks; every block stages the pair's matches in LDS)
 //   6. best + refit              finish_kernel (best hypothesis, inlier mask, normalised least-squares DLT + 10 LM steps, fp64)
 // Every sum has a fixed order and nothing depends on atomics' order, so a result is bit-identical run to run and does not depend on the
 // other pairs of the batch.  The fp32 arithmetic is restated operation by operation in tests/stereo_h_ref.py; contraction into fused
 // multiply-adds is switched off here so that restatement can follow it.
+#include <cmath>
+
 #include "common.h"
 #include "../../include/hesic_stereo_h.h"
 
@@ -415,24 +419,205 @@ __global__ void __launch_bounds__(64) describe_kernel(const int* __restrict__ Ia
     }
 }
 
+// ------------------------------------------------------------------------------------------------ 3b. oriented / extended SURF
+// Orientation (OpenCV SURF's SURFInvoker): Haar responses of size g = 2 round(2 s) at the 109 grid points (i, j), i^2 + j^2 < 36,
+// spaced s around the keypoint, each weighted by G[i + 6] G[j + 6] (13-tap Gaussian, sigma 2.5); the 60-degree window, slid in
+// steps of 5 degrees, whose summed response is longest gives the direction.  Angles come from OpenCV's fastAtan2 polynomial in
+// fp32 so that the restatement reproduces them bit for bit.
+constexpr int ORI_SAMPLES = 109, ORI_WINDOWS = 72;
+
+struct OriTable {
+    float w[ORI_SAMPLES];                                   // G[i + 6] * G[j + 6] in fp32
+    signed char i[ORI_SAMPLES], j[ORI_SAMPLES];             // row-major: i outer, j inner
+};
+
+OriTable ori_table() {
+    double g[13], sum = 0;
+    for (int k = 0; k < 13; ++k) {
+        g[k] = std::exp(-(double)((k - 6) * (k - 6)) / (2.0 * 2.5 * 2.5));
+        sum += g[k];
+    }
+    float G[13];
+    for (int k = 0; k < 13; ++k) G[k] = (float)(g[k] / sum);
+    OriTable t{};
+    int q = 0;
+    for (int i = -6; i <= 6; ++i)
+        for (int j = -6; j <= 6; ++j)
+            if (i * i + j * j < 36) {
+                t.w[q] = G[i + 6] * G[j + 6];
+                t.i[q] = (signed char)i;
+                t.j[q] = (signed char)j;
+                ++q;
+            }
+    return t;
+}
+
+// OpenCV's fastAtan2 (degrees in [0, 360]), every step in fp32
+__device__ __forceinline__ float fast_atan2_deg(float y, float x) {
+    constexpr float R2D = (float)(180.0 / 3.14159265358979323846);
+    constexpr float P1 = 0.9997878412794807f * R2D, P3 = -0.3258083974640975f * R2D, P5 = 0.1555786518463281f * R2D,
+                    P7 = -0.04432655554792128f * R2D;
+    constexpr float EPS = (float)2.220446049250313080847e-16;   // (float)DBL_EPSILON
+    const float ax = fabsf(x), ay = fabsf(y);
+    float a;
+    if (ax >= ay) {
+        const float c = ay / (ax + EPS), c2 = c * c;
+        a = (((P7 * c2 + P5) * c2 + P3) * c2 + P1) * c;
+    } else {
+        const float c = ax / (ay + EPS), c2 = c * c;
+        a = 90.f - (((P7 * c2 + P5) * c2 + P3) * c2 + P1) * c;
+    }
+    if (x < 0) a = 180.f - a;
+    if (y < 0) a = 360.f - a;
+    return a;
+}
+
+// one wave per keypoint: lanes take samples q and q + 64, then windows w and w + 64; lane 0 keeps the first longest window.
+// Out: (cos, sin) of the direction, (1, 0) when no window sums to a non-zero response.
+__global__ void __launch_bounds__(64) orient_kernel(const int* __restrict__ Iall, int H, int W, const float4* __restrict__ kp_all,
+                                                    const int* __restrict__ n_kp, int max_kp, OriTable tab, float2* __restrict__ ori_all) {
+    __shared__ float sX[ORI_SAMPLES], sY[ORI_SAMPLES], wmod[ORI_WINDOWS], wx[ORI_WINDOWS], wy[ORI_WINDOWS];
+    __shared__ int sA[ORI_SAMPLES];
+    const int k = blockIdx.x, n = blockIdx.y, lane = threadIdx.x;
+    if (k >= n_kp[n]) return;
+    const int* I = Iall + (int64_t)n * (H + 1) * (W + 1);
+    const float4 kp = kp_all[(int64_t)n * max_kp + k];
+    const float s = kp.z * 1.2f / 9.f;
+    const int g = 2 * (int)rintf(2.f * s), h = g / 2;
+    const float half = (float)(g - 1) / 2.f;
+    for (int q = lane; q < ORI_SAMPLES; q += 64) {
+        const int x0 = (int)rintf(kp.x + (float)tab.i[q] * s - half);
+        const int y0 = (int)rintf(kp.y + (float)tab.j[q] * s - half);
+        float X = 0.f, Y = 0.f;
+        int ang = -1;                                       // -1: the box leaves the image, the sample is skipped
+        if (x0 >= 0 && y0 >= 0 && x0 + g <= W && y0 + g <= H) {
+            const int64_t gx = box_sum(I, H, W, y0, y0 + g, x0 + h, x0 + g) - box_sum(I, H, W, y0, y0 + g, x0, x0 + h);
+            const int64_t gy = box_sum(I, H, W, y0 + h, y0 + g, x0, x0 + g) - box_sum(I, H, W, y0, y0 + h, x0, x0 + g);
+            X = (float)gx * tab.w[q];
+            Y = (float)gy * tab.w[q];
+            ang = (int)rintf(fast_atan2_deg(Y, X));
+        }
+        sX[q] = X;
+        sY[q] = Y;
+        sA[q] = ang;
+    }
+    __syncthreads();
+    for (int w = lane; w < ORI_WINDOWS; w += 64) {
+        const int w0 = 5 * w;
+        float sx = 0.f, sy = 0.f;
+        for (int q = 0; q < ORI_SAMPLES; ++q) {
+            const int d = abs(sA[q] - w0);
+            if (sA[q] >= 0 && (d < 30 || d > 330)) {
+                sx += sX[q];
+                sy += sY[q];
+            }
+        }
+        wmod[w] = sx * sx + sy * sy;
+        wx[w] = sx;
+        wy[w] = sy;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        float best = 0.f, bx = 0.f, by = 0.f;
+        for (int w = 0; w < ORI_WINDOWS; ++w)
+            if (wmod[w] > best) { best = wmod[w]; bx = wx[w]; by = wy[w]; }
+        float2 o = make_float2(1.f, 0.f);
+        if (best > 0.f) {
+            const float r = sqrtf(bx * bx + by * by);
+            o = make_float2(bx / r, by / r);
+        }
+        ori_all[(int64_t)n * max_kp + k] = o;
+    }
+}
+
+// describe_kernel in the keypoint's frame (ori = nullptr: upright) with D = 64 or 128 components.  The sample (u, v) sits at
+// kp + s R(phi) (u - 9.5, v - 9.5); its axis-aligned Haar responses are rotated into the frame, dx' = c dx + s dy, dy' = -s dx + c dy.
+// With (c, s) = (1, 0) every product by 0 vanishes exactly and D = 64 gives describe_kernel's bits.  D = 128 splits each sum by the
+// sign of the other response, in OpenCV's order: dx, |dx| over dy >= 0; dx, |dx| over dy < 0; dy, |dy| over dx >= 0; dy, |dy| over dx < 0.
+template <int D>
+__global__ void __launch_bounds__(64) describe_ex_kernel(const int* __restrict__ Iall, int H, int W, const float4* __restrict__ kp_all,
+                                                         const float2* __restrict__ ori_all, const int* __restrict__ n_kp, int max_kp,
+                                                         float* __restrict__ desc_all, float* __restrict__ nrm_all) {
+    static_assert(D == 64 || D == 128, "64- or 128-d SURF");
+    __shared__ float sdx[400], sdy[400], comp[D];
+    const int k = blockIdx.x, n = blockIdx.y, lane = threadIdx.x;
+    if (k >= n_kp[n]) return;
+    const int* I = Iall + (int64_t)n * (H + 1) * (W + 1);
+    const float4 kp = kp_all[(int64_t)n * max_kp + k];
+    float c = 1.f, sn = 0.f;
+    if (ori_all) {
+        const float2 o = ori_all[(int64_t)n * max_kp + k];
+        c = o.x;
+        sn = o.y;
+    }
+    const float s = kp.z * 1.2f / 9.f;
+    const int hs = max(1, (int)rintf(s));
+    for (int q = lane; q < 400; q += 64) {
+        const int v = q / 20, u = q % 20;
+        const float fu = (float)u - 9.5f, fv = (float)v - 9.5f;
+        const int px = (int)rintf(kp.x + (fu * c - fv * sn) * s);
+        const int py = (int)rintf(kp.y + (fu * sn + fv * c) * s);
+        const float dx = (float)(box_sum(I, H, W, py - hs, py + hs, px, px + hs) - box_sum(I, H, W, py - hs, py + hs, px - hs, px));
+        const float dy = (float)(box_sum(I, H, W, py, py + hs, px - hs, px + hs) - box_sum(I, H, W, py - hs, py, px - hs, px + hs));
+        const float rx = c * dx + sn * dy, ry = -sn * dx + c * dy;
+        const double du = u - 9.5, dv = v - 9.5;
+        const float gw = (float)exp(-(du * du + dv * dv) / (2.0 * 3.3 * 3.3));
+        sdx[q] = gw * rx;
+        sdy[q] = gw * ry;
+    }
+    __syncthreads();
+    for (int cc = lane; cc < D; cc += 64) {
+        const int per = D / 16, sub = cc / per, kind = cc % per, sy = sub >> 2, sx = sub & 3;
+        const float* src = (D == 64 ? kind < 2 : kind < 4) ? sdx : sdy;
+        const float* oth = src == sdx ? sdy : sdx;
+        const bool neg = D == 128 && (kind & 2), absv = kind & 1;
+        float acc = 0.f;
+        for (int vv = 0; vv < 5; ++vv)
+            for (int uu = 0; uu < 5; ++uu) {
+                const int i = (sy * 5 + vv) * 20 + sx * 5 + uu;
+                const float a = src[i];
+                if (D == 64 || (oth[i] < 0.f) == neg) acc += absv ? fabsf(a) : a;
+            }
+        comp[cc] = acc;
+    }
+    __syncthreads();
+    float ss = 0.f;
+    for (int cc = 0; cc < D; ++cc) ss = ss + comp[cc] * comp[cc];
+    const float nrm = sqrtf(ss);
+    float d[D / 64];
+    for (int r = 0; r < D / 64; ++r) {
+        d[r] = nrm > 0 ? comp[lane + 64 * r] / nrm : 0.f;
+        desc_all[((int64_t)n * max_kp + k) * D + lane + 64 * r] = d[r];
+    }
+    __syncthreads();
+    for (int r = 0; r < D / 64; ++r) comp[lane + 64 * r] = d[r];
+    __syncthreads();
+    if (lane == 0) {
+        float acc = 0.f;
+        for (int cc = 0; cc < D; ++cc) acc = fmaf(comp[cc], comp[cc], acc);
+        nrm_all[(int64_t)n * max_kp + k] = acc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ 4. matching
 // d^2(q, t) = (|a|^2 + |b|^2) - 2 a.b: a.b on v_mfma_f32_16x16x4_f32 (exact fp32 products, k-ordered accumulation), one wave per
 // 16 queries sweeping the whole train set in tiles of 16; each lane keeps the top-2 (distance, then index) of its 4 query rows over
-// its train column, the 16 columns merge by butterfly.  The distance matrix never leaves registers.
+// its train column, the 16 columns merge by butterfly.  The distance matrix never leaves registers.  D: descriptor width (64 / 128).
 __device__ __forceinline__ bool lessdi(float a, int i, float b, int j) { return a < b || (a == b && i < j); }
 
+template <int D>
 __global__ void __launch_bounds__(256) match_kernel(const float* __restrict__ desc_all, const float* __restrict__ nrm_all,
                                                     const int* __restrict__ n_kp, int B, int max_kp, int* __restrict__ best_t) {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int q0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
     const int n1 = n_kp[b], n2 = n_kp[B + b];
     if (q0 >= n1) return;
-    const float* d1 = desc_all + (int64_t)b * max_kp * 64;
-    const float* d2 = desc_all + (int64_t)(B + b) * max_kp * 64;
+    const float* d1 = desc_all + (int64_t)b * max_kp * D;
+    const float* d2 = desc_all + (int64_t)(B + b) * max_kp * D;
     const int r16 = lane & 15, kq = lane >> 4;
-    float a[16];
+    float a[D / 4];
     const int qa = q0 + r16;
-    for (int kk = 0; kk < 16; ++kk) a[kk] = qa < n1 ? d1[(int64_t)qa * 64 + 4 * kk + kq] : 0.f;
+    for (int kk = 0; kk < D / 4; ++kk) a[kk] = qa < n1 ? d1[(int64_t)qa * D + 4 * kk + kq] : 0.f;
     float na[4], bd1[4], bd2[4];
     int bi1[4], bi2[4];
     for (int r = 0; r < 4; ++r) {
@@ -444,8 +629,8 @@ __global__ void __launch_bounds__(256) match_kernel(const float* __restrict__ de
     for (int t0 = 0; t0 < n2; t0 += 16) {
         const int tb = t0 + r16;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int kk = 0; kk < 16; ++kk) {
-            const float bv = tb < n2 ? d2[(int64_t)tb * 64 + 4 * kk + kq] : 0.f;
+        for (int kk = 0; kk < D / 4; ++kk) {
+            const float bv = tb < n2 ? d2[(int64_t)tb * D + 4 * kk + kq] : 0.f;
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], bv, acc, 0, 0, 0);
         }
         if (tb < n2) {
@@ -923,7 +1108,7 @@ extern "C" int hesic_stereo_h_match(const float* desc, const float* nrm, const i
     WS_CHECK(L.total);
     int* best_t = (int*)((char*)ws + L.best_t);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(match_kernel, dim3((max_kp + 63) / 64, B), dim3(256), 0, s, desc, nrm, (const int*)n_kp, B, max_kp, best_t);
+    hipLaunchKernelGGL(match_kernel<64>, dim3((max_kp + 63) / 64, B), dim3(256), 0, s, desc, nrm, (const int*)n_kp, B, max_kp, best_t);
     hipLaunchKernelGGL(compact_matches_kernel, dim3(B), dim3(1024), 0, s, best_t, (const int*)n_kp, max_kp, (int2*)matches, (int*)n_match);
     HESIC_LAUNCH_RETURN("stereo_h_match");
 }
@@ -945,4 +1130,39 @@ extern "C" int hesic_stereo_h_ransac(const float* kp, const int32_t* matches, co
     hipLaunchKernelGGL(finish_kernel, dim3(B), dim3(256), 0, s, (const float4*)kp, (const int2*)matches, (const int*)n_match, B, max_kp,
                        n_hyp, hc, he, hh, H_out, (int*)valid, (int*)inliers, (int*)best, inlier_mask);
     HESIC_LAUNCH_RETURN("stereo_h_ransac");
+}
+
+extern "C" int hesic_stereo_h_orient(const int32_t* I, const float* kp, const int32_t* n_kp, int N, int H, int W, int max_kp, float* ori,
+                                     void* stream) {
+    HESIC_CHECK_ARG(I && kp && n_kp && ori && N > 0 && N <= 65535 && H > 0 && W > 0 && max_kp > 0 && max_kp <= HESIC_STEREO_H_MAX_KEYPOINTS,
+                    "stereo_h_orient: bad arguments");
+    hipLaunchKernelGGL(orient_kernel, dim3(max_kp, N), dim3(64), 0, (hipStream_t)stream, (const int*)I, H, W, (const float4*)kp,
+                       (const int*)n_kp, max_kp, ori_table(), (float2*)ori);
+    HESIC_LAUNCH_RETURN("stereo_h_orient");
+}
+
+extern "C" int hesic_stereo_h_describe_ex(const int32_t* I, const float* kp, const float* ori, const int32_t* n_kp, int N, int H, int W,
+                                          int max_kp, int dim, float* desc, float* nrm, void* stream) {
+    HESIC_CHECK_ARG(I && kp && n_kp && desc && nrm && N > 0 && N <= 65535 && H > 0 && W > 0 && max_kp > 0 &&
+                    max_kp <= HESIC_STEREO_H_MAX_KEYPOINTS, "stereo_h_describe_ex: bad arguments");
+    HESIC_CHECK_ARG(dim == 64 || dim == 128, "stereo_h_describe_ex: dim %d, 64 or 128 expected", dim);
+    auto kern = dim == 64 ? describe_ex_kernel<64> : describe_ex_kernel<128>;
+    hipLaunchKernelGGL(kern, dim3(max_kp, N), dim3(64), 0, (hipStream_t)stream, (const int*)I, H, W, (const float4*)kp, (const float2*)ori,
+                       (const int*)n_kp, max_kp, desc, nrm);
+    HESIC_LAUNCH_RETURN("stereo_h_describe_ex");
+}
+
+extern "C" int hesic_stereo_h_match_ex(const float* desc, const float* nrm, const int32_t* n_kp, int B, int H, int W, int max_kp, int n_hyp,
+                                       int dim, void* ws, size_t ws_bytes, int32_t* matches, int32_t* n_match, void* stream) {
+    HESIC_CHECK_ARG(desc && nrm && n_kp && matches && n_match && B > 0 && B <= 65535 && max_kp > 0 && max_kp <= HESIC_STEREO_H_MAX_KEYPOINTS &&
+                    n_hyp > 0, "stereo_h_match_ex: bad arguments");
+    HESIC_CHECK_ARG(dim == 64 || dim == 128, "stereo_h_match_ex: dim %d, 64 or 128 expected", dim);
+    const WsLayout L = ws_layout(B, H, W, max_kp, n_hyp);
+    WS_CHECK(L.total);
+    int* best_t = (int*)((char*)ws + L.best_t);
+    hipStream_t s = (hipStream_t)stream;
+    auto kern = dim == 64 ? match_kernel<64> : match_kernel<128>;
+    hipLaunchKernelGGL(kern, dim3((max_kp + 63) / 64, B), dim3(256), 0, s, desc, nrm, (const int*)n_kp, B, max_kp, best_t);
+    hipLaunchKernelGGL(compact_matches_kernel, dim3(B), dim3(1024), 0, s, best_t, (const int*)n_kp, max_kp, (int2*)matches, (int*)n_match);
+    HESIC_LAUNCH_RETURN("stereo_h_match_ex");
 }

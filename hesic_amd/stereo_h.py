@@ -8,9 +8,12 @@ same-size pairs in the HIP kernels of ``hesic_amd/csrc/stereo_h.hip`` (C ABI ``i
    0.114 R + 0.587 G + 0.299 B) and an exact int32 integral image;
 2. the Fast-Hessian detector with OpenCV SURF's defaults (4 octaves, 3 layers + 2, box filters 9/15/21/27/33 doubling per octave,
    ``hessianThreshold`` 100), 3x3x3 non-maximum suppression, sub-pixel / sub-scale quadratic fit; the strongest ``max_keypoints``;
-3. **upright** SURF descriptors (U-SURF, 64-d).  This departs from the reference, which uses oriented SURF: the HESIC datasets are
-   rectified side-by-side views with no in-plane rotation, where upright descriptors match better.  Oriented SURF and the 128-d
-   (extended) descriptor are not provided;
+3. SURF descriptors, by default **upright** and 64-d (U-SURF).  This departs from the reference, whose ``SURF_create()`` defaults
+   to oriented 64-d SURF: the HESIC datasets are rectified side-by-side views with no in-plane rotation, where upright descriptors
+   match better.  ``upright=False`` assigns each keypoint OpenCV SURF's dominant direction (109 Haar samples within 6 s, the longest
+   sum over 60-degree windows) and describes it in that frame, which makes pairs with in-plane rotation usable; ``extended=True``
+   gives the 128-d descriptor (each sum split by the sign of the other response).  ``upright=False, extended=False`` is the
+   reference's configuration.  The descriptors keep the integral-image Haar form of U-SURF rather than OpenCV's resampled window;
 4. 2-NN matching of view 1 (query) against view 2 (train) on the matrix cores, ratio test d1^2 < 0.49 d2^2;
 5. RANSAC with a fixed number of hypotheses drawn by a counter hash of (seed, pair, hypothesis, draw), inlier bar 5 px;
 6. a least-squares DLT over the best hypothesis's inliers and 10 Levenberg-Marquardt steps, as ``findHomography`` refines.
@@ -61,8 +64,8 @@ class _Workspace:
         return self.ws
 
 
-def estimate_homography(img1, img2, *, max_keypoints=4096, hypotheses=2048, seed=0, first_pair=0, pair_ids=None, return_details=False,
-                        _ws=None):
+def estimate_homography(img1, img2, *, max_keypoints=4096, hypotheses=2048, seed=0, first_pair=0, pair_ids=None, upright=True,
+                        extended=False, return_details=False, _ws=None):
     """``H`` (left pixel -> right pixel) of B same-size stereo pairs.
 
     img1, img2: (B, 3, H, W) device tensors, uint8 or float in [0, 1] (quantised to uint8 as rint(x * 255) before the grey step).
@@ -71,9 +74,14 @@ def estimate_homography(img1, img2, *, max_keypoints=4096, hypotheses=2048, seed
     ``get_H`` returns None.  The RANSAC sampling of pair b is keyed by its pair number: ``pair_ids[b]`` (a sequence of B integers),
     or ``first_pair + b`` when ``pair_ids`` is not given.  Both views must have the same dtype.
 
+    ``upright`` (default True): U-SURF, every keypoint described in the image axes; False: each keypoint gets its dominant direction
+    and is described in that frame (rotation-invariant matching).  ``extended`` (default False): 64-d descriptors; True: 128-d.
+    ``upright=False, extended=False`` is the reference's ``cv2.xfeatures2d.SURF_create()``; the defaults keep the upright 64-d path.
+
     ``return_details`` adds a dict of the stages: ``integral`` (2B, H+1, W+1) int32 (view 1, then view 2), ``hessian`` (2B, n) float32,
-    ``keypoints`` / ``descriptors`` (lists of 2B tensors: [x, y, size, response] and 64-d), ``matches`` (list of B (M, 2) int32
-    [query, train]), ``inlier_mask`` (list of B (M,) bool) and ``best`` (B,) the winning hypothesis."""
+    ``keypoints`` / ``descriptors`` (lists of 2B tensors: [x, y, size, response] and 64- or 128-d), ``orientations`` (with
+    ``upright=False``: list of 2B (n, 2) [cos, sin], x right and y down), ``matches`` (list of B (M, 2) int32 [query, train]),
+    ``inlier_mask`` (list of B (M,) bool) and ``best`` (B,) the winning hypothesis."""
     if img1.dtype != img2.dtype:
         raise ValueError(f"estimate_homography: the two views differ in dtype ({img1.dtype} vs {img2.dtype}); pass both as uint8 "
                          "or both as float in [0, 1]")
@@ -104,13 +112,23 @@ def estimate_homography(img1, img2, *, max_keypoints=4096, hypotheses=2048, seed
     kp = torch.empty((2 * B, K, 4), dtype=torch.float32, device=dev)
     n_kp = torch.empty((2 * B,), dtype=torch.int32, device=dev)
     L.call("hesic_stereo_h_keypoints", L.ptr(det), B, H, W, K, NH, L.ptr(ws), ws.numel(), L.ptr(kp), L.ptr(n_kp), s)
-    desc = torch.empty((2 * B, K, 64), dtype=torch.float32, device=dev)
+    D = 128 if extended else 64
+    desc = torch.empty((2 * B, K, D), dtype=torch.float32, device=dev)
     nrm = torch.empty((2 * B, K), dtype=torch.float32, device=dev)
-    L.call("hesic_stereo_h_describe", L.ptr(I), L.ptr(kp), L.ptr(n_kp), 2 * B, H, W, K, L.ptr(desc), L.ptr(nrm), s)
     matches = torch.empty((B, K, 2), dtype=torch.int32, device=dev)
     n_match = torch.empty((B,), dtype=torch.int32, device=dev)
-    L.call("hesic_stereo_h_match", L.ptr(desc), L.ptr(nrm), L.ptr(n_kp), B, H, W, K, NH, L.ptr(ws), ws.numel(), L.ptr(matches),
-           L.ptr(n_match), s)
+    ori = None
+    if upright and not extended:                       # U-SURF 64-d: the original entry points
+        L.call("hesic_stereo_h_describe", L.ptr(I), L.ptr(kp), L.ptr(n_kp), 2 * B, H, W, K, L.ptr(desc), L.ptr(nrm), s)
+        L.call("hesic_stereo_h_match", L.ptr(desc), L.ptr(nrm), L.ptr(n_kp), B, H, W, K, NH, L.ptr(ws), ws.numel(), L.ptr(matches),
+               L.ptr(n_match), s)
+    else:
+        if not upright:
+            ori = torch.empty((2 * B, K, 2), dtype=torch.float32, device=dev)
+            L.call("hesic_stereo_h_orient", L.ptr(I), L.ptr(kp), L.ptr(n_kp), 2 * B, H, W, K, L.ptr(ori), s)
+        L.call("hesic_stereo_h_describe_ex", L.ptr(I), L.ptr(kp), L.ptr(ori), L.ptr(n_kp), 2 * B, H, W, K, D, L.ptr(desc), L.ptr(nrm), s)
+        L.call("hesic_stereo_h_match_ex", L.ptr(desc), L.ptr(nrm), L.ptr(n_kp), B, H, W, K, NH, D, L.ptr(ws), ws.numel(),
+               L.ptr(matches), L.ptr(n_match), s)
     Hout = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
     valid = torch.empty((B,), dtype=torch.int32, device=dev)
     inliers = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -129,6 +147,8 @@ def estimate_homography(img1, img2, *, max_keypoints=4096, hypotheses=2048, seed
         "matches": [matches[p, :nm[p]] for p in range(B)],
         "inlier_mask": [mask[p, :nm[p]].bool() for p in range(B)],
     }
+    if ori is not None:
+        details["orientations"] = [ori[n, :nk[n]] for n in range(2 * B)]
     return out + (details,)
 
 
@@ -138,11 +158,13 @@ class HipHomography:
     returns None and its loader yields ``(img1, img2)``.  The device workspace is kept between calls of the same crop size.
 
     It runs on the GPU inside ``__getitem__``: use it with ``DataLoader(num_workers=0)``, or with worker processes started by
-    ``multiprocessing_context="spawn"`` (a forked worker cannot use the parent's HIP context)."""
+    ``multiprocessing_context="spawn"`` (a forked worker cannot use the parent's HIP context).  ``upright`` / ``extended`` select
+    the descriptor as in ``estimate_homography``."""
 
-    def __init__(self, device="cuda", max_keypoints=4096, hypotheses=2048, seed=0):
+    def __init__(self, device="cuda", max_keypoints=4096, hypotheses=2048, seed=0, upright=True, extended=False):
         self.device = torch.device(device)
         self.max_keypoints, self.hypotheses, self.seed = max_keypoints, hypotheses, seed
+        self.upright, self.extended = upright, extended
         self._ws = _Workspace()
 
     def __call__(self, img1, img2):
@@ -150,7 +172,7 @@ class HipHomography:
         t2 = torch.from_numpy(np.ascontiguousarray(img2)).permute(2, 0, 1).unsqueeze(0).to(self.device)
         with torch.cuda.device(self.device):
             H, valid, _ = estimate_homography(t1, t2, max_keypoints=self.max_keypoints, hypotheses=self.hypotheses, seed=self.seed,
-                                              _ws=self._ws)
+                                              upright=self.upright, extended=self.extended, _ws=self._ws)
         if not bool(valid[0]):
             return None
         return H[0].cpu().numpy()
@@ -164,13 +186,15 @@ def _image_size(path):
         return im.size
 
 
-def write_sidecars(root, splits=("train", "test"), batch=8, overwrite=False, estimator=None, seed=0, log=print):
+def write_sidecars(root, splits=("train", "test"), batch=8, overwrite=False, estimator=None, seed=0, log=print, upright=True,
+                   extended=False):
     """Write ``root/<split>/H/<stem>.npy`` (fp64, the full images' H) for every pair of the stereo folder that has none (all with
     ``overwrite``).  Pairs are grouped by size from their file headers and estimated ``batch`` at a time; only the pairs of the current
     batch are decoded (with the loader's reader), so memory does not grow with the folder.  The RANSAC pair number of a pair is its
     index in the split's sorted file list, so its ``H`` depends neither on the batching nor on which sidecars already exist.  An invalid
     pair gets no file (the loader then yields ``(img1, img2)`` for it, as the reference does on a RANSAC failure).
-    ``estimator(x1, x2, pair_ids) -> (H, valid)`` on (B, 3, H, W) uint8 CPU tensors replaces the GPU estimate.
+    ``estimator(x1, x2, pair_ids) -> (H, valid)`` on (B, 3, H, W) uint8 CPU tensors replaces the GPU estimate; ``upright`` /
+    ``extended`` select the descriptor of the GPU estimate as in ``estimate_homography``.
     Returns (written, invalid, skipped)."""
     from .compressai.datasets import _read_rgb
     import glob
@@ -205,7 +229,7 @@ def write_sidecars(root, splits=("train", "test"), batch=8, overwrite=False, est
                 if estimator is not None:
                     Hs, ok = estimator(x1, x2, ids)
                 else:
-                    Hd, vd, _ = estimate_homography(x1.cuda(), x2.cuda(), seed=seed, pair_ids=ids)
+                    Hd, vd, _ = estimate_homography(x1.cuda(), x2.cuda(), seed=seed, pair_ids=ids, upright=upright, extended=extended)
                     Hs, ok = Hd.cpu().numpy(), vd.cpu().tolist()
                 hdir.mkdir(exist_ok=True)
                 for (_, stem, _, _), Hm, v in zip(chunk, Hs, ok):
@@ -228,11 +252,14 @@ def main(argv=None):
     p.add_argument("--batch", type=int, default=8)
     p.add_argument("--overwrite", action="store_true")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--oriented", action="store_true",
+                   help="oriented SURF (rotation-invariant; the reference's SURF_create() default) instead of upright U-SURF")
+    p.add_argument("--extended", action="store_true", help="128-d descriptors instead of 64-d")
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
         print("stereo_h: needs a ROCm device (the estimator has no CPU path)", file=sys.stderr)
         return 2
-    write_sidecars(a.root, a.split, a.batch, a.overwrite, seed=a.seed)
+    write_sidecars(a.root, a.split, a.batch, a.overwrite, seed=a.seed, upright=not a.oriented, extended=a.extended)
     return 0
 
 

@@ -197,6 +197,32 @@ def stereo_pair(seed: int, height: int, width: int):
     return x1.astype(np.float32), x2.astype(np.float32), H.astype(np.float32)
 
 
+def rotated_stereo_pair(seed: int, theta: float, height: int, width: int):
+    """(x1, x2, H) with an in-plane rotation: view 2 is view 1 rotated by ``theta`` degrees (x right, y down) about a point within
+    8 px of the centre, then mapped by ``homography(seed)`` (small translation, mild perspective).  Both views are crops of one
+    field larger than the crop, so view 2 is textured to its corners: U[0,1) noise linearly interpolated from knots every 2, 6 and
+    20 px, summed and stretched to [0, 1].  (``stereo_pair``'s 3x3-boxed pixel noise is too fine for SURF under rotation: rounded
+    sample positions decorrelate it.)  View 2 gets N(0, 0.01) noise as in ``stereo_pair``.  H (view-1 pixel -> view-2 pixel) is
+    exact."""
+    r = np.random.Generator(np.random.PCG64(5_000_011 + seed))
+    pad = int(np.ceil(0.5 * (np.hypot(height, width) - min(height, width)))) + 40
+    fh, fw = height + 2 * pad, width + 2 * pad
+    field = np.zeros((3, fh, fw))
+    for step, amp in ((2, 0.5), (6, 0.7), (20, 0.6)):
+        gh, gw = fh // step + 2, fw // step + 2
+        field += amp * _upsample_linear(r.uniform(0.0, 1.0, size=(3, gh, gw)), gh * step, gw * step)[:, :fh, :fw]
+    field = (field - field.min()) / (field.max() - field.min())
+    cx, cy = (width - 1) / 2 + r.uniform(-8, 8), (height - 1) / 2 + r.uniform(-8, 8)
+    c, s = np.cos(np.deg2rad(theta)), np.sin(np.deg2rad(theta))
+    rot = np.array([[c, -s, cx - c * cx + s * cy], [s, c, cy - s * cx - c * cy], [0, 0, 1.0]])
+    H = homography(seed) @ rot
+    shift = np.array([[1, 0, pad], [0, 1, pad], [0, 0, 1.0]])
+    x1 = field[:, pad:pad + height, pad:pad + width]
+    x2 = _warp_np(field, shift @ H @ np.linalg.inv(shift))[:, pad:pad + height, pad:pad + width]
+    x2 = np.clip(x2 + r.normal(0.0, 0.01, size=x1.shape), 0.0, 1.0)
+    return x1.astype(np.float32), x2.astype(np.float32), (H / H[2, 2]).astype(np.float32)
+
+
 def _upsample_linear(grid: np.ndarray, height: int, width: int) -> np.ndarray:
     """(C, h, w) coarse grid -> (C, height, width), separable linear interpolation with the grid's corners on the image corners."""
     C, h, w = grid.shape

@@ -13,6 +13,8 @@
  *   det    (2B, hesic_stereo_h_det_elems(H, W)) fp32   Hessian responses of the 20 layers (4 octaves x 5), each (H/step) x (W/step)
  *   kp     (2B, max_kp, 4) fp32        keypoints [x, y, size, response], the first n_kp[n] valid, in generation order
  *   desc   (2B, max_kp, 64) fp32       U-SURF descriptors; nrm (2B, max_kp) their squared norms
+ *          (2B, max_kp, dim) fp32      with the _ex entry points: dim = 64 or 128 (extended), upright or oriented
+ *   ori    (2B, max_kp, 2) fp32        keypoint directions [cos, sin] (x right, y down); (1, 0) is upright
  * Per-pair arrays:
  *   matches (B, max_kp, 2) int32       [query in view 1, train in view 2], the first n_match[b] valid, in query order
  *   H_out (B, 9) fp32 (left -> right pixels, h33 = 1; zeros when invalid), valid / inliers / best (B) int32,
@@ -48,6 +50,17 @@ int hesic_stereo_h_describe(const int32_t* I, const float* kp, const int32_t* n_
 /* 2-NN of every view-1 descriptor over view 2 (squared L2 on the matrix cores), ratio test d1^2 < 0.49 d2^2, compacted in query order */
 int hesic_stereo_h_match(const float* desc, const float* nrm, const int32_t* n_kp, int B, int H, int W, int max_kp, int n_hyp, void* ws,
                          size_t ws_bytes, int32_t* matches, int32_t* n_match, void* stream);
+/* dominant direction of the first n_kp[n] keypoints of each of N images (OpenCV SURF's orientation: 109 Haar samples of size
+   4 s in a radius of 6 s, the longest summed response over 60-degree windows in steps of 5 degrees); (1, 0) where no window has a
+   non-zero sum.  max_kp <= HESIC_STEREO_H_MAX_KEYPOINTS */
+int hesic_stereo_h_orient(const int32_t* I, const float* kp, const int32_t* n_kp, int N, int H, int W, int max_kp, float* ori, void* stream);
+/* SURF descriptors of dim = 64 or 128 (extended: each sum split by the sign of the other response) components, in the frame of ori
+   (NULL: upright; ori = (1, 0) everywhere with dim = 64 gives hesic_stereo_h_describe's bits) */
+int hesic_stereo_h_describe_ex(const int32_t* I, const float* kp, const float* ori, const int32_t* n_kp, int N, int H, int W, int max_kp,
+                               int dim, float* desc, float* nrm, void* stream);
+/* hesic_stereo_h_match on descriptors of dim = 64 or 128 components (dim = 64 gives hesic_stereo_h_match's result) */
+int hesic_stereo_h_match_ex(const float* desc, const float* nrm, const int32_t* n_kp, int B, int H, int W, int max_kp, int n_hyp, int dim,
+                            void* ws, size_t ws_bytes, int32_t* matches, int32_t* n_match, void* stream);
 /* RANSAC (n_hyp hypotheses from a counter hash of (seed, pair_ids[b], hypothesis, draw), reprojection error <= 5 px), best
    hypothesis, inlier mask, least-squares DLT + 10 Levenberg-Marquardt steps over its inliers */
 int hesic_stereo_h_ransac(const float* kp, const int32_t* matches, const int32_t* n_match, int B, int H, int W, int max_kp, int n_hyp,
