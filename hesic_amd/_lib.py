@@ -20,6 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libhesic_hip.so")
 LIB_PATH_F16 = os.path.join(_HERE, "libhesic_hip_f16.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_hip.h")
 STEREO_H_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_stereo_h.h")
+CODEC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_codec.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -240,6 +241,17 @@ _STEREO_H_SIGS = {
                               _i32),
 }
 
+# include/hesic_codec.h: the device-resident range coder of the HESIC latents (HSIC.compress_batch / decompress_batch), in both libraries
+CODEC_MAX_ALPHABET = 1024       # HESIC_CODEC_MAX_ALPHABET
+CODEC_OVERFLOW, CODEC_BAD_SYMBOL = 1, 2
+_CODEC_SIGS = {
+    "hesic_rc_stream_cap": ([_i64], _i64),
+    "hesic_gmm_rc_ranges": ([_P(GmmDesc), _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp], _i32),
+    "hesic_rc_encode_streams": ([_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp], _i32),
+    "hesic_rc_compact_streams": ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
+    "hesic_gmm_rc_decode": ([_P(GmmDesc), _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _vp], _i32),
+}
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -255,6 +267,13 @@ def declared_symbols():
 def declared_stereo_h_symbols():
     """Every ``hesic_*`` function declared in include/hesic_stereo_h.h (used by the stereo-homography ABI test)."""
     with open(STEREO_H_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
+def declared_codec_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_codec.h (used by the device-codec ABI test)."""
+    with open(CODEC_HEADER_PATH) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
@@ -278,7 +297,7 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} exports no hesic_abi_version -- not this package's library; {rebuild}") from None
         if ver != ABI_VERSION:
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
-        for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()):
+        for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -1,0 +1,166 @@
+"""``python -m hesic_amd.codec``: code a stereo folder to ``.hsd`` blobs and back, on the GPU.
+
+    encode ROOT OUT [--split test] [--batch 8] [--checkpoint PATH]    ROOT/<split>/{left,right}/ + ROOT/<split>/H/<stem>.npy
+                                                                      (the sidecars ``python -m hesic_amd.stereo_h`` writes)
+                                                                      -> OUT/<stem>.hsd + OUT/<stem>.json, one JSON line of totals
+    decode OUT RECON [--batch 8] [--checkpoint PATH]                  -> RECON/<stem>_left.png, RECON/<stem>_right.png
+
+``.hsd`` is the container of ``hesic_amd.bitstream`` (``HSIC.compress_batch``).  The homography is side information of the codec, as
+in the reference's flow: it travels in ``<stem>.json`` next to the blob, with the original image size (images are zero-padded to
+multiples of 64 for coding and cropped back).  Pairs without a sidecar are skipped and counted.  Without ``--checkpoint`` the
+deterministic synthetic weights are used (both sides must use the same weights and the same ``--dtype``).
+"""
+from __future__ import annotations
+
+import argparse
+import glob
+import json
+import os
+import struct
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+_DTYPES = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}
+
+
+def load_model(checkpoint=None, dtype=torch.float16, device="cuda"):
+    import hesic_amd
+    from . import models, synthetic
+    hesic_amd.set_compute_dtype(dtype)
+    net = models.HSIC()
+    if checkpoint:
+        state = torch.load(checkpoint, map_location="cpu")
+        net.load_state_dict(state.get("state_dict", state) if isinstance(state, dict) else state)
+    else:
+        synthetic.fill_state_dict_(net.state_dict())
+    net = net.to(device).eval()
+    net.update(force=True)
+    return net
+
+
+def _pairs(root, split):
+    """[(stem, left path, right path, H path or None)] of ROOT/<split>, in sorted order."""
+    d = Path(root) / split
+    lefts, rights = sorted(glob.glob(str(d / "left" / "*"))), sorted(glob.glob(str(d / "right" / "*")))
+    if not lefts or len(lefts) != len(rights):
+        raise RuntimeError(f"{d}: {len(lefts)} left and {len(rights)} right images")
+    out = []
+    for lf, rf in zip(lefts, rights):
+        if os.path.basename(lf) != os.path.basename(rf):
+            raise ValueError(f"{d}: cannot pair {os.path.basename(lf)} with {os.path.basename(rf)}")
+        hp = d / "H" / (Path(lf).stem + ".npy")
+        out.append((Path(lf).stem, lf, rf, hp if hp.is_file() else None))
+    return out
+
+
+def read_image(path):
+    """(3, H, W) float32 in [0, 1] of an image file (the loader's reader)."""
+    from .compressai.datasets import _read_rgb
+    return torch.from_numpy(_read_rgb(path)).permute(2, 0, 1).float() / 255.0
+
+
+def quantise(x):
+    """Reconstruction -> (B, H, W, 3) uint8, what the PNGs hold."""
+    return (x.float().clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+
+
+def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, log=print):
+    from .models import pad_to_multiple
+    from .stereo_h import _image_size
+    out = Path(out)
+    out.mkdir(parents=True, exist_ok=True)
+    groups, skipped = {}, 0
+    for stem, lf, rf, hp in _pairs(root, split):
+        if hp is None:
+            skipped += 1
+            continue
+        sa, sb = _image_size(lf), _image_size(rf)
+        if sa != sb:
+            raise ValueError(f"{os.path.basename(lf)}: the two views differ in size ({sa} vs {sb})")
+        groups.setdefault(sa, []).append((stem, lf, rf, hp))
+    n, bpp_sum, nbytes, t0 = 0, 0.0, 0, time.time()
+    for (w, h), items in groups.items():
+        for c0 in range(0, len(items), batch):
+            chunk = items[c0:c0 + batch]
+            x1 = pad_to_multiple(torch.stack([read_image(lf) for _, lf, _, _ in chunk])).cuda()
+            x2 = pad_to_multiple(torch.stack([read_image(rf) for _, _, rf, _ in chunk])).cuda()
+            Hs = [np.load(hp).astype(np.float64).reshape(3, 3) for _, _, _, hp in chunk]
+            Hm = torch.from_numpy(np.stack(Hs)).float().cuda()
+            enc = net.compress_batch(x1, x2, Hm, channels_per_stream=channels_per_stream)
+            for (stem, _, _, _), blob, Hn in zip(chunk, enc["blobs"], Hs):
+                (out / (stem + ".hsd")).write_bytes(blob)
+                (out / (stem + ".json")).write_text(json.dumps({"height": h, "width": w, "h_matrix": Hn.reshape(-1).tolist()}))
+                n += 1
+                nbytes += len(blob)
+                bpp_sum += len(blob) * 8 / (2 * h * w)               # against the ORIGINAL pixels of the two views
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    res = {"pairs": n, "skipped_no_sidecar": skipped, "bytes": nbytes, "mean_bpp": bpp_sum / max(n, 1), "seconds": dt, "pairs_per_s": n / dt if dt > 0 else 0.0}
+    log(json.dumps(res))
+    return res
+
+
+def decode_folder(net, src, recon, batch=8, log=print):
+    from PIL import Image
+    src, recon = Path(src), Path(recon)
+    recon.mkdir(parents=True, exist_ok=True)
+    groups = {}
+    for f in sorted(src.glob("*.hsd")):
+        blob = f.read_bytes()
+        side = f.with_suffix(".json")
+        if len(blob) < 10 or not side.is_file():
+            raise ValueError(f"{f}: not an .hsd blob with its .json side file")
+        groups.setdefault(struct.unpack("<HH", blob[6:10]), []).append((f.stem, blob, json.loads(side.read_text())))
+    n, t0 = 0, time.time()
+    for items in groups.values():
+        for c0 in range(0, len(items), batch):
+            chunk = items[c0:c0 + batch]
+            Hm = torch.tensor([s["h_matrix"] for _, _, s in chunk], dtype=torch.float64).reshape(-1, 3, 3).float().cuda()
+            dec = net.decompress_batch([b for _, b, _ in chunk], Hm)
+            q1, q2 = quantise(dec["x1_hat"]), quantise(dec["x2_hat"])
+            for i, (stem, _, s) in enumerate(chunk):
+                h, w = int(s["height"]), int(s["width"])
+                Image.fromarray(q1[i, :h, :w]).save(recon / (stem + "_left.png"))
+                Image.fromarray(q2[i, :h, :w]).save(recon / (stem + "_right.png"))
+                n += 1
+    dt = time.time() - t0
+    res = {"pairs": n, "seconds": dt, "pairs_per_s": n / dt if dt > 0 else 0.0}
+    log(json.dumps(res))
+    return res
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(prog="python -m hesic_amd.codec", description="HESIC stereo folder <-> .hsd blobs, range-coded on the GPU.")
+    sub = p.add_subparsers(dest="cmd", required=True)
+    e = sub.add_parser("encode", help="ROOT/<split>/{left,right,H}/ -> OUT/<stem>.hsd")
+    e.add_argument("root")
+    e.add_argument("out")
+    e.add_argument("--split", default="test")
+    e.add_argument("--channels-per-stream", type=int, default=8)
+    d = sub.add_parser("decode", help="OUT/<stem>.hsd -> RECON/<stem>_{left,right}.png")
+    d.add_argument("out")
+    d.add_argument("recon")
+    for s in (e, d):
+        s.add_argument("--batch", type=int, default=8)
+        s.add_argument("--checkpoint", default=None)
+        s.add_argument("--dtype", choices=sorted(_DTYPES), default="f16")
+    a = p.parse_args(argv)
+    if not torch.cuda.is_available():
+        print("codec: needs a ROCm device (the range coder has no CPU path)", file=sys.stderr)
+        return 2
+    if a.batch < 1:
+        p.error("--batch must be positive")
+    net = load_model(a.checkpoint, _DTYPES[a.dtype])
+    if a.cmd == "encode":
+        encode_folder(net, a.root, a.out, a.split, a.batch, a.channels_per_stream)
+    else:
+        decode_folder(net, a.out, a.recon, a.batch)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

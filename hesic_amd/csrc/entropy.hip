@@ -6,6 +6,7 @@
 // y_hat / likelihood / symbols are written once.  All arithmetic is fp32; erfc/exp/tanh use the full
 // precision device functions (no fast-math) because the likelihood floors at 1e-9.
 #include "common.h"
+#include "gmm_cdf.h"      // phi_cdf, np_pairwise_sum, cdf_pm: the table-row arithmetic shared with codec.hip
 
 namespace {
 
@@ -272,7 +273,6 @@ __global__ __launch_bounds__(EB_CL * EB_PL) void eb_bwd_kernel(const T* __restri
 }
 
 // ------------------------------------------------------------------- Gaussian / Gaussian mixture
-__device__ __forceinline__ float phi_cdf(float x) { return 0.5f * erfcf(-0.70710678118654752440f * x); }
 __device__ __forceinline__ float phi_pdf(float x) { return 0.39894228040143267794f * expf(-0.5f * x * x); }
 
 // Branch-free erfc for the bf16 path: erfc(a) = exp(-a^2) * P((a-2)/(a+2)) / (1 + 2a) for a >= 0 (P: degree-10 least-squares
@@ -301,8 +301,6 @@ __device__ __forceinline__ float erfc_fast(float z) {
     return z >= 0.f ? ec : 2.f - ec;
 }
 __device__ __forceinline__ float phi_cdf_fast(float x) { return 0.5f * erfc_fast(-0.70710678118654752440f * x); }
-
-constexpr int GMM_MAXK = 8;
 
 template <typename T>
 __global__ void gmm_fwd_kernel(const hesic_gmm_desc d, const T* __restrict__ y, const T* __restrict__ scales,
@@ -347,38 +345,8 @@ __global__ void gmm_fwd_kernel(const hesic_gmm_desc d, const T* __restrict__ y, 
 //   cdf     = [0, cumsum(q)]                                                (exact integers in fp32, as np.add.accumulate)
 // The reference does this with a Python loop per channel and pixel and a host round trip per channel; here it is one
 // launch.  One thread per (channel, pixel); the row is first filled with the clipped pmf (as float bits), then rewritten.
-__device__ float np_pairwise_sum(const float* a, int n) {
-    if (n < 8) {
-        float r = 0.f;
-        for (int i = 0; i < n; ++i) r += a[i];
-        return r;
-    }
-    if (n <= 128) {
-        float r[8];
-        for (int j = 0; j < 8; ++j) r[j] = a[j];
-        int i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-        float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += a[i];
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
-}
-
-// clipped pmf of symbol s under the row's mixture: ONE definition for both table kernels (their tables must agree bit for bit: an
-// encoder may take one and a decoder the other only if both evaluate the same expression)
-template <int DUMMY = 0>
-__device__ __forceinline__ float cdf_pm(int s, const float* mu, const float* sg, const float* wk, int K) {
-    float pm = 0.f;
-    for (int k = 0; k < K; ++k) {
-        const float a = fabsf((float)s - mu[k]);
-        pm += (phi_cdf((0.5f - a) / sg[k]) - phi_cdf((-0.5f - a) / sg[k])) * wk[k];
-    }
-    return fminf(fmaxf(pm, 1.0f / 65536.0f), 1.0f);
-}
+// np_pairwise_sum and cdf_pm (the clipped pmf of one symbol) live in gmm_cdf.h: ONE definition for the table kernels here and the device
+// range coder of codec.hip, whose rows must agree with these tables bit for bit.
 
 template <typename T>
 __global__ void gmm_cdf_kernel(const hesic_gmm_desc d, int b, const T* __restrict__ scales, const T* __restrict__ means,
@@ -413,7 +381,6 @@ __global__ void gmm_cdf_kernel(const hesic_gmm_desc d, int b, const T* __restric
 // whole cost -- spread over the lanes, the clipped pmf staged in LDS, its sum taken by numpy's pairwise order on that array (every lane
 // redundantly: LDS broadcasts), the cumulative counts by a wave scan (integer-valued floats below 2^24: any order is exact).  One thread
 // per row took 15 us for the 2112 rows of a HESIC+ wavefront group (a latency-bound loop of ~40 symbols x 2 erfc); this form ~4 us.
-constexpr int CDF_WAVE_MAX = 1024;
 template <typename T>
 __global__ __launch_bounds__(256) void gmm_cdf_wave_kernel(const hesic_gmm_desc d, int b, const T* __restrict__ scales, const T* __restrict__ means,
                                                            const float* __restrict__ weights, const int32_t* __restrict__ channels, int n_ch, int minmax,

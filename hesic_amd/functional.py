@@ -1957,6 +1957,121 @@ def gmm_cdf_tables(scales, means, weights, channels, minmax, K, b=0, scale_bound
     return out
 
 
+# ------------------------------------------------------------------------------------ device-resident range coder
+# include/hesic_codec.h (csrc/codec.hip): the bit-stream of HSIC.compress_batch / decompress_batch.  Of one VIEW of a batch, image b has
+# its own alphabet (``minmax[b]``) and its own list of coded channels (``channels[b]``, ascending); stream (b, s) carries
+# ``channels_per_stream`` consecutive coded channels.  Tables and symbols stay on the device.
+def rc_check(minmax, channels, M):
+    """Host-side refusal of what the coder's kernels cannot take (nothing is launched): alphabets beyond their LDS row, malformed channel
+    lists.  Returns the normalised (minmax, channels) lists."""
+    if len(minmax) != len(channels) or len(minmax) == 0:
+        raise ValueError("device range coder: one minmax and one channel list per image")
+    mms, chs = [], []
+    for mm, ch in zip(minmax, channels):
+        mm, ch = int(mm), [int(c) for c in ch]
+        if mm < 1 or 2 * mm + 1 > L.CODEC_MAX_ALPHABET:
+            raise ValueError(f"device range coder: an alphabet of 2 * {mm} + 1 symbols is outside its limit of {L.CODEC_MAX_ALPHABET} (one table "
+                             "row per wave in LDS); code this pair with the per-pair HSIC.compress / decompress, which has no such limit")
+        if len(ch) > M or any(c < 0 or c >= M for c in ch) or any(a >= b for a, b in zip(ch, ch[1:])):
+            raise ValueError(f"device range coder: the coded channels must be ascending indices in [0, {M})")
+        mms.append(mm)
+        chs.append(ch)
+    return mms, chs
+
+
+def rc_meta(minmax, channels, M, device):
+    """The per-image header of one view as the kernels read it: int32 (B, M + 2) rows [n_coded, minmax, channel_0, ...], checked by
+    ``rc_check`` first."""
+    mms, chs = rc_check(minmax, channels, M)
+    return torch.tensor([[len(ch), mm] + ch + [0] * (M - len(ch)) for mm, ch in zip(mms, chs)], dtype=torch.int32, device=device)
+
+
+def _rc_args(scales, means, weights, K, scale_bound):
+    L.require_cuda(scales, means)
+    B, KM, H, W = scales.shape
+    M = KM // K
+    ps, sptr, mptr, keep = _sm_pointers(scales.detach(), means.detach(), scales, B, K, M)
+    wts = None if weights is None else weights.detach().reshape(B, K * M).to(torch.float32).contiguous()
+    d = L.GmmDesc(B, H * W, M, K, L.dt(scales), 0, ps, 0, 0, float(scale_bound), 0.0)
+    return d, sptr, mptr, wts, keep, (B, M, H, W)
+
+
+def _rc_streams(M, channels_per_stream):
+    cps = int(channels_per_stream)
+    if cps < 1 or cps > M:
+        raise ValueError(f"channels_per_stream must be in [1, {M}], got {channels_per_stream}")
+    return cps, (M + cps - 1) // cps
+
+
+def gmm_rc_ranges(scales, means, weights, y_hat, minmax, channels, K, scale_bound=0.11, meta=None):
+    """The coding interval of every coded latent: int32 (B, M, H, W, 3) with [j] = (c[s], c[s+1] - c[s], c[A]) of the symbol
+    s = y_hat + minmax[b] of image b's j-th coded channel in the row ``gmm_cdf_tables`` forms for that element (bit for bit); rows
+    j >= len(channels[b]) are not written."""
+    d, sptr, mptr, wts, keep, (B, M, H, W) = _rc_args(scales, means, weights, K, scale_bound)
+    L.require_cuda(y_hat)
+    if y_hat.shape != (B, M, H, W):
+        raise ValueError(f"gmm_rc_ranges: y_hat must be {(B, M, H, W)}, got {tuple(y_hat.shape)}")
+    if meta is None:
+        meta = rc_meta(minmax, channels, M, scales.device)
+    y_hat = _nhwc(y_hat.detach())
+    out = torch.empty((B, M, H, W, 3), dtype=torch.int32, device=scales.device)
+    L.call("hesic_gmm_rc_ranges", C.byref(d), sptr, mptr, L.ptr(wts), L.ptr(y_hat), L.dt(y_hat), L.ptr(meta), L.ptr(out), L.stream())
+    del keep
+    return out
+
+
+def gmm_rc_encode(scales, means, weights, y_hat, minmax, channels, K, channels_per_stream=1, scale_bound=0.11):
+    """One view of a batch -> (bytes, counts): ``counts`` int32 (B, S), S = ceil(M / channels_per_stream), the byte length of every stream
+    (0 beyond an image's coded channels), ``bytes`` uint8 the streams back to back in (b, s) order -- both on the device; what crosses
+    to the host is the payload and the counts.  Raises if a stream overflowed its slot or a symbol had no frequency."""
+    B, KM, H, W = scales.shape
+    M = KM // K
+    cps, S = _rc_streams(M, channels_per_stream)
+    meta = rc_meta(minmax, channels, M, scales.device)
+    triples = gmm_rc_ranges(scales, means, weights, y_hat, minmax, channels, K, scale_bound, meta=meta)
+    dev = scales.device
+    cap = 4 * cps * H * W + 16
+    slots = torch.empty((B * S, cap), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, S), dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.call("hesic_rc_encode_streams", L.ptr(triples), L.ptr(meta), B, M, H * W, cps, L.ptr(slots), cap, L.ptr(counts), L.ptr(status), L.stream())
+    offsets = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
+    st, total = (int(v) for v in torch.stack([status[0].to(torch.int64), offsets[-1]]).cpu())
+    if st:
+        what = ["a stream overflowed its slot of 4 bytes per symbol + 16"] if st & L.CODEC_OVERFLOW else []
+        what += ["a latent lies outside its image's alphabet (zero frequency)"] if st & L.CODEC_BAD_SYMBOL else []
+        raise RuntimeError("gmm_rc_encode: " + " and ".join(what))
+    offsets = offsets - counts.reshape(-1)
+    out = torch.empty((total,), dtype=torch.uint8, device=dev)
+    if total:
+        L.call("hesic_rc_compact_streams", L.ptr(slots), cap, L.ptr(counts), L.ptr(offsets), B * S, L.ptr(out), total, L.stream())
+    return out, counts
+
+
+def gmm_rc_decode(scales, means, weights, minmax, channels, K, data, counts, out_dtype=None, channels_per_stream=1, scale_bound=0.11):
+    """Inverse of ``gmm_rc_encode`` for one view: ``data`` uint8 (device) the streams back to back, ``counts`` (B, S) their lengths ->
+    y_hat (B, M, H, W) channels-last in ``out_dtype`` (default: the compute dtype), unflagged channels zero.  Streams written by the host
+    range coder over ``gmm_cdf_tables`` rows (8-byte termination) decode too."""
+    d, sptr, mptr, wts, keep, (B, M, H, W) = _rc_args(scales, means, weights, K, scale_bound)
+    cps, S = _rc_streams(M, channels_per_stream)
+    dev = scales.device
+    meta = rc_meta(minmax, channels, M, dev)
+    L.require_cuda(data)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise ValueError("gmm_rc_decode: data must be a contiguous 1-d uint8 tensor")
+    counts = torch.as_tensor(counts, dtype=torch.int32, device=dev).contiguous()
+    if counts.numel() != B * S:
+        raise ValueError(f"gmm_rc_decode: {B * S} stream lengths expected, got {counts.numel()}")
+    offsets = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64) - counts.reshape(-1)
+    out_dtype = out_dtype or _compute_dtype
+    y_hat = _empty_nhwc(B, M, H, W, out_dtype, dev)
+    y_hat.zero_()                                   # the unflagged channels: one memset
+    L.call("hesic_gmm_rc_decode", C.byref(d), sptr, mptr, L.ptr(wts), L.ptr(meta), cps, L.ptr(data), data.numel(), L.ptr(offsets), L.ptr(counts),
+           L.ptr(y_hat), L.dt(out_dtype), L.stream())
+    del keep
+    return y_hat
+
+
 def quantize_symbols(y, means=None):
     """EntropyModel._quantize(x, 'symbols', means) (entropy_models.py:98-125): int32 indices."""
     L.require_cuda(y)

@@ -625,6 +625,18 @@ def _round_latent(model, y_hi):
     return model._quantize(y_hi, "dequantize")
 
 
+def _decompress_z(bottleneck, strings, size):
+    """``EntropyBottleneck.decompress`` for a batch.  The reference's form holds its (1, C, 1, 1) medians against an (N, C, H, W) index
+    map and refuses N > 1; here the medians are expanded over the batch and the strings go through ``EntropyModel.decompress`` in one
+    call (each string is its own rANS stream, the values are those of N single calls)."""
+    if len(strings) == 1:
+        return bottleneck.decompress(strings, size)
+    from .compressai.entropy_models.entropy_models import EntropyModel
+    shape = (len(strings), bottleneck._quantized_cdf.size(0), int(size[0]), int(size[1]))
+    medians = bottleneck._medians().detach().view(1, -1, 1, 1).expand(shape[0], -1, -1, -1)
+    return EntropyModel.decompress(bottleneck, list(strings), bottleneck._build_indexes(shape), medians)
+
+
 # --------------------------------------------------------------------------------------------- HESIC
 class HSIC(StereoCompressionModel):
     """HESIC (reference ``HSIC``, ywz/mywork/newnet1.py:696-783)."""
@@ -699,7 +711,7 @@ class HSIC(StereoCompressionModel):
         y1_lo, y1 = self.encoder1.latent(x1, exact=True, lo_abs=self._LO_ABS)
         z1 = self._h_a1.latent(y1_lo)
         z1_strings = self.entropy_bottleneck1.compress(z1)
-        z1_hat = self.entropy_bottleneck1.decompress(z1_strings, z1.size()[-2:]).to(cdt)
+        z1_hat = _decompress_z(self.entropy_bottleneck1, z1_strings, z1.size()[-2:]).to(cdt)
         gmm1 = self._h_s1(z1_hat, hi=True)
         y1_hat = _round_latent(self.gaussian1, y1)
         x1_hat = self.decoder1(y1_hat)
@@ -707,7 +719,7 @@ class HSIC(StereoCompressionModel):
         y2_lo, y2 = self.encoder2.latent(x1_warp, x2, exact=True, lo_abs=self._LO_ABS)
         z2 = self._h_a2.latent(y2_lo)
         z2_strings = self.entropy_bottleneck2.compress(z2)
-        z2_hat = self.entropy_bottleneck2.decompress(z2_strings, z2.size()[-2:]).to(cdt)
+        z2_hat = _decompress_z(self.entropy_bottleneck2, z2_strings, z2.size()[-2:]).to(cdt)
         x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
         y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
         gmm2 = self._h_s2(z2_hat, y1_hat_w, hi=True)
@@ -803,6 +815,105 @@ class HSIC(StereoCompressionModel):
             x2_hat = self.decoder2(y2_hat, x1_hat_warp)
         return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat,
                 "dectime": time.time() - start}
+
+    # ------------------------------------------------------------------------------- batched bit-stream, coded on the device
+    # The same flow for a whole batch, with the range coder on the GPU (csrc/codec.hip): per view one launch for the coding intervals of
+    # every latent of every image, one for the streams (one per ``channels_per_stream`` coded channels), one to compact them -- no table
+    # and no symbol leaves the device.  One self-contained blob per pair (hesic_amd/bitstream.py); the z strings stay on the host rANS
+    # coder.  Pairs are independent: blob i does not depend on what else is in the batch.
+    def compress_batch(self, x1, x2, h_matrix, channels_per_stream=1):
+        """(B, 3, H, W) pairs -> dict(blobs: one ``bytes`` per pair (``bitstream.pack_pair``), bpp_real: one figure per pair over its
+        2 H W pixels, y1_hat, y2_hat, z1_hat, z2_hat).  ``channels_per_stream``: coded channels per range-coder stream -- 1 gives the
+        shortest serial chains (fastest), larger values fewer stream terminations and lengths (smaller blobs).  An image whose latents
+        need an alphabet beyond the device coder's 1024 symbols raises ``ValueError``: code that pair with ``compress``."""
+        from . import bitstream
+        _check_pair(x1, x2, h_matrix)
+        if not x1.is_cuda:
+            raise RuntimeError("HSIC.compress_batch: the device range coder needs tensors on a ROCm device (no CPU fallback)")
+        cps = int(channels_per_stream)
+        if not 1 <= cps <= min(self.M, 255):
+            raise ValueError(f"HSIC.compress_batch: channels_per_stream must be in [1, {min(self.M, 255)}], got {channels_per_stream}")
+        if self.entropy_bottleneck1._offset.numel() == 0:
+            self.update()
+        B, _, H, W = x1.shape
+        with torch.no_grad():
+            v1, v2 = self._analysis(x1, x2, h_matrix)
+            # one small device -> host read: per image, view and channel max |y_hat| (minmax and the flags follow from it)
+            peak = torch.stack([v[0].float().abs().amax(dim=(2, 3)) for v in (v1, v2)]).cpu()
+            views = [[None, None] for _ in range(B)]
+            for vi, ((y_hat, _z_hat, z_strings, gmm), gauss) in enumerate(((v1, self.gaussian1), (v2, self.gaussian2))):
+                flags = (peak[vi] > 0).tolist()
+                minmax = [int(max(float(peak[vi, b].max()), 1.0)) for b in range(B)]
+                channels = [[c for c, f in enumerate(flags[b]) if f] for b in range(B)]
+                data, counts = Fn.gmm_rc_encode(gmm[0], gmm[1], gmm[2], y_hat, minmax, channels, self.K, cps, gauss._bound())
+                data, counts = data.cpu().numpy().tobytes(), counts.cpu().tolist()
+                pos = 0
+                for b in range(B):
+                    streams = []
+                    for n in counts[b][:bitstream.n_streams(flags[b], cps)]:
+                        streams.append(data[pos:pos + n])
+                        pos += n
+                    views[b][vi] = {"minmax": minmax[b], "flags": tuple(int(f) for f in flags[b]), "z": z_strings[b], "streams": streams}
+        blobs = [bitstream.pack_pair({"mode": payload_mode_bytes(), "height": H, "width": W, "channels": self.M, "channels_per_stream": cps,
+                                      "views": views[b]}) for b in range(B)]
+        return {"blobs": blobs, "bpp_real": [len(bl) * 8 / (H * W * 2) for bl in blobs],
+                "y1_hat": v1[0], "y2_hat": v2[0], "z1_hat": v1[1], "z2_hat": v2[1]}
+
+    def decompress_batch(self, blobs, h_matrix):
+        """``blobs``: what ``compress_batch`` returned, in any grouping and order (all of one image size); ``h_matrix`` (B, 3, 3) the
+        matching homographies.  Everything is validated on the host before the first launch."""
+        from . import bitstream
+        blobs = list(blobs)
+        if not blobs:
+            raise ValueError("HSIC.decompress_batch: no blobs")
+        pairs = [bitstream.parse_pair(bl) for bl in blobs]
+        B, p0 = len(pairs), pairs[0]
+        H, W, cps = p0["height"], p0["width"], p0["channels_per_stream"]
+        for p in pairs:
+            if (p["height"], p["width"]) != (H, W):
+                raise ValueError(f"HSIC.decompress_batch: all blobs of one call must have the same size, got {H}x{W} and {p['height']}x{p['width']}; "
+                                 "decode each size in a call of its own")
+            if p["channels_per_stream"] != cps:
+                raise ValueError("HSIC.decompress_batch: all blobs of one call must have the same channels_per_stream")
+            if p["channels"] != self.M:
+                raise ValueError(f"HSIC.decompress_batch: the blob codes {p['channels']} latent channels, this model has {self.M}")
+        if H % 64 or W % 64:
+            raise ValueError(f"HSIC.decompress_batch: the header's size {H}x{W} is not a multiple of 64")
+        if h_matrix.dim() != 3 or h_matrix.shape[-2:] != (3, 3) or h_matrix.shape[0] not in (1, B):
+            raise ValueError(f"HSIC.decompress_batch: h_matrix must be ({B}, 3, 3) (or (1, 3, 3)), got {tuple(h_matrix.shape)}")
+        if not h_matrix.is_cuda:
+            raise RuntimeError("HSIC.decompress_batch: the device range coder needs h_matrix on a ROCm device (no CPU fallback)")
+        per_view = []
+        for vi in range(2):
+            vs = [p["views"][vi] for p in pairs]
+            minmax = [v["minmax"] for v in vs]
+            channels = [[c for c, f in enumerate(v["flags"]) if f] for v in vs]
+            Fn.rc_check(minmax, channels, self.M)                   # alphabets beyond the kernels' limit: refused here
+            S = (self.M + cps - 1) // cps
+            counts = [[len(s) for s in v["streams"]] + [0] * (S - len(v["streams"])) for v in vs]
+            per_view.append((minmax, channels, [v["z"] for v in vs], b"".join(s for v in vs for s in v["streams"]), counts))
+        if self.entropy_bottleneck1._offset.numel() == 0:
+            self.update()
+        dev, cdt, size = h_matrix.device, Fn.compute_dtype(), (H, W)
+        zs = (H // 64, W // 64)
+
+        def decode_view(gmm, view, gauss):
+            minmax, channels, _z, data, counts = view
+            data = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.zeros(0, dtype=torch.uint8, device=dev)
+            return Fn.gmm_rc_decode(gmm[0], gmm[1], gmm[2], minmax, channels, self.K, data, counts, cdt, cps, gauss._bound())
+
+        with torch.no_grad():
+            z1_hat = _decompress_z(self.entropy_bottleneck1, per_view[0][2], zs).to(dev, cdt)
+            z2_hat = _decompress_z(self.entropy_bottleneck2, per_view[1][2], zs).to(dev, cdt)
+            gmm1 = self._h_s1(z1_hat, hi=True)
+            y1_hat = decode_view(gmm1, per_view[0], self.gaussian1)
+            x1_hat = self.decoder1(y1_hat)
+            x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
+            y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
+            gmm2 = self._h_s2(z2_hat, y1_hat_w, hi=True)
+            y2_hat = decode_view(gmm2, per_view[1], self.gaussian2)
+            x2_hat = self.decoder2(y2_hat, x1_hat_warp)
+        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
 
     def _forward_eval(self, x1, x2, h_matrix, two_streams=True):
         """Inference schedule.  The chain that bounds the step is encoder1 -> round -> decoder1 -> warp -> {decoder2 | encoder1 ->
@@ -945,6 +1056,14 @@ def payload_header(extra=b""):
     return PAYLOAD_MAGIC + payload_mode_bytes() + extra
 
 
+def mode_mismatch_message(mode, here):
+    """What a decoder in mode ``here`` says about a payload written in ``mode`` (the .bin payload and the .hsd container)."""
+    return (f"decompress: the payload was written with [{describe_mode_bytes(mode)}] but this process decodes with "
+            f"[{describe_mode_bytes(here)}]; the cumulative-frequency tables would differ in the last count and the range decoder "
+            "would desynchronise.  Select the writer's mode (hesic_amd.set_compute_dtype, set_analysis_precision, "
+            "geometry.use_reference_era_warp / HESIC_WARP_ALIGN_CORNERS, HESIC_SHAPED_WEIGHTS, HESIC_BF16_LATENTS, HESIC_NO_GROUP_HYPER)")
+
+
 def check_payload(payload, n_extra=0):
     """Validate the container header; returns (extra bytes, offset of the range-coder stream)."""
     n = len(PAYLOAD_MAGIC)
@@ -953,10 +1072,7 @@ def check_payload(payload, n_extra=0):
                          "this package, or not one of its payloads): re-encode it -- the header names the mode the tables were formed in")
     mode, here = bytes(payload[n:n + _MODE_BYTES]), payload_mode_bytes()
     if mode != here:
-        raise ValueError(f"decompress: the payload was written with [{describe_mode_bytes(mode)}] but this process decodes with "
-                         f"[{describe_mode_bytes(here)}]; the cumulative-frequency tables would differ in the last count and the range decoder "
-                         "would desynchronise.  Select the writer's mode (hesic_amd.set_compute_dtype, set_analysis_precision, "
-                         "geometry.use_reference_era_warp / HESIC_WARP_ALIGN_CORNERS, HESIC_SHAPED_WEIGHTS, HESIC_BF16_LATENTS, HESIC_NO_GROUP_HYPER)")
+        raise ValueError(mode_mismatch_message(mode, here))
     return payload[n + _MODE_BYTES:n + _MODE_BYTES + n_extra], n + _MODE_BYTES + n_extra
 
 
