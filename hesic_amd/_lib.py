@@ -250,6 +250,11 @@ _CODEC_SIGS = {
     "hesic_rc_encode_streams": ([_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp], _i32),
     "hesic_rc_compact_streams": ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
     "hesic_gmm_rc_decode": ([_P(GmmDesc), _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _vp], _i32),
+    # HESIC+ (HSICJoint.compress_batch / decompress_batch): wavefront-ordered streams
+    "hesic_rc_encode_streams_ordered": ([_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp], _i32),
+    "hesic_joint_gather_batch": ([_vp, _i32, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp], _i32),
+    "hesic_gmm_rc_decode_step": ([_P(GmmDesc), _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp],
+                                 _i32),
 }
 
 _libs = {}                      # torch 16-bit dtype -> CDLL

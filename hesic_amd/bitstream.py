@@ -1,11 +1,12 @@
-"""The ``.hsd`` container of ``HSIC.compress_batch`` / ``decompress_batch``: one self-contained blob per stereo pair.
+"""The ``.hsd`` container of ``HSIC.compress_batch`` / ``decompress_batch`` (HESIC) and of ``HSICJoint.compress_batch`` /
+``decompress_batch`` (HESIC+): one self-contained blob per stereo pair.
 
 Pure Python (no GPU, no kernels): ``pack_pair`` and ``parse_pair`` are inverses, and ``parse_pair`` validates everything a decoder
 relies on -- magic, the mode bytes the cumulative-frequency tables depend on, every length, the CRC -- before anything is launched.
 
 Layout (little endian; ``varint`` = unsigned LEB128)::
 
-    b"HSD\\x01"                     magic + format version
+    b"HSD\\x01" | b"HSJ\\x01"       magic + format version: the KIND of the blob -- "hesic" (HSD) or "joint" (HSJ, HESIC+)
     mode        2 bytes            models.payload_mode_bytes() of the writer (as in the .bin payload of HSIC.compress)
     H, W        2 x uint16         image size (multiples of 64)
     M           uint16             latent channels
@@ -21,6 +22,12 @@ Layout (little endian; ``varint`` = unsigned LEB128)::
 
 Stream s of a view carries the coded channels [s * cps, (s + 1) * cps) of that view's flagged channels (ascending), symbols
 channel-major, then rows, then columns; see DESIGN.md 7 for the coder.
+
+The two kinds share every field; they differ in the magic and in the order of the symbols inside a stream.  A "joint" blob's streams
+walk the latent map in wavefront groups (t = w + 3 h ascending, raster order inside a group), pixel-major: for each pixel the
+stream's channels in ascending order (include/hesic_codec.h).  ``pack_pair`` writes the kind named by ``pair["kind"]`` (absent:
+"hesic"); ``parse_pair`` takes either magic and returns ``"kind": "joint"`` for a HESIC+ blob -- a parsed HESIC blob is the dict it
+always was, without the key; ``kind_of`` reads both.  A decoder checks the kind before anything is launched (``require_kind``).
 """
 from __future__ import annotations
 
@@ -28,6 +35,8 @@ import struct
 import zlib
 
 MAGIC = b"HSD\x01"
+MAGIC_JOINT = b"HSJ\x01"
+KINDS = {"hesic": MAGIC, "joint": MAGIC_JOINT}
 _MAX_VARINT_BYTES = 5            # lengths below 2^35: far beyond any stream
 _ONE_BYTE = [bytes((i,)) for i in range(0x80)]
 
@@ -84,9 +93,26 @@ def n_streams(flags, channels_per_stream):
     return (n + channels_per_stream - 1) // channels_per_stream
 
 
+def kind_of(pair):
+    """"hesic" or "joint": the kind of a parsed pair (or of a dict about to be packed)."""
+    return pair.get("kind") or "hesic"
+
+
+def require_kind(pair, kind, who):
+    """The check a decoder makes before anything is launched: ``ValueError`` naming both kinds."""
+    got = kind_of(pair)
+    if got != kind:
+        names = {"hesic": "HESIC (HSIC, magic b'HSD\\x01')", "joint": "HESIC+ (HSICJoint, magic b'HSJ\\x01')"}
+        raise ValueError(f"{who}: this decoder takes {names[kind]} blobs, the blob is a {names[got]} blob; decode it with the other model "
+                         "(python -m hesic_amd.codec decode --model " + got + ")")
+
+
 def pack_pair(pair) -> bytes:
     """``pair``: dict(mode: 2 bytes | None = this process' mode, height, width, channels, channels_per_stream, views: two dicts(minmax,
-    flags: ``channels`` 0/1 values, z: bytes, streams: list of bytes, one per stream)) -> the blob."""
+    flags: ``channels`` 0/1 values, z: bytes, streams: list of bytes, one per stream)[, kind: "hesic" (default) | "joint"]) -> the blob."""
+    kind = kind_of(pair)
+    if kind not in KINDS:
+        raise ValueError(f"bitstream: unknown kind {kind!r} (\"hesic\" or \"joint\")")
     mode = bytes(pair["mode"]) if pair.get("mode") is not None else _current_mode()
     H, W, M, cps = int(pair["height"]), int(pair["width"]), int(pair["channels"]), int(pair["channels_per_stream"])
     if len(mode) != 2:
@@ -95,7 +121,7 @@ def pack_pair(pair) -> bytes:
         raise ValueError(f"bitstream: size {H}x{W}, {M} channels, {cps} channels per stream do not fit the header")
     if len(pair["views"]) != 2:
         raise ValueError("bitstream: a pair has two views")
-    head = bytearray(MAGIC + mode + struct.pack("<HHHB", H, W, M, cps))
+    head = bytearray(KINDS[kind] + mode + struct.pack("<HHHB", H, W, M, cps))
     body = bytearray()
     for v in pair["views"]:
         minmax, flags, z, streams = int(v["minmax"]), [1 if f else 0 for f in v["flags"]], bytes(v["z"]), [bytes(s) for s in v["streams"]]
@@ -119,8 +145,10 @@ def parse_pair(blob, mode=None):
     """Inverse of ``pack_pair``.  ``mode``: the two mode bytes the decoder runs in (default: this process').  Raises ``ValueError`` on a
     wrong magic, a mode mismatch (the text of ``models.check_payload``), a truncated blob, lengths that do not add up and a CRC mismatch."""
     blob = bytes(blob)
-    if len(blob) < len(MAGIC) or blob[:len(MAGIC)] != MAGIC:
-        raise ValueError("bitstream: not an .hsd blob of this package (bad magic; format 1 starts with b'HSD\\x01')")
+    if len(blob) < len(MAGIC) or blob[:len(MAGIC)] not in (MAGIC, MAGIC_JOINT):
+        raise ValueError("bitstream: not an .hsd blob of this package (bad magic; format 1 starts with b'HSD\\x01', HESIC+ blobs with "
+                         "b'HSJ\\x01')")
+    joint = blob[:len(MAGIC)] == MAGIC_JOINT
     r = _Reader(blob, len(blob) - 4 if len(blob) >= len(MAGIC) + 4 else len(blob))
     r.take(len(MAGIC), "magic")
     got = bytes(r.take(2, "mode bytes"))
@@ -153,4 +181,7 @@ def parse_pair(blob, mode=None):
     crc, = struct.unpack("<I", blob[-4:])
     if crc != zlib.crc32(blob[:-4]) & 0xFFFFFFFF:
         raise ValueError("bitstream: CRC mismatch -- the blob is damaged")
-    return {"mode": got, "height": H, "width": W, "channels": M, "channels_per_stream": cps, "views": views}
+    pair = {"mode": got, "height": H, "width": W, "channels": M, "channels_per_stream": cps, "views": views}
+    if joint:
+        pair["kind"] = "joint"
+    return pair

@@ -1,11 +1,14 @@
 """``python -m hesic_amd.codec``: code a stereo folder to ``.hsd`` blobs and back, on the GPU.
 
-    encode ROOT OUT [--split test] [--batch 8] [--checkpoint PATH]    ROOT/<split>/{left,right}/ + ROOT/<split>/H/<stem>.npy
+    encode ROOT OUT [--split test] [--batch 8] [--checkpoint PATH] [--model hesic|joint]
+                                                                      ROOT/<split>/{left,right}/ + ROOT/<split>/H/<stem>.npy
                                                                       (the sidecars ``python -m hesic_amd.stereo_h`` writes)
                                                                       -> OUT/<stem>.hsd + OUT/<stem>.json, one JSON line of totals
-    decode OUT RECON [--batch 8] [--checkpoint PATH]                  -> RECON/<stem>_left.png, RECON/<stem>_right.png
+    decode OUT RECON [--batch 8] [--checkpoint PATH] [--model hesic|joint]
+                                                                      -> RECON/<stem>_left.png, RECON/<stem>_right.png
 
-``.hsd`` is the container of ``hesic_amd.bitstream`` (``HSIC.compress_batch``).  The homography is side information of the codec, as
+``.hsd`` is the container of ``hesic_amd.bitstream`` (``HSIC.compress_batch``; with ``--model joint`` HESIC+, ``HSICJoint.compress_batch``:
+the blob names its kind, and a decoder of the other model refuses it).  The homography is side information of the codec, as
 in the reference's flow: it travels in ``<stem>.json`` next to the blob, with the original image size (images are zero-padded to
 multiples of 64 for coding and cropped back).  Pairs without a sidecar are skipped and counted.  Without ``--checkpoint`` the
 deterministic synthetic weights are used (both sides must use the same weights and the same ``--dtype``).
@@ -27,11 +30,11 @@ import torch
 _DTYPES = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}
 
 
-def load_model(checkpoint=None, dtype=torch.float16, device="cuda"):
+def load_model(checkpoint=None, dtype=torch.float16, device="cuda", model="hesic"):
     import hesic_amd
     from . import models, synthetic
     hesic_amd.set_compute_dtype(dtype)
-    net = models.HSIC()
+    net = {"hesic": models.HSIC, "joint": models.HSICJoint}[model]()
     if checkpoint:
         state = torch.load(checkpoint, map_location="cpu")
         net.load_state_dict(state.get("state_dict", state) if isinstance(state, dict) else state)
@@ -148,13 +151,14 @@ def main(argv=None):
         s.add_argument("--batch", type=int, default=8)
         s.add_argument("--checkpoint", default=None)
         s.add_argument("--dtype", choices=sorted(_DTYPES), default="f16")
+        s.add_argument("--model", choices=("hesic", "joint"), default="hesic", help="hesic: HSIC (default); joint: HESIC+ (HSICJoint)")
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
         print("codec: needs a ROCm device (the range coder has no CPU path)", file=sys.stderr)
         return 2
     if a.batch < 1:
         p.error("--batch must be positive")
-    net = load_model(a.checkpoint, _DTYPES[a.dtype])
+    net = load_model(a.checkpoint, _DTYPES[a.dtype], model=a.model)
     if a.cmd == "encode":
         encode_folder(net, a.root, a.out, a.split, a.batch, a.channels_per_stream)
     else:

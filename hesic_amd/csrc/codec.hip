@@ -9,6 +9,11 @@
 //   decode  rc_decode_kernel      one wave per stream: per symbol the row in LDS, a wave scan to cumulative counts, the search by
 //                                 ballot / popcount, the state update; the symbol goes straight into the channels-last y_hat
 // Rows of up to 64 symbols (a trained model's) spread their A * K mixture terms over the whole wave (rc_fill_row_small).
+// HESIC+ (HSICJoint.compress_batch / decompress_batch) codes the same streams in wavefront order, pixel-major:
+//   encode  rc_encode_ordered_kernel   rc_encode_kernel's loop over the triples of the whole maps, walked through a pixel permutation
+//   decode  joint_gather_batch_kernel  the 5 x 5 crops and feature rows of one wavefront group of every image of the batch
+//           rc_decode_step_kernel      rc_decode_kernel cut at group boundaries: coder state in device memory, symbols straight into the
+//                                      padded latent maps the next group's crops are cut from
 // The rows are formed by the expressions of gmm_cdf.h, the ones the table kernels of entropy.hip evaluate: a stream coded here decodes
 // with the host coder over hesic_gmm_cdf's tables and the other way round (tests/test_gpu_device_codec.py holds both to that).
 #include "common.h"
@@ -133,12 +138,11 @@ __global__ __launch_bounds__(256) void rc_ranges_kernel(const hesic_gmm_desc d, 
     }
 }
 
-// hesic_rc_encoder_encode (csrc/host/hesic_host.cpp) per lane, over triples instead of table rows
-__global__ __launch_bounds__(64) void rc_encode_kernel(const int32_t* __restrict__ triples, const int32_t* __restrict__ meta, int B, int M, int HW,
-                                                       int cps, int S, uint8_t* __restrict__ slots, int64_t cap, int32_t* __restrict__ counts,
-                                                       int32_t* __restrict__ status) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= B * S) return;
+// hesic_rc_encoder_encode (csrc/host/hesic_host.cpp) per lane, over triples instead of table rows: stream t = (b, s) of both encoder
+// kernels.  order == nullptr: the stream's triples in sequence (channel-major); else symbol i is channel i % nj of pixel order[i / nj].
+__device__ __forceinline__ void rc_encode_stream(const int32_t* __restrict__ triples, const int32_t* __restrict__ meta, int t, int M, int HW, int cps,
+                                                 int S, const int32_t* __restrict__ order, uint8_t* __restrict__ slots, int64_t cap,
+                                                 int32_t* __restrict__ counts, int32_t* __restrict__ status) {
     const int b = t / S, s = t - b * S;
     int n_ch = meta[(int64_t)b * (M + 2)];
     n_ch = n_ch < 0 ? 0 : (n_ch > M ? M : n_ch);
@@ -152,7 +156,14 @@ __global__ __launch_bounds__(64) void rc_encode_kernel(const int32_t* __restrict
     int bad = 0;
     uint64_t low = 0, range = ~0ull;
     for (int64_t i = 0; i < n && !bad; ++i) {
-        const uint32_t c = (uint32_t)tr[3 * i], f = (uint32_t)tr[3 * i + 1], tot = (uint32_t)tr[3 * i + 2];
+        int64_t e = i;
+        if (order) {
+            const int64_t p = i / nj;
+            const int px = order[p];
+            if ((unsigned)px >= (unsigned)HW) { bad = HESIC_CODEC_BAD_SYMBOL; break; }      // a damaged permutation: nothing to address
+            e = (i - p * nj) * HW + px;
+        }
+        const uint32_t c = (uint32_t)tr[3 * e], f = (uint32_t)tr[3 * e + 1], tot = (uint32_t)tr[3 * e + 2];
         if (f == 0 || tot == 0 || (uint64_t)c + f > tot) { bad = HESIC_CODEC_BAD_SYMBOL; break; }
         range /= tot;
         low += (uint64_t)c * range;
@@ -179,6 +190,23 @@ __global__ __launch_bounds__(64) void rc_encode_kernel(const int32_t* __restrict
     counts[t] = bad ? 0 : (int32_t)pos;
 }
 
+__global__ __launch_bounds__(64) void rc_encode_kernel(const int32_t* __restrict__ triples, const int32_t* __restrict__ meta, int B, int M, int HW,
+                                                       int cps, int S, uint8_t* __restrict__ slots, int64_t cap, int32_t* __restrict__ counts,
+                                                       int32_t* __restrict__ status) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * S) return;
+    rc_encode_stream(triples, meta, t, M, HW, cps, S, nullptr, slots, cap, counts, status);
+}
+
+__global__ __launch_bounds__(64) void rc_encode_ordered_kernel(const int32_t* __restrict__ triples, const int32_t* __restrict__ meta, int B, int M,
+                                                               int HW, int cps, int S, const int32_t* __restrict__ order,
+                                                               uint8_t* __restrict__ slots, int64_t cap, int32_t* __restrict__ counts,
+                                                               int32_t* __restrict__ status) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * S) return;
+    rc_encode_stream(triples, meta, t, M, HW, cps, S, order, slots, cap, counts, status);
+}
+
 __global__ __launch_bounds__(256) void rc_compact_kernel(const uint8_t* __restrict__ slots, int64_t cap, const int32_t* __restrict__ counts,
                                                          const int64_t* __restrict__ offsets, uint8_t* __restrict__ out, int64_t out_bytes) {
     const int64_t t = blockIdx.x;
@@ -189,6 +217,76 @@ __global__ __launch_bounds__(256) void rc_compact_kernel(const uint8_t* __restri
     if (off + n > out_bytes) n = out_bytes - off;
     const uint8_t* src = slots + t * cap;
     for (int64_t i = threadIdx.x; i < n; i += blockDim.x) out[off + i] = src[i];
+}
+
+// The coder state of one stream: what rc_decode_step_kernel keeps in device memory between the groups of a walk (4 x 8 bytes).
+struct rc_coder {
+    uint64_t low, range, code;
+    int64_t pos;
+};
+
+__device__ __forceinline__ void rc_coder_begin(rc_coder& c, const uint8_t* __restrict__ in, int64_t len) {
+    c.low = 0; c.range = ~0ull; c.code = 0; c.pos = 0;
+    for (int i = 0; i < 8; ++i) { c.code = (c.code << 8) | (c.pos < len ? in[c.pos] : 0); ++c.pos; }
+}
+
+// One symbol of one stream, by the whole wave: the row of the symbol's mixture (raw: lane k < K its mean k, lane K + k its scale k, as
+// loaded) in LDS, a wave scan to cumulative counts, the search by ballot / popcount, the state update with the coder's renormalisation.
+// Returns the clamped symbol index; every byte read is index-checked against len.  The body of both decoder kernels.
+__device__ __forceinline__ int rc_decode_symbol(float raw, const float* wk, int K, int A, int minmax, float scale_bound, float* frow, uint32_t* crow,
+                                                float* terms, int lane, const uint8_t* __restrict__ in, int64_t len, rc_coder& c) {
+    float tot;
+    if (A <= RC_SMALL_A) {
+        tot = rc_fill_row_small(raw, wk, K, A, minmax, scale_bound, frow, terms, lane);
+    } else {
+        float mu[GMM_MAXK], sg[GMM_MAXK];
+        for (int k = 0; k < K; ++k) {
+            mu[k] = __shfl(raw, k, 64) + (float)minmax;
+            sg[k] = fmaxf(__shfl(raw, K + k, 64), scale_bound);
+        }
+        tot = rc_fill_row(mu, sg, wk, K, A, frow, lane);
+    }
+    uint32_t carry = 0;
+    for (int s0 = 0; s0 < A; s0 += 64) {
+        const int s = s0 + lane;
+        uint32_t v = s < A ? rc_freq(frow[s], tot) : 0u;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t u = (uint32_t)__shfl_up((int)v, o, 64);
+            if (lane >= o) v += u;
+        }
+        v += carry;
+        if (s < A) crow[s] = v;                      // c[s + 1]
+        carry = (uint32_t)__shfl((int)v, 63, 64);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // hesic_rc_decoder_decode_grid's step; the guards on a zero total / zero step only act on states no valid stream reaches
+    const uint64_t total = carry ? carry : 1u;
+    uint64_t step = c.range / total;
+    if (step == 0) step = 1;
+    uint64_t v = (c.code - c.low) / step;
+    if (v >= total) v = total - 1;
+    // last index with c[idx] <= v: c[0] = 0 always counts, c[i] = crow[i - 1] for 1 <= i <= A - 1
+    int idx = 0;
+    for (int s0 = 0; s0 < A - 1; s0 += 64) {
+        const int s = s0 + lane;
+        idx += __popcll(__ballot(s < A - 1 && (uint64_t)crow[s] <= v));
+    }
+    if (idx > A - 1) idx = A - 1;
+    const uint32_t c_lo = idx ? crow[idx - 1] : 0u, c_hi = crow[idx];
+    c.low += (uint64_t)c_lo * step;
+    c.range = step * (uint64_t)(c_hi - c_lo);
+    // the coder's renormalisation; a valid state leaves it within 8 trips, the bound only ends a damaged one
+    for (int it = 0; it < 16; ++it) {
+        if (!((c.low ^ (c.low + c.range)) < RC_TOP || (c.range < RC_BOT && ((c.range = (0 - c.low) & (RC_BOT - 1)), true)))) break;
+        c.code = (c.code << 8) | (c.pos < len ? in[c.pos] : 0);
+        ++c.pos;
+        c.low <<= 8;
+        c.range <<= 8;
+    }
+    return idx;
 }
 
 template <typename T>
@@ -218,9 +316,8 @@ __global__ __launch_bounds__(256) void rc_decode_kernel(const hesic_gmm_desc d, 
     if (off < 0 || off > n_bytes || len < 0) { off = 0; len = 0; }
     if (len > n_bytes - off) len = n_bytes - off;
     const uint8_t* in = bytes + off;
-    int64_t pos = 0;
-    uint64_t low = 0, range = ~0ull, code = 0;
-    for (int i = 0; i < 8; ++i) { code = (code << 8) | (pos < len ? in[pos] : 0); ++pos; }
+    rc_coder c;
+    rc_coder_begin(c, in, len);
     // A stream is one serial chain of symbols, so what a symbol waits for is latency.  The 2 K parameters of a symbol are fetched by 2 K
     // lanes at once (lane k: mean k, lane K + k: scale k) ONE SYMBOL AHEAD, and handed round by shuffles: the loads of symbol i + 1 are
     // in flight while symbol i is evaluated (a run-time K loop of dependent loads per symbol cost more than the arithmetic).  The values
@@ -248,60 +345,107 @@ __global__ __launch_bounds__(256) void rc_decode_kernel(const hesic_gmm_desc d, 
             for (int k = 0; k < d.K; ++k) wk[k] = weights ? weights[(int64_t)b * d.K * d.M + k * d.M + m] : 1.f;
             cur_m = m;
         }
-        {
-            float tot;
-            if (A <= RC_SMALL_A) {
-                tot = rc_fill_row_small(raw, wk, d.K, A, minmax, d.scale_bound, frow, tbuf[wave], lane);
-            } else {
-                float mu[GMM_MAXK], sg[GMM_MAXK];
-                for (int k = 0; k < d.K; ++k) {
-                    mu[k] = __shfl(raw, k, 64) + (float)minmax;
-                    sg[k] = fmaxf(__shfl(raw, d.K + k, 64), d.scale_bound);
-                }
-                tot = rc_fill_row(mu, sg, wk, d.K, A, frow, lane);
-            }
-            uint32_t carry = 0;
-            for (int s0 = 0; s0 < A; s0 += 64) {
-                const int s = s0 + lane;
-                uint32_t v = s < A ? rc_freq(frow[s], tot) : 0u;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const uint32_t u = (uint32_t)__shfl_up((int)v, o, 64);
-                    if (lane >= o) v += u;
-                }
-                v += carry;
-                if (s < A) crow[s] = v;                      // c[s + 1]
-                carry = (uint32_t)__shfl((int)v, 63, 64);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // hesic_rc_decoder_decode_grid's step; the guards on a zero total / zero step only act on states no valid stream reaches
-            const uint64_t total = carry ? carry : 1u;
-            uint64_t step = range / total;
-            if (step == 0) step = 1;
-            uint64_t v = (code - low) / step;
-            if (v >= total) v = total - 1;
-            // last index with c[idx] <= v: c[0] = 0 always counts, c[i] = crow[i - 1] for 1 <= i <= A - 1
-            int idx = 0;
-            for (int s0 = 0; s0 < A - 1; s0 += 64) {
-                const int s = s0 + lane;
-                idx += __popcll(__ballot(s < A - 1 && (uint64_t)crow[s] <= v));
-            }
-            if (idx > A - 1) idx = A - 1;
-            const uint32_t c_lo = idx ? crow[idx - 1] : 0u, c_hi = crow[idx];
-            low += (uint64_t)c_lo * step;
-            range = step * (uint64_t)(c_hi - c_lo);
-            // the coder's renormalisation; a valid state leaves it within 8 trips, the bound only ends a damaged one
-            for (int it = 0; it < 16; ++it) {
-                if (!((low ^ (low + range)) < RC_TOP || (range < RC_BOT && ((range = (0 - low) & (RC_BOT - 1)), true)))) break;
-                code = (code << 8) | (pos < len ? in[pos] : 0);
-                ++pos;
-                low <<= 8;
-                range <<= 8;
-            }
-            if (lane == 0) st_any(yhat, ((int64_t)b * d.HW + hw) * d.M + m, y_dtype, (float)(idx - minmax));
+        const int idx = rc_decode_symbol(raw, wk, d.K, A, minmax, d.scale_bound, frow, crow, tbuf[wave], lane, in, len, c);
+        if (lane == 0) st_any(yhat, ((int64_t)b * d.HW + hw) * d.M + m, y_dtype, (float)(idx - minmax));
+        __builtin_amdgcn_wave_barrier();          // the row buffers are rewritten by the next symbol
+    }
+}
+
+// rc_decode_kernel cut at the group boundaries of a HESIC+ wavefront walk (K = 1, fp32 (scale | mean) rows of the entropy-parameter net,
+// row b * P + p for pixel p of this group in image b: d.HW = P).  One wave per stream (b, s): its coder state comes from / goes back to
+// state[t] (first != 0: begun here from the stream's first 8 bytes), the P * nj symbols of the group are decoded pixel-major and written
+// as symbol - minmax into row centre[p] of image b's padded latent map.  Loop counts follow from meta and P alone.
+__global__ __launch_bounds__(256) void rc_decode_step_kernel(const hesic_gmm_desc d, const float* __restrict__ scales, const float* __restrict__ means,
+                                                             const int32_t* __restrict__ meta, int cps, int S, const uint8_t* __restrict__ bytes,
+                                                             int64_t n_bytes, const int64_t* __restrict__ offsets,
+                                                             const int32_t* __restrict__ counts, uint64_t* __restrict__ state, int first,
+                                                             const int32_t* __restrict__ centre, void* __restrict__ y_rows, int y_dtype,
+                                                             int64_t rows_per_image) {
+    __shared__ float buf[4][CDF_WAVE_MAX];
+    __shared__ uint32_t cum[4][CDF_WAVE_MAX];
+    __shared__ float tbuf[4][RC_SMALL_A];            // K = 1: one term per symbol
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* frow = buf[wave];
+    uint32_t* crow = cum[wave];
+    const int t = blockIdx.x * 4 + wave;
+    if (t >= d.B * S) return;                       // wave-uniform from here on
+    const int b = t / S, s_idx = t - b * S;
+    const int32_t* mt = meta + (int64_t)b * (d.M + 2);
+    int n_ch = mt[0];
+    const int minmax = mt[1];
+    n_ch = n_ch < 0 ? 0 : (n_ch > d.M ? d.M : n_ch);
+    const int j0 = s_idx * cps;
+    if (j0 >= n_ch || minmax < 1 || 2 * minmax + 1 > CDF_WAVE_MAX) return;
+    const int nj = n_ch - j0 < cps ? n_ch - j0 : cps;
+    const int A = 2 * minmax + 1;
+    int64_t off = offsets[t], len = counts[t];
+    if (off < 0 || off > n_bytes || len < 0) { off = 0; len = 0; }
+    if (len > n_bytes - off) len = n_bytes - off;
+    const uint8_t* in = bytes + off;
+    uint64_t* sv = state + (int64_t)t * 4;
+    rc_coder c;
+    if (first) {
+        rc_coder_begin(c, in, len);
+    } else {
+        c.low = sv[0]; c.range = sv[1]; c.code = sv[2]; c.pos = (int64_t)sv[3];
+        if (c.pos < 0) c.pos = len;                  // not a position this kernel stored: read zeros
+    }
+    // parameters one symbol ahead, as in rc_decode_kernel: lane 0 the mean, lane 1 the scale
+    auto fetch = [&](int p, int jj) -> float {
+        if (p >= d.HW || lane >= 2) return 0.f;
+        const int m = mt[2 + j0 + jj];
+        if ((unsigned)m >= (unsigned)d.M) return 0.f;
+        const int64_t sm = ((int64_t)b * d.HW + p) * d.sm_pix_stride + m;
+        return lane == 0 ? means[sm + d.m_c_off] : scales[sm + d.s_c_off];
+    };
+    const float wk[1] = {1.f};
+    float nxt = fetch(0, 0);
+    for (int p = 0; p < d.HW; ++p) {
+        const int row = centre[p];
+        for (int jj = 0; jj < nj; ++jj) {
+            const float raw = nxt;
+            nxt = jj + 1 < nj ? fetch(p, jj + 1) : fetch(p + 1, 0);
+            const int m = mt[2 + j0 + jj];
+            if ((unsigned)m >= (unsigned)d.M) continue;      // a damaged channel list: nothing to address
+            const int idx = rc_decode_symbol(raw, wk, 1, A, minmax, d.scale_bound, frow, crow, tbuf[wave], lane, in, len, c);
+            if (lane == 0 && row >= 0 && row < rows_per_image)
+                st_any(y_rows, ((int64_t)b * rows_per_image + row) * d.M + m, y_dtype, (float)(idx - minmax));
             __builtin_amdgcn_wave_barrier();          // the row buffers are rewritten by the next symbol
+        }
+    }
+    if (lane == 0) { sv[0] = c.low; sv[1] = c.range; sv[2] = c.code; sv[3] = (uint64_t)c.pos; }
+}
+
+// The batch form of glue.hip's joint_step_kernel without its phase 1: for the P pixels of one wavefront group (centre / rows: their padded
+// and raster rows) and the B images, in 16-byte chunks spread over the grid: the 5 x 5 crops of the padded maps -> crops[b * P + p][25][M],
+// the hyper-decoder rows par[b][row] -> feat[b * P + p][0, c_par), view 2's extra rows ext[b][row] -> feat[..][e_off, +M).  A row outside
+// its map reads as zeros.
+struct JointGather {
+    const unsigned char* y_rows; int es, M, Wp; int64_t rows_per_image;
+    const int32_t* centre; const int32_t* rows; int B, P, HW;
+    unsigned char* crops; const unsigned char* par; int c_par; const unsigned char* ext; int e_off; unsigned char* feat; int c_feat;
+};
+__global__ __launch_bounds__(256) void joint_gather_batch_kernel(const JointGather a) {
+    const int rch = a.M * a.es / 16, pch = a.c_par * a.es / 16, fch = a.c_feat * a.es / 16, ech = a.ext ? rch : 0;
+    const int per_row = 25 * rch + pch + ech;                          // chunks per (image, pixel)
+    const int64_t total = (int64_t)a.B * a.P * per_row;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int r = (int)(i / per_row), c = (int)(i - (int64_t)r * per_row);
+        const int b = r / a.P, p = r - b * a.P;
+        u32x4 v = u32x4{0u, 0u, 0u, 0u};
+        if (c < 25 * rch) {
+            const int t = c / rch, cc = c - t * rch;
+            const int64_t src = (int64_t)a.centre[p] + (t / 5 - 2) * a.Wp + (t % 5 - 2);
+            if (src >= 0 && src < a.rows_per_image) v = ((const u32x4*)(a.y_rows + ((int64_t)b * a.rows_per_image + src) * a.M * a.es))[cc];
+            ((u32x4*)a.crops)[(int64_t)r * 25 * rch + c] = v;
+        } else if (c < 25 * rch + pch) {
+            const int cc = c - 25 * rch, row = a.rows[p];
+            if ((unsigned)row < (unsigned)a.HW) v = ((const u32x4*)(a.par + ((int64_t)b * a.HW + row) * a.c_par * a.es))[cc];
+            ((u32x4*)a.feat)[(int64_t)r * fch + cc] = v;
+        } else {
+            const int cc = c - 25 * rch - pch, row = a.rows[p];
+            if ((unsigned)row < (unsigned)a.HW) v = ((const u32x4*)(a.ext + ((int64_t)b * a.HW + row) * a.M * a.es))[cc];
+            ((u32x4*)a.feat)[(int64_t)r * fch + a.e_off * a.es / 16 + cc] = v;
         }
     }
 }
@@ -372,4 +516,59 @@ extern "C" int hesic_gmm_rc_decode(const hesic_gmm_desc* d, const void* scales, 
         hipLaunchKernelGGL(rc_decode_kernel<float>, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *d, (const float*)scales, (const float*)means,
                            weights, meta, channels_per_stream, S, bytes, n_bytes, offsets, counts, y_hat, y_dtype);
     HESIC_LAUNCH_RETURN("gmm_rc_decode");
+}
+
+extern "C" int hesic_rc_encode_streams_ordered(const int32_t* triples, const int32_t* meta, int B, int M, int HW, int channels_per_stream,
+                                               const int32_t* order, uint8_t* slots, int64_t cap, int32_t* counts, int32_t* status, void* stream) {
+    HESIC_CHECK_ARG(triples && meta && order && slots && counts && status, "rc_encode_streams_ordered: null pointer");
+    HESIC_CHECK_ARG(B > 0 && M > 0 && HW > 0 && channels_per_stream >= 1 && channels_per_stream <= M, "rc_encode_streams_ordered: bad geometry");
+    HESIC_CHECK_ARG((int64_t)B * M * HW < (1ll << 31) / 3, "rc_encode_streams_ordered: batch too large for 32-bit element indices");
+    HESIC_CHECK_ARG(cap >= hesic_rc_stream_cap((int64_t)channels_per_stream * HW), "rc_encode_streams_ordered: slots of %lld bytes, a stream needs %lld",
+                    (long long)cap, (long long)hesic_rc_stream_cap((int64_t)channels_per_stream * HW));
+    const int S = (M + channels_per_stream - 1) / channels_per_stream;
+    hipLaunchKernelGGL(rc_encode_ordered_kernel, dim3((B * S + 63) / 64), dim3(64), 0, (hipStream_t)stream, triples, meta, B, M, HW,
+                       channels_per_stream, S, order, slots, cap, counts, status);
+    HESIC_LAUNCH_RETURN("rc_encode_streams_ordered");
+}
+
+extern "C" int hesic_joint_gather_batch(const void* y_rows, int dtype, int M, int Wp, int64_t rows_per_image, const int32_t* centre,
+                                        const int32_t* rows, int group_offset, int P, int HW, int B, void* crops, const void* par, int c_par,
+                                        const void* ext, int e_off, void* feat, int c_feat, void* stream) {
+    HESIC_CHECK_ARG(y_rows && centre && rows && crops && par && feat, "joint_gather_batch: null pointer");
+    HESIC_CHECK_ARG(dtype == HESIC_H16 || dtype == HESIC_F32, "joint_gather_batch: bad dtype");
+    HESIC_CHECK_ARG(B > 0 && M > 0 && Wp > 4 && rows_per_image > 0 && HW > 0 && P > 0 && group_offset >= 0 && (int64_t)group_offset + P <= HW,
+                    "joint_gather_batch: bad geometry (the group [offset, offset + P) must lie inside the HW pixels, P > 0)");
+    const int es = dtype == HESIC_H16 ? 2 : 4;
+    HESIC_CHECK_ARG(c_par > 0 && c_par <= c_feat && e_off >= 0 && (M * es) % 16 == 0 && (c_par * es) % 16 == 0 && (c_feat * es) % 16 == 0 &&
+                        (e_off * es) % 16 == 0 && (!ext || e_off + M <= c_feat),
+                    "joint_gather_batch: rows must be whole 16-byte chunks and the feature slices must fit");
+    HESIC_CHECK_ARG((int64_t)B * P * (25 * M + c_feat) < (1ll << 31) && (int64_t)B * rows_per_image * M < (1ll << 40),
+                    "joint_gather_batch: batch too large for 32-bit row indices");
+    JointGather a;
+    a.y_rows = (const unsigned char*)y_rows; a.es = es; a.M = M; a.Wp = Wp; a.rows_per_image = rows_per_image;
+    a.centre = centre + group_offset; a.rows = rows + group_offset; a.B = B; a.P = P; a.HW = HW;
+    a.crops = (unsigned char*)crops; a.par = (const unsigned char*)par; a.c_par = c_par; a.ext = (const unsigned char*)ext; a.e_off = e_off;
+    a.feat = (unsigned char*)feat; a.c_feat = c_feat;
+    const int64_t chunks = (int64_t)B * P * ((25 * M + c_par + (ext ? M : 0)) * es / 16);
+    hipLaunchKernelGGL(joint_gather_batch_kernel, dim3(grid_for(chunks, 256, 256 * 4)), dim3(256), 0, (hipStream_t)stream, a);
+    HESIC_LAUNCH_RETURN("joint_gather_batch");
+}
+
+extern "C" int hesic_gmm_rc_decode_step(const hesic_gmm_desc* d, const float* scales, const float* means, const int32_t* meta, int channels_per_stream,
+                                        const uint8_t* bytes, int64_t n_bytes, const int64_t* offsets, const int32_t* counts, uint64_t* state,
+                                        int first, const int32_t* centre, int group_offset, int n_pixels, void* y_rows, int y_dtype,
+                                        int64_t rows_per_image, void* stream) {
+    if (int e = check_codec_gmm(d, "gmm_rc_decode_step")) return e;
+    HESIC_CHECK_ARG(d->K == 1 && d->dtype == HESIC_F32, "gmm_rc_decode_step: K = 1 and fp32 (scale, mean) rows only");
+    HESIC_CHECK_ARG(scales && means && meta && offsets && counts && state && centre && y_rows && n_bytes >= 0 && (bytes || n_bytes == 0),
+                    "gmm_rc_decode_step: bad arguments");
+    HESIC_CHECK_ARG(y_dtype == HESIC_H16 || y_dtype == HESIC_F32, "gmm_rc_decode_step: bad y_rows dtype");
+    HESIC_CHECK_ARG(channels_per_stream >= 1 && channels_per_stream <= d->M, "gmm_rc_decode_step: bad channels_per_stream");
+    HESIC_CHECK_ARG(rows_per_image > 0 && n_pixels > 0 && group_offset >= 0 && (int64_t)group_offset + d->HW <= n_pixels,
+                    "gmm_rc_decode_step: the group [offset, offset + P) must lie inside the n_pixels of the map");
+    const int S = (d->M + channels_per_stream - 1) / channels_per_stream;
+    const int n = d->B * S;
+    hipLaunchKernelGGL(rc_decode_step_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *d, scales, means, meta, channels_per_stream, S,
+                       bytes, n_bytes, offsets, counts, state, first, centre + group_offset, y_rows, y_dtype, rows_per_image);
+    HESIC_LAUNCH_RETURN("gmm_rc_decode_step");
 }

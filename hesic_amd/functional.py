@@ -1971,7 +1971,8 @@ def rc_check(minmax, channels, M):
         mm, ch = int(mm), [int(c) for c in ch]
         if mm < 1 or 2 * mm + 1 > L.CODEC_MAX_ALPHABET:
             raise ValueError(f"device range coder: an alphabet of 2 * {mm} + 1 symbols is outside its limit of {L.CODEC_MAX_ALPHABET} (one table "
-                             "row per wave in LDS); code this pair with the per-pair HSIC.compress / decompress, which has no such limit")
+                             "row per wave in LDS); code this pair with the per-pair HSIC.compress / decompress (HESIC+: HSICJoint.compress / "
+                             "decompress), which have no such limit")
         if len(ch) > M or any(c < 0 or c >= M for c in ch) or any(a >= b for a, b in zip(ch, ch[1:])):
             raise ValueError(f"device range coder: the coded channels must be ascending indices in [0, {M})")
         mms.append(mm)
@@ -2020,10 +2021,12 @@ def gmm_rc_ranges(scales, means, weights, y_hat, minmax, channels, K, scale_boun
     return out
 
 
-def gmm_rc_encode(scales, means, weights, y_hat, minmax, channels, K, channels_per_stream=1, scale_bound=0.11):
+def gmm_rc_encode(scales, means, weights, y_hat, minmax, channels, K, channels_per_stream=1, scale_bound=0.11, order=None):
     """One view of a batch -> (bytes, counts): ``counts`` int32 (B, S), S = ceil(M / channels_per_stream), the byte length of every stream
     (0 beyond an image's coded channels), ``bytes`` uint8 the streams back to back in (b, s) order -- both on the device; what crosses
-    to the host is the payload and the counts.  Raises if a stream overflowed its slot or a symbol had no frequency."""
+    to the host is the payload and the counts.  Raises if a stream overflowed its slot or a symbol had no frequency.
+    ``order``: int32 (H * W) on the device, the raster index of the i-th pixel in coding order -- the HESIC+ stream (pixel-major, walked
+    through that permutation; include/hesic_codec.h) instead of the channel-major HESIC stream."""
     B, KM, H, W = scales.shape
     M = KM // K
     cps, S = _rc_streams(M, channels_per_stream)
@@ -2034,7 +2037,14 @@ def gmm_rc_encode(scales, means, weights, y_hat, minmax, channels, K, channels_p
     slots = torch.empty((B * S, cap), dtype=torch.uint8, device=dev)
     counts = torch.empty((B, S), dtype=torch.int32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    L.call("hesic_rc_encode_streams", L.ptr(triples), L.ptr(meta), B, M, H * W, cps, L.ptr(slots), cap, L.ptr(counts), L.ptr(status), L.stream())
+    if order is None:
+        L.call("hesic_rc_encode_streams", L.ptr(triples), L.ptr(meta), B, M, H * W, cps, L.ptr(slots), cap, L.ptr(counts), L.ptr(status), L.stream())
+    else:
+        L.require_cuda(order)
+        if order.dtype != torch.int32 or order.numel() != H * W or not order.is_contiguous():
+            raise ValueError(f"gmm_rc_encode: order must be a contiguous int32 tensor of {H * W} pixels")
+        L.call("hesic_rc_encode_streams_ordered", L.ptr(triples), L.ptr(meta), B, M, H * W, cps, L.ptr(order), L.ptr(slots), cap, L.ptr(counts),
+               L.ptr(status), L.stream())
     offsets = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
     st, total = (int(v) for v in torch.stack([status[0].to(torch.int64), offsets[-1]]).cpu())
     if st:
@@ -2070,6 +2080,40 @@ def gmm_rc_decode(scales, means, weights, minmax, channels, K, data, counts, out
            L.ptr(y_hat), L.dt(out_dtype), L.stream())
     del keep
     return y_hat
+
+
+def joint_gather_batch(y_rows, Wp, centre, rows, group_offset, P, crops, par, ext, e_off, feat):
+    """One wavefront group of a batch of HESIC+ latent maps (``hesic_joint_gather_batch``): ``y_rows`` (B, rows, M) the padded maps,
+    ``centre`` / ``rows`` int32 (HW) the padded and raster row of every pixel in coding order, ``par`` (B, HW, c_par), ``ext``
+    (B, HW, M) or None -> ``crops`` (>= B * P, 25, M) and ``feat`` (>= B * P, c_feat), rows b * P + p."""
+    B, n_rows, M = y_rows.shape
+    L.require_cuda(y_rows, centre, rows, crops, par, ext, feat)
+    HW = centre.numel()
+    # the entry point sees pointers only: every size it relies on is checked here
+    if (crops.shape[0] < B * P or crops.shape[1:] != (5, 5, M) or feat.dim() != 2 or feat.shape[0] < B * P or par.dim() != 3 or par.shape[:2] != (B, HW)
+            or rows.numel() != HW or centre.dtype != torch.int32 or rows.dtype != torch.int32 or (ext is not None and ext.shape != (B, HW, M))):
+        raise ValueError("joint_gather_batch: crops (>= B P, 5, 5, M), feat (>= B P, c_feat), par (B, HW, c_par), ext (B, HW, M), int32 centre / rows (HW) expected")
+    if any(t is not None and (t.dtype != y_rows.dtype or not t.is_contiguous()) for t in (y_rows, crops, par, ext, feat)):
+        raise ValueError("joint_gather_batch: the maps, crops, par, ext and feat must be contiguous tensors of one dtype")
+    L.call("hesic_joint_gather_batch", L.ptr(y_rows), L.dt(y_rows), M, int(Wp), n_rows, L.ptr(centre), L.ptr(rows), int(group_offset), int(P),
+           centre.numel(), B, L.ptr(crops), L.ptr(par), par.shape[2], L.ptr(ext), int(e_off), L.ptr(feat), feat.shape[1], L.stream())
+
+
+def gmm_rc_decode_step(sm, B, P, M, meta, channels_per_stream, data, offsets, counts, state, first, centre, group_offset, y_rows, scale_bound=0.11):
+    """The symbols of one wavefront group for every stream of a batch (``hesic_gmm_rc_decode_step``): ``sm`` fp32 (B * P, 2 M) rows
+    [scales | means] of the entropy-parameter net, ``state`` int64 (B * S, 4) the coder states (begun here when ``first``), written as
+    symbol - minmax into rows ``centre[group_offset + p]`` of the padded maps ``y_rows`` (B, rows, M)."""
+    L.require_cuda(sm, meta, data, offsets, counts, state, centre, y_rows)
+    cps, S = _rc_streams(M, channels_per_stream)
+    if sm.dtype != torch.float32 or sm.numel() != B * P * 2 * M or not sm.is_contiguous():
+        raise ValueError(f"gmm_rc_decode_step: sm must be contiguous fp32 ({B * P}, {2 * M}) rows")
+    if (meta.shape != (B, M + 2) or meta.dtype != torch.int32 or offsets.numel() != B * S or offsets.dtype != torch.int64 or counts.numel() != B * S
+            or counts.dtype != torch.int32 or state.numel() != B * S * 4 or state.dtype != torch.int64 or data.dtype != torch.uint8
+            or centre.dtype != torch.int32 or y_rows.shape[0] != B or y_rows.shape[2] != M):
+        raise ValueError("gmm_rc_decode_step: meta / offsets / counts / state / centre / y_rows do not fit the batch")
+    d = L.GmmDesc(B, P, M, 1, L.F32, 0, 2 * M, 0, M, float(scale_bound), 0.0)
+    L.call("hesic_gmm_rc_decode_step", C.byref(d), L.ptr(sm), L.ptr(sm), L.ptr(meta), cps, L.ptr(data), data.numel(), L.ptr(offsets), L.ptr(counts),
+           L.ptr(state), int(bool(first)), L.ptr(centre), int(group_offset), centre.numel(), L.ptr(y_rows), L.dt(y_rows), y_rows.shape[1], L.stream())
 
 
 def quantize_symbols(y, means=None):

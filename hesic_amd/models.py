@@ -637,6 +637,45 @@ def _decompress_z(bottleneck, strings, size):
     return EntropyModel.decompress(bottleneck, list(strings), bottleneck._build_indexes(shape), medians)
 
 
+def _batch_blobs(who, kind, blobs, h_matrix, M):
+    """The host-side validation of ``decompress_batch`` (both codecs), before anything is launched: every blob parses
+    (``bitstream.parse_pair``), is of ``kind``, and they agree on size and channels_per_stream; alphabets and channel lists are what the
+    device coder takes.  Returns (B, H, W, cps, per view (minmax, channels, z strings, stream bytes back to back, (B, S) lengths))."""
+    from . import bitstream
+    blobs = list(blobs)
+    if not blobs:
+        raise ValueError(f"{who}: no blobs")
+    pairs = [bitstream.parse_pair(bl) for bl in blobs]
+    for p in pairs:
+        bitstream.require_kind(p, kind, who)
+    B, p0 = len(pairs), pairs[0]
+    H, W, cps = p0["height"], p0["width"], p0["channels_per_stream"]
+    for p in pairs:
+        if (p["height"], p["width"]) != (H, W):
+            raise ValueError(f"{who}: all blobs of one call must have the same size, got {H}x{W} and {p['height']}x{p['width']}; "
+                             "decode each size in a call of its own")
+        if p["channels_per_stream"] != cps:
+            raise ValueError(f"{who}: all blobs of one call must have the same channels_per_stream")
+        if p["channels"] != M:
+            raise ValueError(f"{who}: the blob codes {p['channels']} latent channels, this model has {M}")
+    if H % 64 or W % 64:
+        raise ValueError(f"{who}: the header's size {H}x{W} is not a multiple of 64")
+    per_view = []
+    for vi in range(2):
+        vs = [p["views"][vi] for p in pairs]
+        minmax = [v["minmax"] for v in vs]
+        channels = [[c for c, f in enumerate(v["flags"]) if f] for v in vs]
+        Fn.rc_check(minmax, channels, M)                   # alphabets beyond the kernels' limit: refused here
+        S = (M + cps - 1) // cps
+        counts = [[len(s) for s in v["streams"]] + [0] * (S - len(v["streams"])) for v in vs]
+        per_view.append((minmax, channels, [v["z"] for v in vs], b"".join(s for v in vs for s in v["streams"]), counts))
+    if h_matrix.dim() != 3 or h_matrix.shape[-2:] != (3, 3) or h_matrix.shape[0] not in (1, B):
+        raise ValueError(f"{who}: h_matrix must be ({B}, 3, 3) (or (1, 3, 3)), got {tuple(h_matrix.shape)}")
+    if not h_matrix.is_cuda:
+        raise RuntimeError(f"{who}: the device range coder needs h_matrix on a ROCm device (no CPU fallback)")
+    return B, H, W, cps, per_view
+
+
 # --------------------------------------------------------------------------------------------- HESIC
 class HSIC(StereoCompressionModel):
     """HESIC (reference ``HSIC``, ywz/mywork/newnet1.py:696-783)."""
@@ -862,36 +901,7 @@ class HSIC(StereoCompressionModel):
     def decompress_batch(self, blobs, h_matrix):
         """``blobs``: what ``compress_batch`` returned, in any grouping and order (all of one image size); ``h_matrix`` (B, 3, 3) the
         matching homographies.  Everything is validated on the host before the first launch."""
-        from . import bitstream
-        blobs = list(blobs)
-        if not blobs:
-            raise ValueError("HSIC.decompress_batch: no blobs")
-        pairs = [bitstream.parse_pair(bl) for bl in blobs]
-        B, p0 = len(pairs), pairs[0]
-        H, W, cps = p0["height"], p0["width"], p0["channels_per_stream"]
-        for p in pairs:
-            if (p["height"], p["width"]) != (H, W):
-                raise ValueError(f"HSIC.decompress_batch: all blobs of one call must have the same size, got {H}x{W} and {p['height']}x{p['width']}; "
-                                 "decode each size in a call of its own")
-            if p["channels_per_stream"] != cps:
-                raise ValueError("HSIC.decompress_batch: all blobs of one call must have the same channels_per_stream")
-            if p["channels"] != self.M:
-                raise ValueError(f"HSIC.decompress_batch: the blob codes {p['channels']} latent channels, this model has {self.M}")
-        if H % 64 or W % 64:
-            raise ValueError(f"HSIC.decompress_batch: the header's size {H}x{W} is not a multiple of 64")
-        if h_matrix.dim() != 3 or h_matrix.shape[-2:] != (3, 3) or h_matrix.shape[0] not in (1, B):
-            raise ValueError(f"HSIC.decompress_batch: h_matrix must be ({B}, 3, 3) (or (1, 3, 3)), got {tuple(h_matrix.shape)}")
-        if not h_matrix.is_cuda:
-            raise RuntimeError("HSIC.decompress_batch: the device range coder needs h_matrix on a ROCm device (no CPU fallback)")
-        per_view = []
-        for vi in range(2):
-            vs = [p["views"][vi] for p in pairs]
-            minmax = [v["minmax"] for v in vs]
-            channels = [[c for c, f in enumerate(v["flags"]) if f] for v in vs]
-            Fn.rc_check(minmax, channels, self.M)                   # alphabets beyond the kernels' limit: refused here
-            S = (self.M + cps - 1) // cps
-            counts = [[len(s) for s in v["streams"]] + [0] * (S - len(v["streams"])) for v in vs]
-            per_view.append((minmax, channels, [v["z"] for v in vs], b"".join(s for v in vs for s in v["streams"]), counts))
+        B, H, W, cps, per_view = _batch_blobs("HSIC.decompress_batch", "hesic", blobs, h_matrix, self.M)
         if self.entropy_bottleneck1._offset.numel() == 0:
             self.update()
         dev, cdt, size = h_matrix.device, Fn.compute_dtype(), (H, W)
@@ -1299,6 +1309,30 @@ class HSICJoint(StereoCompressionModel):
         cuts = np.flatnonzero(np.diff(t[order])) + 1
         return np.split(order.astype(np.int64), cuts)
 
+    def _coder_inputs(self, x1, x2, h_matrix):
+        """The encoder's side of the real bit-stream for B pairs, shared by ``compress`` and ``compress_batch`` (their streams must be formed
+        from the same numbers): per view (y_hat, z strings, z_hat, scales, means) with the context model evaluated on the whole maps.
+        Call it under ``torch.no_grad()`` and ``Fn.no_split_k()`` with the context masks applied to the weights."""
+        size = (x1.shape[-2], x1.shape[-1])
+        cdt = Fn.compute_dtype()
+        y1_lo, y1 = self.encoder1.latent(x1, exact=True, lo_abs=self._LO_ABS)
+        z1 = _seq3_hi(self.h_a1, y1_lo)
+        z1_strings = self.entropy_bottleneck1.compress(z1)
+        z1_hat = _decompress_z(self.entropy_bottleneck1, z1_strings, z1.size()[-2:]).to(cdt)
+        y1_hat = _round_latent(self.gaussian_conditional1, y1)
+        sc1, mu1 = self._gauss_full(1, self._params_view(1, z1_hat), y1_hat)
+        x1_hat = self.decoder1(y1_hat)
+        x1_warp = warp_perspective(x1, h_matrix, size)
+        y2_lo, y2 = self.encoder2.latent(x1_warp, x2, exact=True, lo_abs=self._LO_ABS)
+        z2 = _seq3_hi(self.h_a2, y2_lo)
+        z2_strings = self.entropy_bottleneck2.compress(z2)
+        z2_hat = _decompress_z(self.entropy_bottleneck2, z2_strings, z2.size()[-2:]).to(cdt)
+        x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
+        y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
+        y2_hat = _round_latent(self.gaussian_conditional2, y2)
+        sc2, mu2 = self._gauss_full(2, self._params_view(2, z2_hat), y2_hat, y1_hat_w)
+        return (y1_hat, z1_strings, z1_hat, sc1, mu1), (y2_hat, z2_strings, z2_hat, sc2, mu2)
+
     ORDER_RASTER, ORDER_WAVEFRONT = 0, 1
     _TABLE_BYTES = 256 << 20           # bound of one batch of cumulative-frequency tables (device buffer + its host copy)
 
@@ -1317,28 +1351,11 @@ class HSICJoint(StereoCompressionModel):
             raise ValueError('compress: order must be "raster" or "wavefront"')
         if self.entropy_bottleneck1._offset.numel() == 0:
             self.update()
-        size = (x1.shape[-2], x1.shape[-1])
         start = time.time()
         with torch.no_grad(), Fn.no_split_k():
             self.context_prediction1.weight.data *= self.context_prediction1.mask
             self.context_prediction2.weight.data *= self.context_prediction2.mask
-            cdt = Fn.compute_dtype()
-            y1_lo, y1 = self.encoder1.latent(x1, exact=True, lo_abs=self._LO_ABS)
-            z1 = _seq3_hi(self.h_a1, y1_lo)
-            z1_strings = self.entropy_bottleneck1.compress(z1)
-            z1_hat = self.entropy_bottleneck1.decompress(z1_strings, z1.size()[-2:]).to(cdt)
-            y1_hat = _round_latent(self.gaussian_conditional1, y1)
-            sc1, mu1 = self._gauss_full(1, self._params_view(1, z1_hat), y1_hat)
-            x1_hat = self.decoder1(y1_hat)
-            x1_warp = warp_perspective(x1, h_matrix, size)
-            y2_lo, y2 = self.encoder2.latent(x1_warp, x2, exact=True, lo_abs=self._LO_ABS)
-            z2 = _seq3_hi(self.h_a2, y2_lo)
-            z2_strings = self.entropy_bottleneck2.compress(z2)
-            z2_hat = self.entropy_bottleneck2.decompress(z2_strings, z2.size()[-2:]).to(cdt)
-            x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
-            y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
-            y2_hat = _round_latent(self.gaussian_conditional2, y2)
-            sc2, mu2 = self._gauss_full(2, self._params_view(2, z2_hat), y2_hat, y1_hat_w)
+            (y1_hat, z1_strings, z1_hat, sc1, mu1), (y2_hat, z2_strings, z2_hat, sc2, mu2) = self._coder_inputs(x1, x2, h_matrix)
             head = bytearray(np.array(x1.shape[2:], dtype=np.uint16).tobytes())
             enc = RangeEncoder()
             bound = self.gaussian_conditional1._bound()
@@ -1682,6 +1699,175 @@ class HSICJoint(StereoCompressionModel):
             x2_hat = self.decoder2(y2_hat, x1_hat_warp)
         return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat,
                 "dectime": time.time() - start}
+
+
+    # ------------------------------------------------------------------------------- batched bit-stream, coded on the device
+    # HESIC+ for a whole batch with the range coder on the GPU (csrc/codec.hip; stream definition in include/hesic_codec.h).  The encoder
+    # knows every latent: one evaluation of the context model on the whole maps of the B images, one launch for the coding intervals, one
+    # for the streams (walked in wavefront order), one to compact them.  The decoder walks the groups of ``_wavefronts`` ONCE for the B
+    # images together: per group a gather of the B * P crops and feature rows, the masked 5x5 conv, the three 1x1 layers and the step
+    # decoder, which writes the symbols straight into the padded maps -- six dependent launches, no host in the loop; the walk of a view is
+    # captured as one HIP graph and replayed.  As in the per-pair path the convs run unsplit, so that the decoder sums in the encoder's order.
+    def compress_batch(self, x1, x2, h_matrix, channels_per_stream=1):
+        """(B, 3, H, W) pairs -> dict(blobs: one ``bytes`` per pair (``bitstream.pack_pair``, kind "joint"), bpp_real: one figure per pair
+        over its 2 H W pixels, y1_hat, y2_hat, z1_hat, z2_hat).  ``channels_per_stream`` as in ``HSIC.compress_batch``.  An image whose
+        latents need an alphabet beyond the device coder's 1024 symbols raises ``ValueError``: code that pair with ``compress``."""
+        import numpy as np
+        from . import bitstream
+        _check_pair(x1, x2, h_matrix)
+        if not x1.is_cuda:
+            raise RuntimeError("HSICJoint.compress_batch: the device range coder needs tensors on a ROCm device (no CPU fallback)")
+        cps = int(channels_per_stream)
+        if not 1 <= cps <= min(self.M, 255):
+            raise ValueError(f"HSICJoint.compress_batch: channels_per_stream must be in [1, {min(self.M, 255)}], got {channels_per_stream}")
+        if self.entropy_bottleneck1._offset.numel() == 0:
+            self.update()
+        B, _, H, W = x1.shape
+        with torch.no_grad(), Fn.no_split_k():
+            self.context_prediction1.weight.data *= self.context_prediction1.mask
+            self.context_prediction2.weight.data *= self.context_prediction2.mask
+            (y1_hat, z1_strings, z1_hat, sc1, mu1), (y2_hat, z2_strings, z2_hat, sc2, mu2) = self._coder_inputs(x1, x2, h_matrix)
+            order = torch.from_numpy(np.concatenate(self._wavefronts(H // 16, W // 16)).astype(np.int32)).to(x1.device)
+            bound = self.gaussian_conditional1._bound()
+            # one small device -> host read: per image, view and channel max |y_hat| (minmax and the flags follow from it)
+            peak = torch.stack([y.float().abs().amax(dim=(2, 3)) for y in (y1_hat, y2_hat)]).cpu()
+            views = [[None, None] for _ in range(B)]
+            for vi, (y_hat, z_strings, sc, mu) in enumerate(((y1_hat, z1_strings, sc1, mu1), (y2_hat, z2_strings, sc2, mu2))):
+                flags = (peak[vi] > 0).tolist()
+                minmax = [int(max(float(peak[vi, b].max()), 1.0)) for b in range(B)]
+                channels = [[c for c, f in enumerate(flags[b]) if f] for b in range(B)]
+                data, counts = Fn.gmm_rc_encode(sc, mu, None, y_hat, minmax, channels, 1, cps, bound, order=order)
+                data, counts = data.cpu().numpy().tobytes(), counts.cpu().tolist()
+                pos = 0
+                for b in range(B):
+                    streams = []
+                    for n in counts[b][:bitstream.n_streams(flags[b], cps)]:
+                        streams.append(data[pos:pos + n])
+                        pos += n
+                    views[b][vi] = {"minmax": minmax[b], "flags": tuple(int(f) for f in flags[b]), "z": z_strings[b], "streams": streams}
+        blobs = [bitstream.pack_pair({"kind": "joint", "mode": payload_mode_bytes(), "height": H, "width": W, "channels": self.M,
+                                      "channels_per_stream": cps, "views": views[b]}) for b in range(B)]
+        return {"blobs": blobs, "bpp_real": [len(bl) * 8 / (H * W * 2) for bl in blobs],
+                "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
+
+    _BATCH_WALKS = 8          # cached walks kept per module (two per decoded (size, B, cps): one per view), least recently used first out
+
+    def _batch_walk_state(self, which, yh, yw, B, cps, dev):
+        """Static buffers (and, once captured, the graph) of the batched walk of one view, cached on the module per (view, map size, B,
+        channels_per_stream, device) and dropped when the format or the weights change.  The cache keeps the ``_BATCH_WALKS`` most recently
+        used entries: a new key costs two Python-paced walks (warm-up and capture) before its first replay, so a caller with many sizes
+        or batch sizes (a folder's tail batches) pays that again when a key comes back after eight others.  An evicted entry's graph and
+        buffers may still be in use by a replay that has not finished: eviction happens at the start of a later call on the same stream,
+        and the allocator defers the release of memory a stream still uses, so nothing is freed under a running replay."""
+        import numpy as np
+        cdt = Fn.compute_dtype()
+        ctx_m = self.context_prediction1 if which == 1 else self.context_prediction2
+        ep = self.entropy_parameters1 if which == 1 else self.entropy_parameters2
+        tag = (Fn._cache_epoch, cdt) + tuple((p_.data_ptr(), p_._version) for p_ in list(ctx_m.parameters()) + list(ep.parameters()))
+        cache = self.__dict__.setdefault("_bw_cache", {})
+        key = (which, yh, yw, B, cps, dev.index)
+        st = cache.pop(key, None)
+        if st is not None and st["tag"] == tag:
+            cache[key] = st                                  # most recently used last
+            return st
+        while len(cache) >= self._BATCH_WALKS:               # every entry owns a captured graph and a worst-case payload buffer
+            cache.pop(next(iter(cache)))
+        if not hasattr(ctx_m, "_packer"):
+            ctx_m._packer = Fn.PackedWeight()
+        M, Wp, HW = self.M, yw + 4, yh * yw
+        groups = self._wavefronts(yh, yw)
+        pmax = max(len(g) for g in groups)
+        all_pix = np.concatenate(groups)
+        centre = (all_pix // yw + 2) * Wp + (all_pix % yw) + 2
+        c_par = (self.h_s1 if which == 1 else self.h_s2)[4].out_channels
+        c_feat = c_par + ctx_m.out_channels + (M if which == 2 else 0)
+        S = (M + cps - 1) // cps
+        st = {"tag": tag, "groups": [len(g) for g in groups], "ctx_m": ctx_m, "ep": ep, "graph": None, "Wp": Wp, "c_par": c_par,
+              "e_off": c_par + ctx_m.out_channels,
+              "y_pad": torch.zeros((B, M, yh + 4, Wp), dtype=cdt, device=dev).contiguous(memory_format=torch.channels_last),
+              "par": torch.zeros((B, HW, c_par), dtype=cdt, device=dev),
+              "ext": torch.zeros((B, HW, M), dtype=cdt, device=dev) if which == 2 else None,
+              "centre": torch.from_numpy(centre.astype(np.int32)).to(dev), "rows": torch.from_numpy(all_pix.astype(np.int32)).to(dev),
+              "crops": torch.zeros((B * pmax, 5, 5, M), dtype=cdt, device=dev), "feat": torch.zeros((B * pmax, c_feat), dtype=cdt, device=dev),
+              "meta": torch.zeros((B, M + 2), dtype=torch.int32, device=dev),
+              # the payload's worst case is the encoder's slot: 4 bytes per symbol + 16 per stream (a stream is at most 2 per symbol + flush)
+              "data": torch.zeros(B * (4 * M * HW + 16 * S), dtype=torch.uint8, device=dev),
+              "offsets": torch.zeros(B * S, dtype=torch.int64, device=dev), "counts": torch.zeros(B * S, dtype=torch.int32, device=dev),
+              "coder": torch.zeros((B * S, 4), dtype=torch.int64, device=dev)}
+        st["y_rows"] = st["y_pad"].permute(0, 2, 3, 1).reshape(B, (yh + 4) * Wp, M)          # a view of the NHWC storage
+        cache[key] = st
+        return st
+
+    def _batch_walk(self, st, B, cps, bound):
+        """The launches of one view's walk: per group gather -> masked conv into its slice of the feature rows -> the 1x1 net -> step decoder."""
+        ctx_m, M, off = st["ctx_m"], self.M, 0
+        for P in st["groups"]:
+            n = B * P
+            Fn.joint_gather_batch(st["y_rows"], st["Wp"], st["centre"], st["rows"], off, P, st["crops"], st["par"], st["ext"], st["e_off"], st["feat"])
+            crops = st["crops"][:n].permute(0, 3, 1, 2)                                                        # (B P, M, 5, 5), NHWC in memory
+            feat = st["feat"][:n].view(n, st["feat"].shape[1], 1, 1)
+            Fn.conv2d_into(crops, ctx_m.weight, ctx_m.bias, feat, st["c_par"], kernel_size=5, stride=1, padding=0, mask=ctx_m.mask,
+                           tap_mask=ctx_m._tap_mask, packer=ctx_m._packer)
+            sm = _seq3_hi(st["ep"], feat)                                                                      # (B P, 2M, 1, 1) fp32: [scales | means]
+            Fn.gmm_rc_decode_step(sm, B, P, M, st["meta"], cps, st["data"], st["offsets"], st["counts"], st["coder"], off == 0, st["centre"], off,
+                                  st["y_rows"], bound)
+            off += P
+
+    def _decode_view_batch(self, which, params, view, counts_cps, extra, yh, yw):
+        minmax, channels, _z, data, counts = view
+        B, cps = params.shape[0], counts_cps
+        dev = params.device
+        st = self._batch_walk_state(which, yh, yw, B, cps, dev)
+        if len(data) > st["data"].numel():
+            raise ValueError(f"HSICJoint.decompress_batch: {len(data)} stream bytes for view {which}, beyond the coder's worst case of "
+                             f"{st['data'].numel()} for this batch: not a payload of this coder")
+        bound = float(self.gaussian_conditional1._bound())
+        # refill the static buffers the walk reads (a replayed graph names their addresses)
+        st["y_pad"].zero_()
+        st["par"].copy_(params.permute(0, 2, 3, 1).reshape(st["par"].shape))
+        if extra is not None:
+            st["ext"].copy_(extra.permute(0, 2, 3, 1).reshape(st["ext"].shape))
+        st["meta"].copy_(Fn.rc_meta(minmax, channels, self.M, dev))
+        if data:
+            st["data"][:len(data)].copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
+        cnt = torch.tensor(counts, dtype=torch.int32).reshape(-1)
+        st["counts"].copy_(cnt)
+        st["offsets"].copy_(torch.cumsum(cnt, 0, dtype=torch.int64) - cnt)
+        if st["graph"] is None or st["bound"] != bound:
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):                  # warm-up off the default stream (packs weights, loads kernels): a full decode
+                self._batch_walk(st, B, cps, bound)
+            torch.cuda.current_stream().wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._batch_walk(st, B, cps, bound)
+            st["graph"], st["bound"] = g, bound
+            st["y_pad"].zero_()
+        st["graph"].replay()
+        return st["y_pad"][:, :, 2:-2, 2:-2].contiguous(memory_format=torch.channels_last)
+
+    def decompress_batch(self, blobs, h_matrix):
+        """``blobs``: what ``compress_batch`` returned, in any grouping and order (all of one image size and channels_per_stream);
+        ``h_matrix`` (B, 3, 3) the matching homographies.  Everything is validated on the host before the first launch."""
+        B, H, W, cps, per_view = _batch_blobs("HSICJoint.decompress_batch", "joint", blobs, h_matrix, self.M)
+        if self.entropy_bottleneck1._offset.numel() == 0:
+            self.update()
+        dev, cdt, size = h_matrix.device, Fn.compute_dtype(), (H, W)
+        yh, yw = H // 16, W // 16
+        zs = (yh // 4, yw // 4)
+        with torch.no_grad(), Fn.no_split_k():
+            self.context_prediction1.weight.data *= self.context_prediction1.mask
+            self.context_prediction2.weight.data *= self.context_prediction2.mask
+            z1_hat = _decompress_z(self.entropy_bottleneck1, per_view[0][2], zs).to(dev, cdt)
+            z2_hat = _decompress_z(self.entropy_bottleneck2, per_view[1][2], zs).to(dev, cdt)
+            y1_hat = self._decode_view_batch(1, self._params_view(1, z1_hat), per_view[0], cps, None, yh, yw)
+            x1_hat = self.decoder1(y1_hat)
+            x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
+            y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
+            y2_hat = self._decode_view_batch(2, self._params_view(2, z2_hat), per_view[1], cps, y1_hat_w, yh, yw)
+            x2_hat = self.decoder2(y2_hat, x1_hat_warp)
+        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
 
 
 # -------------------------------------------------------------------- enhancement (SURVEY 8f rank 1)
