@@ -21,6 +21,7 @@ LIB_PATH_F16 = os.path.join(_HERE, "libhesic_hip_f16.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_hip.h")
 STEREO_H_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_stereo_h.h")
 CODEC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_codec.h")
+MSSSIM_LOSS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_msssim_loss.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -257,6 +258,12 @@ _CODEC_SIGS = {
                                  _i32),
 }
 
+# include/hesic_msssim_loss.h: the backward of hesic_ssim_scale (functional.ms_ssim, rd_loss(distortion="ms-ssim")), in both libraries
+_MSSSIM_LOSS_SIGS = {
+    "hesic_ssim_scale_backward": ([_vp, _P(_i64), _vp, _P(_i64), _i32, _i32, _i32, _i32, _f32, _vp, _P(_i64), _P(C.c_double), _i32, _i32, _vp,
+                                   _vp, _vp, _vp], _i32),
+}
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -283,6 +290,13 @@ def declared_codec_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_msssim_loss_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_msssim_loss.h (used by the MS-SSIM loss ABI test)."""
+    with open(MSSSIM_LOSS_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def _load(h16):
     l = _libs.get(h16)
     if l is None:
@@ -302,7 +316,7 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} exports no hesic_abi_version -- not this package's library; {rebuild}") from None
         if ver != ABI_VERSION:
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
-        for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()):
+        for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

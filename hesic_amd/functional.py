@@ -2417,9 +2417,174 @@ class _RdLossFn(torch.autograd.Function):
 SCALED_LOSS = True      # False (Trainer.step): loss.backward() is called on the unscaled loss, skip the six g_loss multiplies
 
 
-def rd_loss(out, x1, x2, lmbda):
-    """dict(loss, bpp_loss, mse_loss) like the reference's criterion; differentiable through ``loss``."""
+# ----------------------------------------------------------------------------- MS-SSIM as a training loss
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+DISTORTIONS = ("mse", "ms-ssim")
+_ms_consts = {}
+
+
+def _ms_const(values, device):
+    """A small fp64 device constant (per-scale counts, exponents), built by fill kernels and kept: no host-to-device copy, so a step that
+    meets a new image size while it is being captured into a graph stays capturable."""
+    key = (tuple(values), device)
+    t = _ms_consts.get(key)
+    if t is None:
+        t = torch.empty(len(values), dtype=torch.float64, device=device)
+        for i, v in enumerate(values):
+            t[i:i + 1].fill_(float(v))
+        if not torch.cuda.is_current_stream_capturing():      # a tensor made during a capture lives in that graph's memory pool
+            _ms_consts[key] = t
+    return t
+
+
+def _ms_ssim_check(x_hat, x):
+    if x_hat.shape != x.shape or x.dim() != 4:
+        raise ValueError("ms_ssim: two (N, C, H, W) tensors of the same shape")
+    if min(x.shape[-2:]) <= 160:
+        raise ValueError("ms_ssim: the smaller image side must exceed (11 - 1) * 2^4 = 160")
+
+
+def _ms_ssim_forward(a, b, data_range):
+    """The launches and the arithmetic of ``models.ms_ssim`` on fp32 images ``a`` (reconstruction) and ``b`` (target); returns the (N,) fp64
+    value, the fp64 sums (5, B, C, 2), the images of the five scales [(a, b)] and the valid positions per scale."""
+    B, Cc, H, W = a.shape
+    sums = torch.empty((5, B, Cc, 2), dtype=torch.float64, device=a.device).fill_(0)
+    counts, pyramid = [], []
+    for lvl in range(5):
+        sa, sb = (C.c_int64 * 4)(*a.stride()), (C.c_int64 * 4)(*b.stride())
+        L.call("hesic_ssim_scale", L.ptr(a), sa, L.ptr(b), sb, B, Cc, H, W, float(data_range), L.ptr(sums[lvl]), L.stream())
+        counts.append((H - 10) * (W - 10))
+        pyramid.append((a, b))
+        if lvl < 4:
+            Ho, Wo = (H + 2 * (H % 2) - 2) // 2 + 1, (W + 2 * (W % 2) - 2) // 2 + 1
+            na, nb = (torch.empty((B, Cc, Ho, Wo), dtype=torch.float32, device=a.device) for _ in range(2))
+            L.call("hesic_avgpool2_pad", L.ptr(a), sa, L.ptr(na), B, Cc, H, W, L.stream())
+            L.call("hesic_avgpool2_pad", L.ptr(b), sb, L.ptr(nb), B, Cc, H, W, L.stream())
+            a, b, H, W = na, nb, Ho, Wo
+    means = sums / _ms_const(counts, sums.device).reshape(5, 1, 1, 1)
+    v = torch.cat((means[:4, :, :, 1], means[4:, :, :, 0]), 0).clamp_min(0)                 # cs of scales 1-4, ssim of scale 5
+    w = _ms_const(MS_SSIM_WEIGHTS, sums.device).reshape(5, 1, 1)
+    return torch.prod(v ** w, 0).mean(1), sums, pyramid, counts
+
+
+def _ms_ssim_backward(pyramid, sums, counts, grad_out, data_range):
+    """d(sum_n grad_out[n] MS[n]) / d x_hat: five launches of ``hesic_ssim_scale_backward`` from the coarsest scale to the finest, each
+    adding 0.25 x the coarser gradient of a pixel's pool cell.  ``grad_out``: (N,) fp64 on the device.  Contiguous fp32 result."""
+    cnt, wts = (C.c_int64 * 5)(*counts), (C.c_double * 5)(*MS_SSIM_WEIGHTS)
+    grad_out = grad_out.contiguous()
+    g = None
+    for lvl in range(4, -1, -1):
+        a, b = pyramid[lvl]
+        B, Cc, H, W = a.shape
+        gx = torch.empty((B, Cc, H, W), dtype=torch.float32, device=a.device)
+        L.call("hesic_ssim_scale_backward", L.ptr(a), (C.c_int64 * 4)(*a.stride()), L.ptr(b), (C.c_int64 * 4)(*b.stride()), B, Cc, H, W,
+               float(data_range), L.ptr(sums), cnt, wts, 5, lvl, L.ptr(grad_out), L.ptr(g), L.ptr(gx), L.stream())
+        g = gx
+    return g
+
+
+class _MsSsimFn(torch.autograd.Function):
+    """``ms_ssim`` with a gradient for the reconstruction (the target is a constant): keeps the pooled images of scales 2-5 and the fp64 sums."""
+
+    @staticmethod
+    def forward(ctx, x_hat, x, data_range):
+        a, b = (t if t.dtype == torch.float32 else t.float() for t in (x_hat, x))
+        val, sums, pyramid, counts = _ms_ssim_forward(a, b, data_range)
+        ctx.save_for_backward(sums, *[t for pair in pyramid for t in pair])
+        ctx.meta = (counts, float(data_range))
+        return val
+
+    @staticmethod
+    def backward(ctx, g_val):
+        sums, *flat = ctx.saved_tensors
+        counts, data_range = ctx.meta
+        pyramid = [(flat[2 * i], flat[2 * i + 1]) for i in range(5)]
+        return _ms_ssim_backward(pyramid, sums, counts, g_val.to(torch.float64), data_range), None, None
+
+
+def ms_ssim(x_hat, x, data_range=1.0):
+    """``models.ms_ssim`` (same launches, same (N,) fp64 values) as a differentiable function of ``x_hat``: the backward is five launches of
+    ``hesic_ssim_scale_backward`` (csrc/msssim.hip) and returns an fp32 gradient of ``x_hat``'s shape; ``x`` is a constant.  Where a
+    per-scale mean is <= 0 the definition clamps it: that image's value and gradient are 0.  16-bit images are cast to fp32 first."""
+    L.require_cuda(x_hat, x)
+    _ms_ssim_check(x_hat, x)
+    return _apply(_MsSsimFn, x_hat, x, data_range)
+
+
+class _RdMsSsimLossFn(torch.autograd.Function):
+    """The R-D criterion with MS-SSIM as the distortion: loss = lmbda * ((1 - mean_n MS(x1_hat, x1)) + (1 - mean_n MS(x2_hat, x2))) + bpp --
+    no 255^2 factor, reconstructions not clamped.  Returns (loss, bpp, mse, ms_ssim_loss); the MSE is still reported (the fused reduction
+    behind bpp computes it anyway).  Gradients: the likelihoods' as in ``_RdLossFn``, the reconstructions' from ``hesic_ssim_scale_backward``
+    with grad_out = -lmbda / N per image."""
+
+    @staticmethod
+    def forward(ctx, lmbda, x1, x2, x1_hat, x2_hat, *liks):
+        import math
+        B, Cc, H, W = x1.shape
+        npix = B * H * W
+        acc = _zeros(3, torch.float64, x1.device)
+        liks = tuple(l if (l.is_contiguous() or l.is_contiguous(memory_format=_CL)) else l.contiguous() for l in liks)
+        if RD_SUMS_FUSED and len(liks) <= 8:
+            rd_sums(liks, [acc[0:1]] * len(liks), [(x1_hat, x1), (x2_hat, x2)], [acc[1:2], acc[2:3]])
+        else:
+            for l in liks:
+                sum_log2(l, acc[0:1])
+            sum_sq_diff(x1_hat, x1, acc[1:2])
+            sum_sq_diff(x2_hat, x2, acc[2:3])
+        out3 = torch.empty(3, dtype=torch.float32, device=x1.device)
+        L.call("hesic_rd_loss_combine", L.ptr(acc), 0.0, npix, B * Cc * H * W, L.ptr(out3), L.stream())      # lambda 0: (bpp, bpp, mse)
+        saved, metas, msl = [], [], None
+        for xh, x in ((x1_hat, x1), (x2_hat, x2)):
+            a, b = (t if t.dtype == torch.float32 else t.float() for t in (xh, x))
+            val, sums, pyramid, counts = _ms_ssim_forward(a, b, 1.0)
+            d = 1.0 - val.mean()
+            msl = d if msl is None else msl + d
+            saved += [sums, *[t for pair in pyramid for t in pair]]
+            metas.append(counts)
+        loss = (float(lmbda) * msl).float() + out3[1]
+        ctx.save_for_backward(*saved, *liks)
+        ctx.meta = (float(lmbda), B, metas, -1.0 / (math.log(2.0) * npix))
+        bpp, mse, msl = out3[1], out3[2], msl.float()
+        ctx.mark_non_differentiable(bpp, mse, msl)
+        return loss, bpp, mse, msl
+
+    @staticmethod
+    def backward(ctx, g_loss, g_bpp, g_mse, g_msl):
+        lmbda, B, metas, lik_scale = ctx.meta
+        saved = ctx.saved_tensors
+        liks = saved[22:]
+        # as in _RdLossFn: g_loss stays on the device and is applied only when SCALED_LOSS is on -- here to the B values of grad_out
+        # instead of the gradient images
+        go = torch.empty(B, dtype=torch.float64, device=g_loss.device).fill_(-lmbda / B)
+        if SCALED_LOSS:
+            go = go.mul_(g_loss)
+        grads = []
+        for v in range(2):
+            sums, *flat = saved[11 * v:11 * v + 11]
+            grads.append(_ms_ssim_backward([(flat[2 * i], flat[2 * i + 1]) for i in range(5)], sums, metas[v], go, 1.0))
+        gl = []
+        for l in liks:
+            o = torch.empty_like(l)
+            L.call("hesic_log_backward", L.ptr(l), lik_scale, L.ptr(o), l.numel(), L.stream())
+            gl.append(o)
+        if SCALED_LOSS:
+            gl = [t.mul_(g_loss) for t in gl]
+        return (None, None, None, grads[0], grads[1], *gl)
+
+
+def rd_loss(out, x1, x2, lmbda, distortion="mse"):
+    """dict(loss, bpp_loss, mse_loss) like the reference's criterion; differentiable through ``loss``.  ``distortion="ms-ssim"``:
+    loss = lmbda * ms_ssim_loss + bpp_loss with ms_ssim_loss = (1 - mean MS(x1_hat, x1)) + (1 - mean MS(x2_hat, x2)) (no 255^2 factor; images
+    with a side > 160), reported next to the other three."""
+    if distortion not in DISTORTIONS:
+        raise ValueError(f"rd_loss: distortion must be one of {DISTORTIONS}, got {distortion!r}")
     lk = out["likelihoods"]
+    if distortion == "ms-ssim":
+        L.require_cuda(x1, x2, out["x1_hat"], out["x2_hat"])
+        _ms_ssim_check(out["x1_hat"], x1)
+        _ms_ssim_check(out["x2_hat"], x2)
+        loss, bpp, mse, msl = _RdMsSsimLossFn.apply(lmbda, x1, x2, out["x1_hat"], out["x2_hat"], lk["y1"], lk["y2"], lk["z1"], lk["z2"])
+        return {"loss": loss, "bpp_loss": bpp.detach(), "mse_loss": mse.detach(), "ms_ssim_loss": msl.detach()}
     loss, bpp, mse = _RdLossFn.apply(lmbda, x1, x2, out["x1_hat"], out["x2_hat"], lk["y1"], lk["y2"], lk["z1"], lk["z2"])
     return {"loss": loss, "bpp_loss": bpp.detach(), "mse_loss": mse.detach()}
 

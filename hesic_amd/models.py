@@ -2145,7 +2145,8 @@ def ms_ssim(x_hat, x, data_range=1.0):
     as the reference's evaluation calls it (ywz/mywork/test3real.py:107-109; the package is third party and absent: its published
     algorithm is restated in ``csrc/msssim.hip``, pinned against the oracle and an independent numpy route).  Five launches of
     ``hesic_ssim_scale`` with four 2 x 2 pools in between; no host synchronisation.  fp32 images of any strides; the smaller side must
-    exceed 160 pixels (five scales of an 11-tap window)."""
+    exceed 160 pixels (five scales of an 11-tap window).  This is the metric and carries no gradient: to train for it use
+    ``functional.ms_ssim`` (same values, differentiable in ``x_hat``) or ``functional.rd_loss(..., distortion="ms-ssim")``."""
     L.require_cuda(x_hat, x)
     if x_hat.shape != x.shape or x.dim() != 4:
         raise ValueError("ms_ssim: two (N, C, H, W) tensors of the same shape")

@@ -348,8 +348,13 @@ class Trainer:
     """Holds the model, ``Adam(parameters, lr)`` + ``Adam(aux_parameters, aux_lr)`` (newtrain1.py:294-295) over flat
     parameter / gradient buffers and, when a process group is up, one in-place reducer per optimiser group."""
 
-    def __init__(self, model, lr=1e-4, aux_lr=1e-3, lmbda=1e-2, bucket_mb=25.0, overlap=True, force_collectives=False, collective=None):
-        self.model, self.lmbda = model, float(lmbda)
+    def __init__(self, model, lr=1e-4, aux_lr=1e-3, lmbda=1e-2, bucket_mb=25.0, overlap=True, force_collectives=False, collective=None,
+                 distortion="mse"):
+        if distortion not in Fn.DISTORTIONS:
+            raise ValueError(f"Trainer: distortion must be one of {Fn.DISTORTIONS}, got {distortion!r}")
+        # "ms-ssim": loss = lmbda * ((1 - MS-SSIM(x1_hat, x1)) + (1 - MS-SSIM(x2_hat, x2))) + bpp (functional.rd_loss); lmbda has no 255^2
+        # factor there, so values of the MSE criterion do not carry over
+        self.model, self.lmbda, self.distortion = model, float(lmbda), distortion
         main, aux = list(model.parameters()), list(model.aux_parameters())
         self.main_group, self.aux_group = FlatGroup(main), FlatGroup(aux)
         self.on_gpu = self.main_group.flat_p.is_cuda
@@ -368,11 +373,18 @@ class Trainer:
 
     def _forward_loss(self, x1, x2, h_matrix, noise):
         out = self.model(x1, x2, h_matrix, noise=noise)
-        return Fn.rd_loss(out, x1, x2, self.lmbda)
+        return Fn.rd_loss(out, x1, x2, self.lmbda, distortion=self.distortion)
+
+    def _check_inputs(self, x1, x2):
+        """Host-side refusals, before anything is launched (or staged into a graph's static buffers)."""
+        if self.distortion == "ms-ssim" and min(min(x1.shape[-2:]), min(x2.shape[-2:])) <= 160:
+            raise ValueError("Trainer: distortion='ms-ssim' needs images whose smaller side exceeds (11 - 1) * 2^4 = 160 (five scales of an "
+                             f"11-tap window), got {tuple(x1.shape[-2:])}")
 
     def step(self, x1, x2, h_matrix, noise=None):
         """One iteration in the reference's order: zero both -> forward -> R-D loss backward -> (reduce) -> optimizer.step
         -> aux loss backward -> (reduce) -> aux_optimizer.step.  Returns the loss dict (device scalars, no sync)."""
+        self._check_inputs(x1, x2)
         self.model.train()
         self.main_group.zero_grad()
         self.aux_group.zero_grad()
@@ -466,6 +478,7 @@ class GraphedTrainer(Trainer):
     def step(self, x1, x2, h_matrix, noise=None):
         if not self.capturable:
             return super().step(x1, x2, h_matrix, noise=noise)
+        self._check_inputs(x1, x2)
         self._stage(x1, x2, h_matrix, noise)
         self.calls += 1
         if self.graph is None and self.calls <= self.warmup:

@@ -649,8 +649,11 @@ int hesic_probe_mfma_loop(const void* src_64k, float* sink_4k, int iters, double
 int hesic_ssim_scale(const float* x, const int64_t x_strides[4], const float* y, const int64_t y_strides[4], int B, int C, int H, int W,
                      float data_range, double* sums, void* stream);
 int hesic_avgpool2_pad(const float* x, const int64_t x_strides[4], float* y, int B, int C, int H, int W, void* stream);
+/* MS-SSIM as a training loss: the backward of hesic_ssim_scale, one launch per scale, is declared and documented in hesic_msssim_loss.h
+ * (included at the end of this header; a header of its own like the stereo-homography and codec entry points, HESIC_ABI_VERSION unchanged). */
 
 #ifdef __cplusplus
 }
 #endif
+#include "hesic_msssim_loss.h"
 #endif /* HESIC_HIP_H */
