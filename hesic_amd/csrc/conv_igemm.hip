@@ -1585,6 +1585,245 @@ __global__ __launch_bounds__(256, 2) void igemm_tr4_kernel(const IgemmArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------- stride-1 5 x 5 conv, Cin = 128: the input patch resident in LDS
+// The 128 -> 960 output convs of the entropy-parameter nets (gmm_sigma / gmm_means / gmm_weights of gmm_hyper_y1 / _y2, ywz/mywork/newnet1.py) on
+// igemm_glds_kernel<128,128,64> refill a 16 KB x tile AND a 16 KB w tile in each of their 50 stages, although the 25 x tiles of a channel chunk are
+// 25 whole-pixel shifts of ONE input patch.  Here (the stride-1 sibling of igemm_tr4_kernel's HALO form) a block takes a 16 x 16 q-tile x 128 couts,
+// stages the tile's 20 x 20 patch with all 128 channels ONCE (400 pixels x 256 B = 100 KB, through registers, out-of-image pixels as zeros from
+// out-of-range buffer offsets) and keeps it for the whole K loop; the ring carries weight tiles only (NS x 16 KB, 2 LDS-DMA pieces per wave and
+// stage instead of 8), and each weight tile serves twice the pixels: 0.9 MB through the global -> LDS path per 256 pixels x 128 couts instead of
+// 3.2 MB.  8 waves as 2 cout x 4 pixel slices of 64 x 64, one block per CU (100 KB + ring of dynamic LDS).
+//   * 16-byte slot s of patch pixel (hy, hx) sits at position s ^ (hx & 15): the 16-lane groups of a b128 fragment read ({0-3, 12-15} of one tile
+//     row + {4-11} of the next: 16 consecutive hx modulo 16) cover the 64 banks exactly once at every tap shift;
+//   * a fragment read of (tap, chunk c, k-substep ks) is a per-lane base + a wave-uniform tap offset, XOR (c * 128 + ks * 32);
+//   * the epilogue (igemm_glds_kernel's plain one: bias, act / act2 by act_split, fp32 straight from the accumulators and / or the 16-bit tile
+//     through LDS) stages its tile in the dead patch; its stores are plain global stores (no register soffset: see the store-hazard note above).
+// K walk per output value exactly as igemm_glds_kernel walks a stride-1 launch (taps in raster order, channel chunk innermost, k-substeps
+// ascending, the same mfma_32x32x16 operands into the same accumulator layout): bit-identical.
+#ifndef IGEMM_S1P_NS
+#define IGEMM_S1P_NS 2      // depth of the weight ring (2 or 3: measured equal)
+#endif
+constexpr int S1P_HW = 20, S1P_PATCH = S1P_HW * S1P_HW * 256, S1P_WT = 128 * 64 * 2;
+constexpr int s1p_lds_bytes(int ns) { return S1P_PATCH + ns * S1P_WT; }
+template <int NS>
+__global__ __launch_bounds__(512, 1) void igemm_s1p_kernel(const IgemmArgs a) {
+    using T = h16_t;
+    constexpr int BM = 256, BN = 128, BK = 64, NW = 8, NT = NW * 64;
+    constexpr int CPR = BK * 2 / 16, RPB = 256 / (BK * 2);
+    constexpr int WT = S1P_WT, WI = BN * CPR / 64 / NW;          // 2 weight DMA pieces per wave and stage
+    constexpr int HW_ = S1P_HW, HPIX = HW_ * HW_, RING = S1P_PATCH;
+    constexpr int WM = 2, WN = 4, MI = BN / WM / 32, NI = BM / WN / 32;
+    constexpr int OROW = BN * 2 + 16;
+    static_assert(NS >= 2 && NS <= 3 && BM * OROW <= S1P_PATCH && s1p_lds_bytes(NS) <= 160 * 1024, "LDS budget");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];    // patch | weight ring
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    // order: cout tile, tile x, tile y, image (one phase, no K slices)
+    uint32_t rest = fdiv((uint32_t)bid, a.fd_nt);
+    const int nt = bid - (int)rest * a.n_tiles;
+    uint32_t q_ = fdiv(rest, a.fd_tx);
+    const int tx = (int)(rest - q_ * (uint32_t)a.tiles_x);
+    rest = q_; q_ = fdiv(rest, a.fd_ty);
+    const int ty = (int)(rest - q_ * (uint32_t)a.tiles_y);
+    const int b = (int)q_;
+    const int n0 = nt * BN;
+    constexpr int kchunks = 128 / BK, nsteps = 25 * kchunks;
+    const T* __restrict__ xg = (const T*)a.x;
+
+    const int wm = wave % WM, wn = wave / WM;
+    const int frow = lane & 31, fh = lane >> 5;
+    auto off = [&](int row, int slot) { return (row * CPR + (slot ^ ((row / RPB) & (CPR - 1)))) * 16; };
+
+    constexpr uint32_t OOB = 0x80000000u;
+    asm volatile("" ::"v"((__attribute__((address_space(3))) unsigned char*)smem) : "memory");
+    const int neg = (a.KH * a.W + a.KW) * a.x_ps;                  // elements; keeps every patch offset non-negative
+    const int row0 = ty * 16, col0 = tx * 16;
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(xg + ((int64_t)b * a.H + row0) * a.W * a.x_ps - neg), 0, (int)OOB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, (int)OOB, 0x00020000);
+    const int gco = a.x_group_step ? (nt / a.tiles_per_group) * a.x_group_step : 0;      // grouped launch: this cout tile's input slice
+    const int act_eff = (a.act_split && n0 >= a.act_split) ? a.act2 : a.act;
+    uint32_t wv[WI];
+    {
+        const int prow = lane / CPR, pslot = lane % CPR;
+#pragma unroll
+        for (int i = 0; i < WI; ++i) {
+            const int row = (wave * WI + i) * (64 / CPR) + prow;
+            const int ls = pslot ^ ((row / RPB) & (CPR - 1));
+            wv[i] = (n0 + row) < a.Cout ? (uint32_t)(((n0 + row) * a.Cin + ls * 8) * 2) : OOB;
+        }
+    }
+    // weight cursor (SGPR): stage t is chunk t & 1 of tap t >> 1
+    const uint32_t wtap = (uint32_t)(a.Cout * a.Cin * 2);
+    uint32_t s_w = 0;
+    int w_chunk = 0;
+    auto issue = [&](int buf) {
+        unsigned char* ws = smem + RING + buf * WT;
+        const uint32_t sw = s_w + (uint32_t)(w_chunk * BK * 2);
+#pragma unroll
+        for (int i = 0; i < WI; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (__attribute__((address_space(3))) void*)(ws + (wave * WI + i) * 1024), 16, (int)wv[i], (int)sw, 0, 0);
+        if (++w_chunk == kchunks) { w_chunk = 0; s_w += wtap; }
+    };
+#pragma unroll
+    for (int s = 0; s < NS - 1; ++s) issue(s);                     // the first weight stages fly under the patch load
+
+    // the input patch of the tile, once, through registers (16 bytes per lane and step: position e & 15 of patch pixel e >> 4)
+    {
+        constexpr int HSTEPS = (HPIX * 16 + NT - 1) / NT;
+        u32x4 hv[HSTEPS];
+#pragma unroll
+        for (int i = 0; i < HSTEPS; ++i) {
+            const int e = i * NT + tid, hp = e >> 4, hy = hp / HW_, hx = hp - hy * HW_;
+            const int iy = row0 - 2 + hy, ix = col0 - 2 + hx;
+            const int ls = (e & 15) ^ (hx & 15);
+            const bool ok = hp < HPIX && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+            const uint32_t vo = ok ? (uint32_t)(((((hy - 2) * a.W + ix) * a.x_ps + a.x_co + gco + ls * 8) + neg) * 2) : OOB;
+            hv[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, (int)vo, 0, 0);          // out of range: zeros
+        }
+#pragma unroll
+        for (int i = 0; i < HSTEPS; ++i) {
+            const int e = i * NT + tid;
+            if (e < HPIX * 16) *(u32x4*)(smem + e * 16) = hv[i];
+        }
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                   // the K loop's first barrier publishes the patch
+    }
+    // consumer side of the patch: this lane's pixels of the tile (pixel p = (p >> 4, p & 15)) as patch addresses at tap (0, 0)
+    int hbase[NI];
+    const int hsw = frow & 15;
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+        const int pq = wn * (BM / WN) + j * 32 + frow;
+        hbase[j] = ((pq >> 4) * HW_ + (pq & 15)) * 256;
+    }
+
+    f32x16 acc[MI][NI];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    {
+        // The K loop is rotated by one k-substep against igemm_glds_kernel's: the wait + barrier that publish stage s + 1 stand in front of the LAST
+        // substep's MFMAs of stage s, and the first fragments of stage s + 1 are read there -- under those MFMAs instead of behind the barrier
+        // with all eight waves of the CU idle on the LDS latency (the x fragments never depended on the barrier: the patch is resident).  The
+        // buffer of stage s is free once every wave is past that barrier (its last fragments are in registers: lgkmcnt(0) in front of it), so the
+        // request for stage s + NS follows the barrier directly.  Same products in the same order.
+        constexpr int KS = BK / 16;
+        int buf = 0, nxt = NS - 1, ky = 0, kx = 0, chunk = 0;
+        const unsigned char* ws = smem;
+        int hx_[NI], hchunk = 0;
+        auto next_stage = [&]() {        // fragment addresses of the stage under the consumer cursor; the cursor moves on
+            ws = smem + RING + buf * WT;
+            buf = (buf + 1 == NS) ? 0 : buf + 1;
+            hchunk = chunk * 128;
+#pragma unroll
+            for (int j = 0; j < NI; ++j) hx_[j] = (hbase[j] + (ky * HW_ + kx) * 256) | (((fh ^ (hsw + kx)) & 15) << 4);
+            if (++chunk == kchunks) { chunk = 0; if (++kx == 5) { kx = 0; ++ky; } }
+        };
+        h16x8 wf[2][MI], xf[2][NI];
+        auto ldf = [&](int set, int ks) {
+#pragma unroll
+            for (int i = 0; i < MI; ++i) wf[set][i] = *(const h16x8*)(ws + off(wm * (BN / WM) + i * 32 + frow, ks * 2 + fh));
+#pragma unroll
+            for (int j = 0; j < NI; ++j) xf[set][j] = *(const h16x8*)(smem + (hx_[j] ^ (hchunk + ks * 32)));
+        };
+        __builtin_amdgcn_s_barrier();                              // stages 0 .. NS - 2 and the patch are in LDS (waited for above)
+        issue(nxt);
+        nxt = (nxt + 1 == NS) ? 0 : nxt + 1;
+        next_stage();
+        ldf(0, 0);
+        for (int step = 0; step < nsteps; ++step) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                if (ks + 1 < KS) ldf((ks + 1) & 1, ks + 1);
+                else if (step + 1 < nsteps) {
+                    const int rem = nsteps - 2 - step;             // stages behind stage step + 1
+                    if constexpr (NS == 2) wait_dma_groups<WI>(0);
+                    else wait_dma_groups<WI>(rem < NS - 2 ? rem : NS - 2);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    if (step + NS < nsteps) issue(nxt);
+                    nxt = (nxt + 1 == NS) ? 0 : nxt + 1;
+                    next_stage();
+                    ldf(0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < MI; ++i)
+#pragma unroll
+                    for (int j = 0; j < NI; ++j)
+                        acc[i][j] = mfma_32x32x16_h16(wf[ks & 1][i], xf[ks & 1][j], acc[i][j], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+
+    if (a.y32) {
+        // fp32 copy of the output straight from the accumulators (as igemm_glds_kernel)
+#pragma unroll
+        for (int j = 0; j < NI; ++j) {
+            const int pr = wn * (BM / WN) + j * 32 + frow;
+            const int qy = row0 + (pr >> 4), qx = col0 + (pr & 15);
+            if (qy < a.QH && qx < a.QW) {
+                float* dst = a.y32 + (((int64_t)b * a.Ho + qy) * a.Wo + qx) * a.y32_ps + a.y32_co + n0;
+#pragma unroll
+                for (int i = 0; i < MI; ++i)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int cl = wm * (BN / WM) + i * 32 + 8 * g + 4 * fh;
+                        if (n0 + cl < a.Cout) {
+                            const f32x4 bq = a.bias ? *(const f32x4*)(a.bias + n0 + cl) : f32x4{0.f, 0.f, 0.f, 0.f};
+                            *(f32x4*)(dst + cl) = f32x4{apply_act(acc[i][j][4 * g] + bq[0], act_eff), apply_act(acc[i][j][4 * g + 1] + bq[1], act_eff),
+                                                        apply_act(acc[i][j][4 * g + 2] + bq[2], act_eff), apply_act(acc[i][j][4 * g + 3] + bq[3], act_eff)};
+                        }
+                    }
+            }
+        }
+        if (!a.y) return;
+    }
+    // 16-bit output: the tile through the (dead) patch, full NHWC rows out
+    T* __restrict__ yg = (T*)a.y;
+    __syncthreads();     // every wave is done with the patch before the tile overwrites it
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int cl = wm * (BN / WM) + i * 32 + 8 * g + 4 * fh;
+            float bv[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bv[e] = (a.bias && (n0 + cl + e) < a.Cout) ? a.bias[n0 + cl + e] : 0.f;
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+                const int pr = wn * (BM / WN) + j * 32 + frow;
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = apply_act(acc[i][j][4 * g + e] + bv[e], act_eff);
+                uint32_t h0, l0, h1, l1;
+                split_h2(v[0], v[1], h0, l0);
+                split_h2(v[2], v[3], h1, l1);
+                *(u32x2*)(smem + pr * OROW + cl * 2) = u32x2{h0, h1};
+            }
+        }
+    }
+    __syncthreads();
+    constexpr int CPO = BN * 2 / 16;
+    constexpr int TOT = BM * CPO;
+#pragma unroll
+    for (int c = tid; c < TOT; c += NT) {
+        const int pr = c / CPO, cc = c % CPO;
+        const int qy = row0 + (pr >> 4), qx = col0 + (pr & 15);
+        const int ch = n0 + cc * 8;
+        if (qy < a.QH && qx < a.QW && ch < a.Cout) {
+            const int64_t o = (((int64_t)b * a.Ho + qy) * a.Wo + qx) * a.y_ps + a.y_co + ch;
+            *(u32x4*)(yg + o) = *(const u32x4*)(smem + pr * OROW + cc * 16);
+        }
+    }
+}
+
 // y = act(sum of the K-slice partials + bias) as bf16 (y) and / or fp32 (y32): one thread per pixel and 8 channels
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, int nslice, int64_t npix, int Cout,
                                                             const float* __restrict__ bias, int act, h16_t* __restrict__ y,
@@ -2104,6 +2343,23 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
     }
     const size_t ws_need = ksplit > 1 ? (size_t)ksplit * d->B * d->Ho * d->Wo * d->Cout * sizeof(float) : 0;
     if (g_ws_need) { *g_ws_need = ws_need; return 0; }
+    // Stride-1 5 x 5 convs on 128 input channels with the input patch resident in LDS (igemm_s1p_kernel: 16 x 16 q-tile x 128 couts, one block
+    // per CU).  HESIC_IGEMM_S1_PATCH = 0: never, 1 (default): auto, 2: whenever the shape is eligible; read on every call.
+    // Auto, set by measurement: the 256-pixel grid must fill the chip (>= 256 blocks, rounds of the 256 CUs >= 70 % full),
+    // the 16 x 16 tiles must not hang over the map by more than 1/8 of their pixels (the 56 x 68 maps of config C5, 20 tiles of 256 for 3808
+    // pixels: a tie) and there must be >= 32 pixel tiles (B = 4 at 32 x 32, grouped: the launch alone gains, 64 -> 57 us, the HESIC+ B = 4
+    // step does not).  Smaller grids lose outright (128 blocks: 36 -> 43 us; B = 1: 28 -> 43 us).
+    bool use_s1p = false;
+    {
+        const char* e = getenv("HESIC_IGEMM_S1_PATCH");
+        const int mode = e ? atoi(e) : 1;
+        const bool shape = fast && !d->transposed && s == 1 && d->KH == 5 && d->KW == 5 && p == 2 && cin_k == 128 && !hilo && !gdn &&
+                           !d->tap_mask_lo && !a.in_abs && BN == 128 && ksplit == 1;
+        const int64_t t16 = (int64_t)((a.QW + 15) / 16) * ((a.QH + 15) / 16) * a.B, nb = t16 * a.n_tiles, rounds = (nb + 255) / 256;
+        const bool fills = nb >= 256 && nb * 10 >= rounds * 256 * 7 && (int64_t)a.QH * a.QW * a.B * 8 >= t16 * 256 * 7 && t16 >= 32;
+        use_s1p = shape && mode && (mode >= 2 || fills);
+        if (use_s1p) bm = 256;
+    }
     HESIC_CHECK_ARG(ws_need <= g_ws_bytes, "conv2d_forward_ws: workspace too small (%zu < %zu bytes)", g_ws_bytes, ws_need);
     a.ksplit = ksplit; a.ws = g_ws;
     // 2-D pixel patch: as square as the q-grid allows
@@ -2112,6 +2368,7 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
     if (bm == 128 && a.QW >= 32 && a.QH < 8) TW = 32;
     if (TW > bm) TW = bm;
     int TH = bm / TW;
+    if (use_s1p) TW = TH = 16;                     // the patch kernel's only tile
     a.TW = TW; a.TH = TH; a.tw_shift = ilog2(TW);
     a.tiles_x = (a.QW + TW - 1) / TW; a.tiles_y = (a.QH + TH - 1) / TH;
     const int64_t nblocks = (int64_t)a.n_tiles * a.tiles_x * a.tiles_y * a.B * a.nphase * ksplit;
@@ -2130,6 +2387,7 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
     }
     if (g_plan_out) {
         if (use_tr4) { g_plan_out[0] = 128; g_plan_out[1] = 128; g_plan_out[2] = 64; g_plan_out[3] = 2; return 0; }
+        if (use_s1p) { g_plan_out[0] = 256; g_plan_out[1] = 128; g_plan_out[2] = 64; g_plan_out[3] = 1; return 0; }
         g_plan_out[0] = bm; g_plan_out[1] = BN; g_plan_out[2] = fast ? (((bm == 32) || (bm == 64 && BN == 64)) && cin_k % 128 == 0 ? 128 : (cin_k % 64 == 0 ? 64 : 32)) : BK; g_plan_out[3] = fast ? 1 : 0;
         return 0;
     }
@@ -2175,7 +2433,19 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
         const int stage = (bm + BN) * bk * 2;
         const int64_t per_cu = (nblocks + 255) / 256;
         const bool deep = bm < 128 ? per_cu * 4 * stage <= 160 * 1024 : (bk == 32 && per_cu * 4 * stage <= 160 * 1024);
-        if (bm == 256) {
+        if (use_s1p) {
+            // resident input patch, weights-only ring (igemm_s1p_kernel): more than the 64 KB of static LDS, requested once per device
+            constexpr int NS = IGEMM_S1P_NS, LDS = s1p_lds_bytes(NS);
+            static std::atomic<uint64_t> attr_done{0};
+            int dev = 0;
+            (void)hipGetDevice(&dev);
+            if (!((attr_done.load(std::memory_order_relaxed) >> (dev & 63)) & 1)) {
+                HESIC_CHECK_ARG(hipFuncSetAttribute((const void*)igemm_s1p_kernel<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess,
+                                "conv2d_forward: the resident-patch kernel needs %d bytes of dynamic LDS", LDS);
+                attr_done.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
+            }
+            hipLaunchKernelGGL((igemm_s1p_kernel<NS>), grid, dim3(512), LDS, st, a);
+        } else if (bm == 256) {
             // pair conv + GDN on 256 pixels x 128 couts: 8 waves of 64 x 64, one block per CU (see the tile choice above)
             hipLaunchKernelGGL((igemm_glds_kernel<256, 128, 64, 2, 3, 8, 0, 1>), grid, dim3(512), 0, st, a);
         } else if (use_tr4) {
