@@ -127,15 +127,23 @@ def combine(a, b_):
 
 
 def unit(R, q):
-    """sqrt(n) * 2^-24 * S_e: the unit bound of output ``q``."""
-    return math.sqrt(R["n"][q]) * U24 * R["S"][q]
+    """sqrt(n) * 2^-24 * S_e: the unit bound of output ``q`` (n: one count per output, or a tensor of per-element counts)."""
+    n = R["n"][q]
+    return (n.double().sqrt() if torch.is_tensor(n) else math.sqrt(n)) * U24 * R["S"][q]
+
+
+def storage_term(R, q):
+    """What storing output ``q`` in 16 bits may add to its error: u |ref_e| (+ h for a format with subnormals) where S_e > 0, else 0.  bf16
+    (u = 2^-8, h = 0) unless the reference names another format (``u16``, ``h16``: tests/enh_ref.py)."""
+    ref = R["ref"][q]
+    if not ((q == "y" and R["y16"]) or (q == "dx" and R["dx16"])):
+        return torch.zeros_like(ref)
+    h = R.get("h16", 0.0)
+    return R.get("u16", U8) * ref.abs() + (h * (R["S"][q] > 0) if h else 0.0)
 
 
 def bars(R, q, c=C_BAR):
-    bar = c * unit(R, q)
-    if (q == "y" and R["y16"]) or (q == "dx" and R["dx16"]):
-        bar = bar + U8 * R["ref"][q].abs()
-    return bar
+    return c * unit(R, q) + storage_term(R, q)
 
 
 def check(R, q, got, c=C_BAR):
@@ -147,7 +155,7 @@ def check(R, q, got, c=C_BAR):
     bar = bars(R, q, c)
     u = unit(R, q)
     live = u > 0
-    store = U8 * ref.abs() if ((q == "y" and R["y16"]) or (q == "dx" and R["dx16"])) else torch.zeros_like(err)
+    store = storage_term(R, q)
     ratio = float(((err - store).clamp_min(0)[live] / u[live]).max()) if bool(live.any()) else 0.0
     bad = ~(err <= bar)                              # NaN counts as a miss
     msg = ""
