@@ -22,6 +22,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_hip.h")
 STEREO_H_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_stereo_h.h")
 CODEC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_codec.h")
 MSSSIM_LOSS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_msssim_loss.h")
+TRAIN_CTL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_train_ctl.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -264,6 +265,15 @@ _MSSSIM_LOSS_SIGS = {
                                    _vp, _vp, _vp], _i32),
 }
 
+# include/hesic_train_ctl.h: device-resident step controls of the training step (train.FlatAdam on the control path), in both libraries
+_TRAIN_CTL_SIGS = {
+    "hesic_grad_norm_ctl": ([_vp, _i64, _vp, _vp, _vp, _vp], _i32),
+    "hesic_adam_step_ctl": ([_vp, _vp, _vp], _i32),
+}
+# the control block (HESIC_TRAIN_CTL_* of that header): fp32 entries, and the fp64 partials hesic_grad_norm_ctl needs
+CTL_LR, CTL_MAX_NORM, CTL_SKIP_NONFINITE, CTL_GRAD_NORM, CTL_CLIP_COEF, CTL_APPLIED, CTL_SKIPPED, CTL_FLOATS = 0, 1, 2, 3, 4, 5, 6, 8
+GRAD_NORM_MAX_BLOCKS = 1024
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -297,6 +307,13 @@ def declared_msssim_loss_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_train_ctl_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_train_ctl.h (used by the step-controls ABI test)."""
+    with open(TRAIN_CTL_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def _load(h16):
     l = _libs.get(h16)
     if l is None:
@@ -316,7 +333,8 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} exports no hesic_abi_version -- not this package's library; {rebuild}") from None
         if ver != ABI_VERSION:
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
-        for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()):
+        for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
+                + list(_TRAIN_CTL_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

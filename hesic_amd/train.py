@@ -135,14 +135,42 @@ class FlatGroup:
 class FlatAdam:
     """``torch.optim.Adam(params, lr)`` (newtrain1.py:294-295; no amsgrad / weight decay) over a ``FlatGroup``: ONE update
     launch for the whole group (``hesic_adam_step`` on the flat buffers; padding elements have zero gradient and stay
-    zero).  ``state_dict()`` / ``load_state_dict()`` speak ``torch.optim.Adam``'s per-parameter format."""
+    zero).  ``state_dict()`` / ``load_state_dict()`` speak ``torch.optim.Adam``'s per-parameter format.
 
-    def __init__(self, group: FlatGroup, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    ``controls`` (a dict with ``max_norm`` -- ``None``: no clipping --, ``skip_nonfinite`` and ``also_require``, another ``FlatAdam`` on
+    the control path or ``None``) switches the step to the device-resident controls of include/hesic_train_ctl.h: ``step()`` is then
+    ``hesic_grad_norm_ctl`` (the global L2 norm of the flat gradient, the clip coefficient and the apply / skip decision, written into the
+    control block ``ctl``) followed by ``hesic_adam_step_ctl``, which reads the learning rate, the coefficient and the decision from that
+    block.  Nothing is read back: the pair can be recorded into a HIP graph, and ``sync_lr()`` (a device fill OUTSIDE the graph) changes
+    the rate every later replay uses.  Without ``controls`` a step is the single ``hesic_adam_step`` it always was."""
+
+    def __init__(self, group: FlatGroup, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, controls=None):
         self.group, self.betas, self.eps = group, (float(betas[0]), float(betas[1])), float(eps)
         self.exp_avg = torch.zeros_like(group.flat_p)
         self.exp_avg_sq = torch.zeros_like(group.flat_p)
         self.step_count = torch.zeros((), dtype=torch.float32, device=group.flat_p.device)
         self.param_groups = [{"params": group.params, "lr": float(lr), "betas": self.betas, "eps": self.eps}]
+        self.ctl = self.partials = self.also_require = self._ctl_lr = None
+        if controls is not None:
+            from . import _lib as L
+            dev = group.flat_p.device
+            block = [0.0] * L.CTL_FLOATS
+            block[L.CTL_LR] = float(lr)
+            block[L.CTL_MAX_NORM] = 0.0 if controls.get("max_norm") is None else float(controls["max_norm"])
+            block[L.CTL_SKIP_NONFINITE] = 1.0 if controls.get("skip_nonfinite") else 0.0
+            block[L.CTL_CLIP_COEF], block[L.CTL_APPLIED] = 1.0, 1.0
+            self.ctl = torch.tensor(block, dtype=torch.float32).to(dev)
+            self.partials = torch.zeros(L.GRAD_NORM_MAX_BLOCKS, dtype=torch.float64, device=dev)
+            self.also_require = controls.get("also_require")
+            self._ctl_lr = float(lr)
+
+    def sync_lr(self):
+        """Control path: bring the control block's learning rate to ``param_groups[0]["lr"]`` (one device fill when it changed, nothing
+        otherwise).  Never call it while a graph is being captured: the fill would be recorded with today's value."""
+        lr = float(self.param_groups[0]["lr"])
+        if self.ctl is not None and lr != self._ctl_lr:
+            self.ctl[0:1].fill_(lr)
+            self._ctl_lr = lr
 
     def zero_grad(self, set_to_none=False):
         self.group.zero_grad()
@@ -155,7 +183,13 @@ class FlatAdam:
         c.p[0], c.g[0], c.m[0], c.v[0] = g.flat_p.data_ptr(), g.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
         c.step[0], c.numel[0] = self.step_count.data_ptr(), g.numel
         c.n, c.lr, c.beta1, c.beta2, c.eps = 1, float(self.param_groups[0]["lr"]), self.betas[0], self.betas[1], self.eps
-        L.call("hesic_adam_step", C.byref(c), L.stream())
+        if self.ctl is None:
+            L.call("hesic_adam_step", C.byref(c), L.stream())
+        else:
+            # the flat gradient is read twice and never scaled: the norm's launch pair decides, the update applies g * clip_coef
+            L.call("hesic_grad_norm_ctl", L.ptr(g.flat_g), g.numel, L.ptr(self.partials), L.ptr(self.ctl),
+                   None if self.also_require is None else L.ptr(self.also_require.ctl), L.stream())
+            L.call("hesic_adam_step_ctl", C.byref(c), L.ptr(self.ctl), L.stream())
         # the kernel writes through raw pointers: bump the version counters (like any in-place optimiser) -- every cache of
         # packed weights / GDN parameters / bottleneck tables is keyed on them
         torch.autograd.graph.increment_version(g.params)
@@ -176,6 +210,7 @@ class FlatAdam:
             self.step_count.fill_(float(st["step"]))
         if sd.get("param_groups"):
             self.param_groups[0]["lr"] = sd["param_groups"][0].get("lr", self.param_groups[0]["lr"])
+            self.sync_lr()
 
 
 class FlatReducer:
@@ -346,12 +381,41 @@ WGRAD_STREAM = False      # module switch (off): weight gradients on a stream of
 
 class Trainer:
     """Holds the model, ``Adam(parameters, lr)`` + ``Adam(aux_parameters, aux_lr)`` (newtrain1.py:294-295) over flat
-    parameter / gradient buffers and, when a process group is up, one in-place reducer per optimiser group."""
+    parameter / gradient buffers and, when a process group is up, one in-place reducer per optimiser group.
+
+    Step controls (all off by default; with none set a step issues exactly the launches it always did):
+
+    - ``clip_max_norm``: clip the gradient of ``model.parameters()`` to this global L2 norm before the main Adam, with
+      ``torch.nn.utils.clip_grad_norm_``'s coefficient ``min(1, max_norm / (norm + 1e-6))``.  The norm is taken of the flat gradient buffer
+      AFTER the reduction over the ranks (every rank sees the same buffer and reaches the same coefficient).  The bottlenecks' aux group is
+      not clipped, as ``clip_grad_norm_(model.parameters(), ...)`` would not touch it in the reference's loop.
+    - ``skip_nonfinite``: a NaN / Inf anywhere in the main gradient skips the step AS A WHOLE -- parameters, both optimisers' moments and
+      both step counters stay as they were; the aux group has the same guard on its own gradient (which can only withhold the aux update:
+      the main one has been applied by then).
+    - ``live_lr``: the learning rates are read from device memory by every step, so ``set_lr`` and direct writes to
+      ``optimizer.param_groups[0]["lr"]`` (torch's schedulers) take effect under ``GraphedTrainer``'s replay too.
+
+    Any of the three puts the step on the control path (``FlatAdam(controls=...)``): on the device nothing is read back and the step stays
+    capturable.  ``step`` then also returns ``grad_norm`` (of the main group, before clipping), ``clip_coef`` and ``skipped``, the running
+    count of steps in which an update was withheld.  The gradient buffers are left unscaled.  Host modules (the gloo tests) get the same
+    semantics from ``clip_grad_norm_`` and an ``isfinite`` test around ``torch.optim.Adam``.  ``Stage2Trainer`` and ``MultiTensorAdam``
+    have no such controls: a user loop on them can call torch's own ``clip_grad_norm_``."""
 
     def __init__(self, model, lr=1e-4, aux_lr=1e-3, lmbda=1e-2, bucket_mb=25.0, overlap=True, force_collectives=False, collective=None,
-                 distortion="mse"):
+                 distortion="mse", clip_max_norm=None, skip_nonfinite=False, live_lr=False):
         if distortion not in Fn.DISTORTIONS:
             raise ValueError(f"Trainer: distortion must be one of {Fn.DISTORTIONS}, got {distortion!r}")
+        if clip_max_norm is not None:
+            import math
+            ok = isinstance(clip_max_norm, (int, float)) and not isinstance(clip_max_norm, bool)
+            if not ok or not math.isfinite(clip_max_norm) or clip_max_norm <= 0:
+                raise ValueError(f"Trainer: clip_max_norm must be a finite positive number (or None: no clipping), got {clip_max_norm!r}")
+            clip_max_norm = float(clip_max_norm)
+        for name, flag in (("skip_nonfinite", skip_nonfinite), ("live_lr", live_lr)):
+            if not isinstance(flag, bool):
+                raise TypeError(f"Trainer: {name} must be a bool, got {type(flag).__name__}")
+        self.clip_max_norm, self.skip_nonfinite, self.live_lr = clip_max_norm, skip_nonfinite, live_lr
+        self.controls = clip_max_norm is not None or skip_nonfinite or live_lr
         # "ms-ssim": loss = lmbda * ((1 - MS-SSIM(x1_hat, x1)) + (1 - MS-SSIM(x2_hat, x2))) + bpp (functional.rd_loss); lmbda has no 255^2
         # factor there, so values of the MSE criterion do not carry over
         self.model, self.lmbda, self.distortion = model, float(lmbda), distortion
@@ -359,8 +423,11 @@ class Trainer:
         self.main_group, self.aux_group = FlatGroup(main), FlatGroup(aux)
         self.on_gpu = self.main_group.flat_p.is_cuda
         if self.on_gpu:
-            self.optimizer = FlatAdam(self.main_group, lr=lr)
-            self.aux_optimizer = FlatAdam(self.aux_group, lr=aux_lr)
+            ctl = {"max_norm": clip_max_norm, "skip_nonfinite": skip_nonfinite, "also_require": None} if self.controls else None
+            self.optimizer = FlatAdam(self.main_group, lr=lr, controls=ctl)
+            # the aux group: no clipping, the same guard, and never applied in a step whose main update was withheld
+            self.aux_optimizer = FlatAdam(self.aux_group, lr=aux_lr,
+                                          controls=dict(ctl, max_norm=None, also_require=self.optimizer) if self.controls else None)
         else:       # host modules (the gloo tests): torch's Adam on the same views
             self.optimizer = torch.optim.Adam(self.main_group.params, lr=lr)
             self.aux_optimizer = torch.optim.Adam(self.aux_group.params, lr=aux_lr)
@@ -370,6 +437,41 @@ class Trainer:
         self.main_reducer = FlatReducer(self.main_group, bucket_mb, overlap=overlap, force=force_collectives, collective=collective)
         self.aux_reducer = FlatReducer(self.aux_group, bucket_mb, overlap=False, force=force_collectives, collective=collective)
         self.world = self.main_reducer.world
+        self._host_stats = {"grad_norm": torch.zeros(()), "clip_coef": torch.ones(()), "skipped": 0, "applied": True}
+
+    def set_lr(self, lr, aux_lr=None):
+        """Set the learning rate of the main optimiser (and of the aux optimiser when ``aux_lr`` is given) for every following step: writes
+        ``param_groups`` and, on the control path, the device control blocks (a device fill, outside any graph)."""
+        self.optimizer.param_groups[0]["lr"] = float(lr)
+        if aux_lr is not None:
+            self.aux_optimizer.param_groups[0]["lr"] = float(aux_lr)
+        self._sync_lr()
+
+    def _sync_lr(self):
+        if self.controls and self.on_gpu and not torch.cuda.is_current_stream_capturing():
+            self.optimizer.sync_lr()
+            self.aux_optimizer.sync_lr()
+
+    def _host_step(self, aux):
+        """The control path for host modules: torch's own clip and an isfinite test around ``torch.optim.Adam.step``."""
+        st = self._host_stats
+        if not aux:
+            params = self.main_group.params
+            if self.clip_max_norm is not None:
+                norm = torch.nn.utils.clip_grad_norm_(params, self.clip_max_norm)
+                coef = torch.clamp(self.clip_max_norm / (norm + 1e-6), max=1.0)
+            else:
+                norm, coef = torch.linalg.vector_norm(self.main_group.flat_g), torch.ones(())
+            st["grad_norm"], st["clip_coef"] = norm.detach(), coef.detach()
+            st["applied"] = not (self.skip_nonfinite and not bool(torch.isfinite(norm)))
+            if st["applied"]:
+                self.optimizer.step()
+            return
+        applied = st["applied"] and not (self.skip_nonfinite and not bool(torch.isfinite(self.aux_group.flat_g).all()))
+        if applied:
+            self.aux_optimizer.step()
+        else:
+            st["skipped"] += 1
 
     def _forward_loss(self, x1, x2, h_matrix, noise):
         out = self.model(x1, x2, h_matrix, noise=noise)
@@ -385,6 +487,7 @@ class Trainer:
         """One iteration in the reference's order: zero both -> forward -> R-D loss backward -> (reduce) -> optimizer.step
         -> aux loss backward -> (reduce) -> aux_optimizer.step.  Returns the loss dict (device scalars, no sync)."""
         self._check_inputs(x1, x2)
+        self._sync_lr()                           # control path: param_groups -> control block (not while capturing: GraphedTrainer does it)
         self.model.train()
         self.main_group.zero_grad()
         self.aux_group.zero_grad()
@@ -414,7 +517,10 @@ class Trainer:
             if wst is not None:
                 torch.cuda.current_stream().wait_stream(wst)    # every weight gradient is in the flat buffer from here on
         self.main_reducer.finish()
-        self.optimizer.step()
+        if self.controls and not self.on_gpu:
+            self._host_step(aux=False)
+        else:
+            self.optimizer.step()                 # control path: norm of the REDUCED gradient -> decision -> update, all on the device
         if self.on_gpu:
             Fn.repack_all()                       # every packed conv weight of the step refreshed (and re-tagged) in ONE launch
         aux = self.model.aux_loss()
@@ -424,11 +530,24 @@ class Trainer:
         finally:
             Fn.grad_slots_active(slots)
         self.aux_reducer.finish()
-        self.aux_optimizer.step()
+        if self.controls and not self.on_gpu:
+            self._host_step(aux=True)
+        else:
+            self.aux_optimizer.step()
         # detached scalars only: a returned loss that still requires grad would keep this step's autograd graph (and its
         # AccumulateGrad nodes, bound to this step's stream) alive into the next one
         crit = {k: v.detach() for k, v in crit.items()}
         crit["aux_loss"] = aux.detach()
+        if self.controls and self.on_gpu:
+            from . import _lib as L
+            # views of the control blocks while a graph is captured (every replay refreshes them), copies otherwise; the count is the aux
+            # block's: it includes the steps the main group withheld
+            own = (lambda t: t) if torch.cuda.is_current_stream_capturing() else torch.clone
+            crit["grad_norm"], crit["clip_coef"] = own(self.optimizer.ctl[L.CTL_GRAD_NORM]), own(self.optimizer.ctl[L.CTL_CLIP_COEF])
+            crit["skipped"] = own(self.aux_optimizer.ctl[L.CTL_SKIPPED])
+        elif self.controls:
+            st = self._host_stats
+            crit["grad_norm"], crit["clip_coef"], crit["skipped"] = st["grad_norm"], st["clip_coef"], torch.tensor(float(st["skipped"]))
         return crit
 
 
@@ -443,7 +562,13 @@ class GraphedTrainer(Trainer):
     gradient), the next call captures zero_grad -> forward -> R-D backward -> reduce -> Adam -> aux backward -> reduce -> aux
     Adam and every later call is a copy of the inputs into the static buffers plus one graph launch.  The quantisation noise
     is drawn inside the graph by the graph-safe Philox generator unless a ``noise`` dict is given at capture time (then it is
-    a static input too).  The returned dict holds the graph's static loss tensors (overwritten by the next call)."""
+    a static input too).  The returned dict holds the graph's static loss tensors (overwritten by the next call).
+
+    The learning rate: WITHOUT step controls (``clip_max_norm`` / ``skip_nonfinite`` / ``live_lr``, see ``Trainer``) the captured Adam
+    launches hold the rate of the capture BY VALUE in their kernel arguments -- a later write to ``optimizer.param_groups[0]["lr"]`` is
+    ignored by every replay, and ``set_lr`` refuses with a ``RuntimeError`` rather than pretend.  WITH any of them (``live_lr=True`` is the
+    one that asks for nothing else) the rate lives in the control block: ``set_lr`` and writes to ``param_groups`` are picked up before
+    every replay by a device fill outside the graph."""
 
     def __init__(self, model, *args, warmup=3, **kw):
         super().__init__(model, *args, **kw)
@@ -460,6 +585,13 @@ class GraphedTrainer(Trainer):
             import warnings
             warnings.warn("GraphedTrainer: the process group's backend is not nccl/RCCL -- its collectives cannot be captured into a HIP "
                           "graph, steps run eagerly")
+
+    def set_lr(self, lr, aux_lr=None):
+        if self.graph is not None and not self.controls:
+            raise RuntimeError("GraphedTrainer.set_lr: the captured step holds its learning rate by value in the kernel arguments of its "
+                               "Adam launches, a replay cannot see a new one -- build the trainer with live_lr=True (the rate is then "
+                               "read from device memory by every replay)")
+        super().set_lr(lr, aux_lr)
 
     def _stage(self, x1, x2, h_matrix, noise):
         if self._in is None:
@@ -480,6 +612,7 @@ class GraphedTrainer(Trainer):
             return super().step(x1, x2, h_matrix, noise=noise)
         self._check_inputs(x1, x2)
         self._stage(x1, x2, h_matrix, noise)
+        self._sync_lr()                           # control path: this call's rate, filled in ahead of the capture / the replay
         self.calls += 1
         if self.graph is None and self.calls <= self.warmup:
             side = torch.cuda.Stream(device=x1.device)
