@@ -23,6 +23,7 @@ STEREO_H_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_st
 CODEC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_codec.h")
 MSSSIM_LOSS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_msssim_loss.h")
 TRAIN_CTL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_train_ctl.h")
+HOMOGRAPHY_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_train.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -274,6 +275,17 @@ _TRAIN_CTL_SIGS = {
 CTL_LR, CTL_MAX_NORM, CTL_SKIP_NONFINITE, CTL_GRAD_NORM, CTL_CLIP_COEF, CTL_APPLIED, CTL_SKIPPED, CTL_FLOATS = 0, 1, 2, 3, 4, 5, 6, 8
 GRAD_NORM_MAX_BLOCKS = 1024
 
+# include/hesic_homography_train.h: the photometric loss of HomographyNet's training, d(warp_perspective)/dM and the DLT adjoint
+# (homography.photometric_loss, functional._WarpMFn, homography.get_perspective_transform / h_matrix_from_delta), in both libraries
+_HOMOGRAPHY_TRAIN_SIGS = {
+    "hesic_photometric_forward": ([_P(WarpDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "hesic_photometric_backward": ([_P(WarpDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "hesic_warp_perspective_backward_m": ([_P(WarpDesc), _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "hesic_perspective_transform_backward": ([_vp, _vp, _vp, _vp, _vp, _i32, _vp], _i32),
+    "hesic_h_from_delta_backward": ([_vp, _vp, _f32, _f32, _i32, _vp, _vp, _i32, _vp], _i32),
+}
+HTRAIN_MAX_BLOCKS, HTRAIN_PARTIAL_WIDTH = 64, 9      # fp64 partials per image of the workspace those entry points take
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -314,6 +326,13 @@ def declared_train_ctl_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_homography_train_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_homography_train.h (used by the homography-training ABI test)."""
+    with open(HOMOGRAPHY_TRAIN_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def _load(h16):
     l = _libs.get(h16)
     if l is None:
@@ -334,7 +353,7 @@ def _load(h16):
         if ver != ABI_VERSION:
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
         for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
-                + list(_TRAIN_CTL_SIGS.items()):
+                + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -1660,9 +1660,137 @@ class _WarpFn(torch.autograd.Function):
         return dsrc.to(sdt), None, None, None, None
 
 
+class _WarpMFn(torch.autograd.Function):
+    """``_WarpFn`` for a matrix that requires grad: the same forward and source gradient (``_WarpFn``'s own code, which a warp by a constant
+    matrix keeps using untouched), plus ``hesic_warp_perspective_backward_m`` on the source kept for it."""
+
+    class _Saved:
+        """The part of an autograd context ``_WarpFn`` uses."""
+
+        def save_for_backward(self, *tensors):
+            self.saved_tensors = tensors
+
+    @staticmethod
+    def forward(ctx, src, M, dsize, align_corners, inverse_map=False):
+        inner = _WarpMFn._Saved()
+        dst = _WarpFn.forward(inner, src, M, dsize, align_corners, inverse_map)
+        ctx.save_for_backward(inner.saved_tensors[0], src.detach())
+        ctx.meta, ctx.m_dtype = inner.meta, M.dtype
+        return dst
+
+    @staticmethod
+    def backward(ctx, g):
+        inner = _WarpMFn._Saved()
+        Mf, src = ctx.saved_tensors
+        inner.saved_tensors, inner.meta = (Mf,), ctx.meta
+        dsrc = _WarpFn.backward(inner, g)[0]
+        (B, Cc, H, W), _, Ho, Wo, ac, inv = ctx.meta
+        g = g.contiguous()
+        ss, ds = src.stride(), g.stride()
+        d = L.WarpDesc(B, Cc, H, W, Ho, Wo, ac, L.dt(src), L.dt(g), inv, ss[0], ss[1], ss[2], ss[3], ds[0], ds[1], ds[2], ds[3])
+        dM = torch.empty((B, 3, 3), dtype=torch.float32, device=g.device)
+        L.call("hesic_warp_perspective_backward_m", C.byref(d), L.ptr(src), L.ptr(g), L.ptr(Mf), L.ptr(_htrain_partials(B, g.device)),
+               L.ptr(dM), L.stream())
+        return dsrc, dM.to(ctx.m_dtype), None, None, None
+
+
+def _htrain_partials(B, device):
+    """The fp64 per-block partials of the image-sized entry points of include/hesic_homography_train.h (written before they are read)."""
+    return torch.empty(B * L.HTRAIN_MAX_BLOCKS * L.HTRAIN_PARTIAL_WIDTH, dtype=torch.float64, device=device)
+
+
+class _PhotometricFn(torch.autograd.Function):
+    """mean |bilinear(img_a, h p) - patch_b| with h = DLT(corners - corners[:,0] -> corners + delta); autograd to ``delta`` only."""
+
+    @staticmethod
+    def forward(ctx, delta, img_a, patch_b, corners, align_corners):
+        L.require_cuda(delta, img_a, patch_b, corners)
+        B, Cc, H, W = img_a.shape
+        Ho, Wo = patch_b.shape[-2:]
+        ss, ds = img_a.stride(), patch_b.stride()
+        d = L.WarpDesc(B, Cc, H, W, Ho, Wo, int(align_corners), L.F32, L.F32, 1, ss[0], ss[1], ss[2], ss[3], ds[0], ds[1], ds[2], ds[3])
+        dl, cn = delta.detach().contiguous(), corners.contiguous()
+        h = torch.empty((B, 9), dtype=torch.float64, device=img_a.device)
+        loss = torch.empty((1,), dtype=torch.float32, device=img_a.device)
+        L.call("hesic_photometric_forward", C.byref(d), L.ptr(img_a), L.ptr(patch_b), L.ptr(cn), L.ptr(dl), L.ptr(h),
+               L.ptr(_htrain_partials(B, img_a.device)), L.ptr(loss), L.stream())
+        ctx.save_for_backward(dl, img_a, patch_b, cn, h)
+        ctx.desc = d
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dl, img_a, patch_b, cn, h = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        d_delta = torch.empty_like(dl)
+        L.call("hesic_photometric_backward", C.byref(ctx.desc), L.ptr(img_a), L.ptr(patch_b), L.ptr(cn), L.ptr(dl), L.ptr(h), L.ptr(g),
+               L.ptr(_htrain_partials(dl.shape[0], dl.device)), L.ptr(d_delta), L.stream())
+        return d_delta, None, None, None, None
+
+
+def photometric_loss(delta, img_a, patch_b, corners, align_corners=True):
+    return _apply(_PhotometricFn, delta, img_a, patch_b, corners, align_corners)
+
+
+class _PerspectiveTransformFn(torch.autograd.Function):
+    """kornia.get_perspective_transform (4-point DLT) with the adjoint kernel as its backward."""
+
+    @staticmethod
+    def forward(ctx, src, dst):
+        L.require_cuda(src, dst)
+        H = torch.empty((src.shape[0], 3, 3), dtype=torch.float32, device=src.device)
+        L.call("hesic_perspective_transform", L.ptr(src), L.ptr(dst), L.ptr(H), src.shape[0], L.stream())
+        ctx.save_for_backward(src, dst)
+        return H
+
+    @staticmethod
+    def backward(ctx, g):
+        src, dst = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        d_src = torch.empty_like(src) if ctx.needs_input_grad[0] else None
+        d_dst = torch.empty_like(dst) if ctx.needs_input_grad[1] else None
+        L.call("hesic_perspective_transform_backward", L.ptr(src), L.ptr(dst), L.ptr(g), L.ptr(d_src), L.ptr(d_dst), src.shape[0], L.stream())
+        return d_src, d_dst
+
+
+def perspective_transform(src, dst):
+    """``src``, ``dst``: (B,4,2) fp32 contiguous."""
+    return _apply(_PerspectiveTransformFn, src, dst)
+
+
+class _HFromDeltaFn(torch.autograd.Function):
+    """hesic_h_from_delta (DLT, 3x3 inverse, h_adjust) with its adjoint with respect to ``delta``."""
+
+    @staticmethod
+    def forward(ctx, corners, delta, ratio_a, ratio_b, subtract_origin):
+        L.require_cuda(corners, delta)
+        H = torch.empty((corners.shape[0], 3, 3), dtype=torch.float32, device=corners.device)
+        L.call("hesic_h_from_delta", L.ptr(corners), L.ptr(delta), ratio_a, ratio_b, subtract_origin, L.ptr(H), corners.shape[0], L.stream())
+        ctx.save_for_backward(corners, delta)
+        ctx.meta = (ratio_a, ratio_b, subtract_origin)
+        return H
+
+    @staticmethod
+    def backward(ctx, g):
+        corners, delta = ctx.saved_tensors
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("h_matrix_from_delta: the gradient goes to delta only")
+        g = g.to(torch.float32).contiguous()
+        d_delta = torch.empty_like(delta)
+        L.call("hesic_h_from_delta_backward", L.ptr(corners), L.ptr(delta), *ctx.meta, L.ptr(g), L.ptr(d_delta), corners.shape[0], L.stream())
+        return None, d_delta, None, None, None
+
+
+def h_from_delta(corners, delta, ratio_a, ratio_b, subtract_origin):
+    """``corners``, ``delta``: (B,4,2) fp32 contiguous."""
+    return _apply(_HFromDeltaFn, corners, delta, float(ratio_a), float(ratio_b), int(subtract_origin))
+
+
 def warp_perspective(src, M, dsize, align_corners=True, inverse_map=False):
     """``inverse_map``: ``M`` already maps destination pixels to source pixels, i.e. this is the warp by ``M^-1``
     (Independent_EN warps view 2 by ``torch.inverse(h_matrix)``, newnet1.py:1290-1291: no 3x3 inversion launches)."""
+    if torch.is_grad_enabled() and M.requires_grad:
+        return _apply(_WarpMFn, src, M, dsize, align_corners, inverse_map)
     return _apply(_WarpFn, src, M, dsize, align_corners, inverse_map)
 
 

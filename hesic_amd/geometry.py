@@ -35,7 +35,8 @@ def warp_convention():
 
 def warp_perspective(src, M, dsize, flags="bilinear", border_mode=None, align_corners=None, inverse_map=False):
     """dst(x', y') = bilinear(src, M^-1 (x', y', 1)), zeros outside.  src (B,C,H,W), M (B,3,3) maps source
-    pixels to destination pixels, dsize = (H_out, W_out).  HIP kernel: csrc/warp.hip."""
+    pixels to destination pixels, dsize = (H_out, W_out).  HIP kernel: csrc/warp.hip.  Differentiable in ``src`` and, when ``M``
+    requires grad, in ``M`` (csrc/homography_train.hip: hesic_warp_perspective_backward_m)."""
     if flags != "bilinear":
         raise NotImplementedError("hesic_amd.warp_perspective: bilinear only")
     if border_mode not in (None, "zeros"):

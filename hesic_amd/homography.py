@@ -21,9 +21,10 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import functional as Fn
+from . import geometry
 from .compressai.models.utils import HipConv2d
 
-__all__ = ["Net", "Block", "Flatten", "max_pool2", "get_perspective_transform", "h_matrix_from_delta", "h_matrix"]
+__all__ = ["Net", "Block", "Flatten", "max_pool2", "get_perspective_transform", "h_matrix_from_delta", "h_matrix", "photometric_loss"]
 
 
 def max_pool2(x):
@@ -120,23 +121,39 @@ class Net(nn.Module):
 
 
 def get_perspective_transform(src, dst):
-    """kornia.get_perspective_transform (B,4,2),(B,4,2) -> (B,3,3) with dst ~ H src."""
+    """kornia.get_perspective_transform (B,4,2),(B,4,2) -> (B,3,3) with dst ~ H src.  Differentiable in both point sets (the DLT adjoint,
+    ``hesic_perspective_transform_backward``)."""
     L.require_cuda(src, dst)
-    src, dst = src.contiguous().float(), dst.contiguous().float()
-    H = torch.empty((src.shape[0], 3, 3), dtype=torch.float32, device=src.device)
-    L.call("hesic_perspective_transform", L.ptr(src), L.ptr(dst), L.ptr(H), src.shape[0], L.stream())
-    return H
+    return Fn.perspective_transform(src.contiguous().float(), dst.contiguous().float())
 
 
 def h_matrix_from_delta(corners, delta, img_h, img_w, pic_size, subtract_origin=True):
     """newtrain1_real.py:113-123: corners0 = corners - corners[:,0]; h = gpt(corners0, corners0 + delta);
-    h_matrix = h_adjust(img_h, img_w, pic_size, pic_size, inverse(h)) -- one kernel, no host round trip."""
+    h_matrix = h_adjust(img_h, img_w, pic_size, pic_size, inverse(h)) -- one kernel, no host round trip.  Differentiable in ``delta``
+    (``hesic_h_from_delta_backward``: h_adjust, the 3x3 inverse and the DLT adjoint in one kernel)."""
     L.require_cuda(corners, delta)
-    corners, delta = corners.contiguous().float(), delta.contiguous().float()
-    H = torch.empty((corners.shape[0], 3, 3), dtype=torch.float32, device=corners.device)
-    L.call("hesic_h_from_delta", L.ptr(corners), L.ptr(delta), float(img_h) / float(pic_size), float(img_w) / float(pic_size),
-           int(subtract_origin), L.ptr(H), corners.shape[0], L.stream())
-    return H
+    return Fn.h_from_delta(corners.contiguous().float(), delta.contiguous().float(), float(img_h) / float(pic_size),
+                           float(img_w) / float(pic_size), subtract_origin)
+
+
+def photometric_loss(delta, img_a, patch_b, corners):
+    """The loss HomographyNet trains on (ywz/mywork/model.py:18-45; udh/udh/QHtrain.py:99)::
+
+        c0 = corners - corners[:, :1];  h = get_perspective_transform(c0, corners + delta)
+        patch_b_hat = warp_perspective(img_a, inverse(h), patch_b.shape[-2:]);  loss = l1_loss(patch_b_hat, patch_b)
+
+    ``patch_b_hat(p) = bilinear(img_a, h p)`` is the warp by ``inverse(h)``: no matrix is inverted.  ``delta``, ``corners`` (B,4,2);
+    ``img_a`` (B,C,H,W) and ``patch_b`` (B,C,h,w) fp32 with any strides.  Returns a 0-d fp32 device tensor with autograd to ``delta`` only,
+    bit-identical from run to run; the sampling convention is ``geometry.DEFAULT_ALIGN_CORNERS``, as in ``geometry.warp_perspective``."""
+    if img_a.requires_grad or patch_b.requires_grad:
+        raise RuntimeError("photometric_loss: the gradient goes to delta only (img_a / patch_b must not require grad)")
+    if img_a.dim() != 4 or patch_b.dim() != 4 or patch_b.shape[:2] != img_a.shape[:2]:
+        raise ValueError(f"photometric_loss: expected img_a (B,C,H,W) and patch_b (B,C,h,w), got {tuple(img_a.shape)}, {tuple(patch_b.shape)}")
+    if tuple(delta.shape) != (img_a.shape[0], 4, 2) or corners.shape != delta.shape:
+        raise ValueError(f"photometric_loss: expected delta and corners (B,4,2), got {tuple(delta.shape)}, {tuple(corners.shape)}")
+    if img_a.dtype != torch.float32 or patch_b.dtype != torch.float32:
+        raise TypeError("photometric_loss: float32 images")
+    return Fn.photometric_loss(delta.float(), img_a, patch_b, corners.float(), geometry.DEFAULT_ALIGN_CORNERS)
 
 
 def h_matrix(net, homo_img1, homo_img2, homo_corners, img_h, img_w, pic_size=256):
