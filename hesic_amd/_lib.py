@@ -24,6 +24,7 @@ CODEC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_codec
 MSSSIM_LOSS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_msssim_loss.h")
 TRAIN_CTL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_train_ctl.h")
 HOMOGRAPHY_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_train.h")
+HOMOGRAPHY_NET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_net.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -286,6 +287,23 @@ _HOMOGRAPHY_TRAIN_SIGS = {
 }
 HTRAIN_MAX_BLOCKS, HTRAIN_PARTIAL_WIDTH = 64, 9      # fp64 partials per image of the workspace those entry points take
 
+# include/hesic_homography_net.h: HomographyNet in training mode -- max-pool backward, flatten + dropout, the small-batch Linear layer over
+# the fp32 master weight (functional._MaxPool2Fn / _FlattenDropoutFn / _LinearFn, homography.Net, train.HomographyTrainer), in both libraries
+_u64 = C.c_uint64
+_HOMOGRAPHY_NET_SIGS = {
+    "hesic_maxpool2_backward": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
+    "hesic_flatten_dropout_forward": ([_vp, _vp, _i32, _i32, _i32, _u32, _f32, _u64, _u32, _u32, _i32, _vp], _i32),
+    "hesic_flatten_dropout_backward": ([_vp, _vp, _i32, _i32, _i32, _u32, _f32, _u64, _u32, _u32, _i32, _vp], _i32),
+    "hesic_linear_forward_ws_bytes": ([_i32, _i32, _i32], C.c_size_t),
+    "hesic_linear_forward": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp], _i32),
+    "hesic_linear_dgrad": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
+    "hesic_linear_wgrad": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
+    "hesic_bias_grad": ([_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], _i32),
+    "hesic_narrow_in_wgrad": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
+}
+LINEAR_MAX_ROWS = 64            # HESIC_LINEAR_MAX_ROWS
+DET_MAX_BLOCKS = 256            # HESIC_DET_MAX_BLOCKS
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -333,6 +351,13 @@ def declared_homography_train_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_homography_net_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_homography_net.h (used by the HomographyNet-training ABI test)."""
+    with open(HOMOGRAPHY_NET_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def _load(h16):
     l = _libs.get(h16)
     if l is None:
@@ -353,7 +378,7 @@ def _load(h16):
         if ver != ABI_VERSION:
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
         for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
-                + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()):
+                + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

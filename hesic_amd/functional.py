@@ -540,12 +540,14 @@ def _out_hw(H, W, k, stride, pad, transposed):
     return f(H), f(W)
 
 
-def _narrow_conv_grads(x, weight, gy, cfg, dims, has_bias, need_dx, need_dw, bias=None):
-    """dx / dw / dbias of an image-side conv (few channels on one side: strided kernels)."""
+def _narrow_conv_grads(x, weight, gy, cfg, dims, has_bias, need_dx, need_dw, bias=None, ydt=None):
+    """dx / dw / dbias of an image-side conv (few channels on one side: strided kernels).  ``ydt``: the storage type the forward gave its
+    output (``_ConvFn`` keeps it: the global compute dtype may have been restored to something else by the time the backward runs)."""
     k, stride, pad, transposed, act, in_abs, tap_mask, packer, mask = cfg
     B, H, W, Cin, Ho, Wo, Cout = dims
     dx = dw = db = None
-    ydt = torch.float32 if _is_narrow(Cout) else (_compute_dtype if _is_narrow(Cin) else x.dtype)
+    if ydt is None:
+        ydt = torch.float32 if _is_narrow(Cout) else (_compute_dtype if _is_narrow(Cin) else x.dtype)
     gy = gy.to(ydt)
     gy = gy.contiguous() if _is_narrow(Cout) else _nhwc(gy)
     w = (weight.detach() if mask is None else weight.detach() * mask).contiguous()
@@ -656,6 +658,63 @@ def _wide_conv_grads(x, weight, gy, cfg, dims, has_bias, need_dx, need_dw, bias=
     return dx, dw, db
 
 
+_det_conv_grads = False
+
+
+class deterministic_conv_grads:
+    """``with deterministic_conv_grads():`` -- convs whose FORWARD runs inside the block take the order-fixed bias gradient
+    (``hesic_bias_grad``) and, for a 3x3 conv with two input channels, the order-fixed weight gradient (``hesic_narrow_in_wgrad``) in their
+    backward, wherever that runs: the usual kernels end those two sums in float atomics, whose last bits change from run to run.
+    ``homography.Net`` uses it with grad mode on (bit-identical steps and resumes); nothing else does, and outside it every conv launches
+    what it always did."""
+
+    def __enter__(self):
+        global _det_conv_grads
+        self._prev, _det_conv_grads = _det_conv_grads, True
+
+    def __exit__(self, *exc):
+        global _det_conv_grads
+        _det_conv_grads = self._prev
+
+
+def _det_target(param, shape, device):
+    """(buffer, slot, accumulate) of an order-fixed gradient under the flat-slot protocol: the slot's buffer (added to once it has been
+    written) or a fresh tensor."""
+    slot = _slot_for(param)
+    if slot is not None:
+        return slot.grad, slot, int(slot.writes > 0)
+    return torch.empty(shape, dtype=torch.float32, device=device), None, 0
+
+
+def _det_conv_param_grads(ctx, x, weight, gy):
+    """The order-fixed part of a conv's parameter gradients: (dw or None, db or None, dw_done, db_done).  ``gy``: NHWC, after the activation's
+    backward."""
+    k, stride, pad, transposed, act, in_abs, tap_mask, packer, mask = ctx.cfg
+    B, H, W, Cin, Ho, Wo, Cout = ctx.dims
+    dw = db = None
+    dw_done = db_done = False
+    if _is_narrow(Cout) or 256 % Cout or not gy.is_contiguous(memory_format=_CL):
+        return dw, db, dw_done, db_done
+    if ctx.has_bias and ctx.needs_input_grad[2]:
+        db, slot, acc = _det_target(ctx.bias, (Cout,), gy.device)
+        ws = torch.empty(L.DET_MAX_BLOCKS * Cout, dtype=torch.float32, device=gy.device)
+        L.call("hesic_bias_grad", L.ptr(gy), L.ptr(db), L.ptr(ws), B * Ho * Wo, Cout, acc, L.dt(gy), L.stream())
+        if slot is not None:
+            _slot_done(slot)
+            db = None
+        db_done = True
+    if (ctx.narrow and ctx.needs_input_grad[1] and Cin == 2 and k == 3 and stride == 1 and pad == 1 and not transposed and mask is None and not in_abs
+            and x.dtype == torch.float32 and x.is_contiguous() and weight.dtype == torch.float32):
+        dw, slot, acc = _det_target(weight, weight.shape, gy.device)
+        ws = torch.empty(L.DET_MAX_BLOCKS * Cout * Cin * 9, dtype=torch.float32, device=gy.device)
+        L.call("hesic_narrow_in_wgrad", L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(ws), B, Cin, H, W, Cout, acc, L.dt(gy), L.stream())
+        if slot is not None:
+            _slot_done(slot)
+            dw = None
+        dw_done = True
+    return dw, db, dw_done, db_done
+
+
 class _ConvFn(torch.autograd.Function):
     """conv()/deconv() of compressai/models/utils.py:104-118 (+ MaskedConv2d, layers.py:21-45)."""
 
@@ -674,7 +733,7 @@ class _ConvFn(torch.autograd.Function):
         narrow = _is_narrow(Cin) or _is_narrow(Cout) or Cin % 32 or Cout % 8 or (transposed and (Ho != H * stride))
         ctx.cfg, ctx.narrow, ctx.dims = cfg, narrow, (B, H, W, Cin, Ho, Wo, Cout)
         if narrow:
-            ydt = torch.float32 if _is_narrow(Cout) else (_compute_dtype if _is_narrow(Cin) else x.dtype)
+            ydt = ctx.ydt = torch.float32 if _is_narrow(Cout) else (_compute_dtype if _is_narrow(Cin) else x.dtype)
             if not _is_narrow(Cin):
                 x = _nhwc(x)
             y = _empty_nhwc(B, Cout, Ho, Wo, ydt, x.device) if not _is_narrow(Cout) else \
@@ -692,7 +751,7 @@ class _ConvFn(torch.autograd.Function):
             wp = packer.get(weight, mask, Cout, Cin, k, k, transposed, False, x.dtype)
             y = _wide_conv(x, wp, bias, B, H, W, Cin, Ho, Wo, Cout, k, stride, pad, transposed, act, in_abs, tap_mask)
         ctx.save_for_backward(x, weight, y if act else None)
-        ctx.has_bias, ctx.bias = bias is not None, bias
+        ctx.has_bias, ctx.bias, ctx.det = bias is not None, bias, _det_conv_grads
         return y
 
     @staticmethod
@@ -707,8 +766,18 @@ class _ConvFn(torch.autograd.Function):
             L.call("hesic_act_backward", L.ptr(y_act), L.ptr(gyc), L.ptr(g2), y_act.numel(), act, L.dt(y_act), L.stream())
             gy = g2
         dx = dw = db = None
-        if ctx.narrow:
-            dx, dw, db = _narrow_conv_grads(x, weight, gy, ctx.cfg, ctx.dims, ctx.has_bias, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.bias)
+        if ctx.det:
+            # order-fixed bias (and first-layer weight) gradients; the usual kernels compute what is left
+            ddw, ddb, dw_done, db_done = _det_conv_param_grads(ctx, x, weight, _nhwc(gy) if gy.dim() == 4 and not _is_narrow(Cout) else gy)
+            has_bias, need_dw = ctx.has_bias and not db_done, ctx.needs_input_grad[1] and not dw_done
+            if ctx.narrow:
+                dx, dw, db = _narrow_conv_grads(x, weight, gy, ctx.cfg, ctx.dims, has_bias, ctx.needs_input_grad[0], need_dw, ctx.bias, ydt=ctx.ydt)
+            else:
+                dx, dw, db = _wide_conv_grads(x, weight, gy, ctx.cfg, ctx.dims, has_bias, ctx.needs_input_grad[0], need_dw, ctx.bias)
+            dw, db = (ddw if dw_done else dw), (ddb if db_done else db)
+        elif ctx.narrow:
+            dx, dw, db = _narrow_conv_grads(x, weight, gy, ctx.cfg, ctx.dims, ctx.has_bias, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.bias,
+                                            ydt=ctx.ydt)
         else:
             dx, dw, db = _wide_conv_grads(x, weight, gy, ctx.cfg, ctx.dims, ctx.has_bias, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.bias)
         if not ctx.has_bias:
@@ -1784,6 +1853,151 @@ class _HFromDeltaFn(torch.autograd.Function):
 def h_from_delta(corners, delta, ratio_a, ratio_b, subtract_origin):
     """``corners``, ``delta``: (B,4,2) fp32 contiguous."""
     return _apply(_HFromDeltaFn, corners, delta, float(ratio_a), float(ratio_b), int(subtract_origin))
+
+
+# ------------------------------------------------------------------------------ HomographyNet in training mode
+# include/hesic_homography_net.h: the pieces of ywz/mywork/model.py:73-101 that are not convolutions, with their gradients.
+class _MaxPool2Fn(torch.autograd.Function):
+    """nn.MaxPool2d(2, 2) on a channels_last map.  The backward recomputes the argmax from the input (saved anyway: it is the ``y_act`` of the
+    conv in front) -- first maximum in the scan order (0,0), (0,1), (1,0), (1,1), torch's rule -- and writes every element of the gradient."""
+
+    @staticmethod
+    def forward(ctx, x):
+        L.require_cuda(x)
+        x = _nhwc(x)
+        B, Cc, H, W = x.shape
+        y = _empty_nhwc(B, Cc, H // 2, W // 2, x.dtype, x.device)
+        L.call("hesic_maxpool2_forward", L.ptr(x), L.ptr(y), B, H, W, Cc, L.dt(x), L.stream())
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        B, Cc, H, W = x.shape
+        gy = _nhwc(gy.to(x.dtype))
+        gx = _empty_nhwc(B, Cc, H, W, x.dtype, x.device)
+        L.call("hesic_maxpool2_backward", L.ptr(x), L.ptr(gy), L.ptr(gx), B, H, W, Cc, L.dt(x), L.stream())
+        return gx
+
+
+def max_pool2(x):
+    return _apply(_MaxPool2Fn, x)
+
+
+def dropout_args(p, seed=0, step=0, site=0):
+    """The by-value arguments of ``hesic_flatten_dropout_*`` for drop probability ``p``: (thr, scale, seed, step, site) with
+    thr = round-half-even(p * 2^32) clamped to [0, 2^32 - 1] and scale = 1.0f / (1.0f - (float)p) as an fp32 value."""
+    import numpy as np
+    p = float(p)
+    if not (0.0 <= p and np.float32(p) < np.float32(1.0)):
+        raise ValueError(f"dropout: p must be in [0, 1) as an fp32 value, got {p}")
+    thr = min(max(int(round(p * 4294967296.0)), 0), 4294967295)
+    scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+    return thr, scale, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, int(site) & 0xFFFFFFFF
+
+
+class _FlattenDropoutFn(torch.autograd.Function):
+    """``x.reshape(B, -1)`` of the reference (NCHW flatten order) of a channels_last map -- or a (B, F) matrix as it is -- with inverted
+    dropout on the way; the mask is a Philox4x32-10 stream of (seed, step, site, logical index) that the backward regenerates."""
+
+    @staticmethod
+    def forward(ctx, x, cfg):
+        L.require_cuda(x)
+        if x.dim() == 4:
+            x = _nhwc(x)
+            B, Cc, HW = x.shape[0], x.shape[1], x.shape[2] * x.shape[3]
+        else:
+            x = x.contiguous()
+            (B, Cc), HW = x.shape, 1
+        y = torch.empty((B, Cc * HW), dtype=x.dtype, device=x.device)
+        L.call("hesic_flatten_dropout_forward", L.ptr(x), L.ptr(y), B, HW, Cc, *cfg, L.dt(x), L.stream())
+        ctx.cfg, ctx.shape, ctx.dtype = cfg, tuple(x.shape), x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        shape = ctx.shape
+        gy = gy.to(ctx.dtype).contiguous()
+        if len(shape) == 4:
+            gx = _empty_nhwc(*shape, ctx.dtype, gy.device)
+            B, Cc, HW = shape[0], shape[1], shape[2] * shape[3]
+        else:
+            gx = torch.empty(shape, dtype=ctx.dtype, device=gy.device)
+            (B, Cc), HW = shape, 1
+        L.call("hesic_flatten_dropout_backward", L.ptr(gy), L.ptr(gx), B, HW, Cc, *ctx.cfg, L.dt(ctx.dtype), L.stream())
+        return gx, None
+
+
+def flatten_dropout(x, cfg):
+    """``cfg`` = ``dropout_args(p, seed, step, site)``; p = 0 is the plain flatten."""
+    return _apply(_FlattenDropoutFn, x, cfg)
+
+
+class _LinearFn(torch.autograd.Function):
+    """act(x W^T + b) for up to ``_lib.LINEAR_MAX_ROWS`` rows over the fp32 master weight in nn.Linear's layout (no packed copy): the
+    weight is streamed once by the forward, once by the data gradient, and its gradient written once, into the flat slot when it has one."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act):
+        L.require_cuda(x, weight)
+        if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1]:
+            raise RuntimeError(f"linear: expected x (B, In) and weight (Out, In), got {tuple(x.shape)}, {tuple(weight.shape)}")
+        if weight.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+            raise TypeError("linear: fp32 weight and bias")
+        x = x.contiguous()
+        B, In = x.shape
+        Out = weight.shape[0]
+        nws = int(L.lib().hesic_linear_forward_ws_bytes(B, In, Out))
+        ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
+        y = torch.empty((B, Out), dtype=x.dtype, device=x.device)
+        L.call("hesic_linear_forward", L.ptr(x), L.ptr(_c(weight)), L.ptr(bias), L.ptr(y), B, In, Out, act, L.dt(x), L.ptr(ws), nws, L.stream())
+        ctx.save_for_backward(x, weight, y if act else None)
+        ctx.act, ctx.has_bias, ctx.bias = act, bias is not None, bias
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, y_act = ctx.saved_tensors
+        B, In = x.shape
+        Out = weight.shape[0]
+        gy = gy.to(x.dtype).contiguous()
+        if ctx.act:
+            g2 = torch.empty_like(y_act)
+            L.call("hesic_act_backward", L.ptr(y_act), L.ptr(gy), L.ptr(g2), y_act.numel(), ctx.act, L.dt(y_act), L.stream())
+            gy = g2
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            L.call("hesic_linear_dgrad", L.ptr(gy), L.ptr(_c(weight)), L.ptr(dx), B, In, Out, L.dt(x), L.stream())
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            # flat gradient slots: an untouched (cleared) slot is written directly, a slot that already holds a gradient is added to.  One
+            # flag serves both outputs: adding into a cleared slot is the same as writing it, and a plain output is zero-filled first.
+            ws_ = _slot_for(weight) if weight.is_contiguous() else None
+            bs_ = _slot_for(ctx.bias) if ctx.has_bias else None
+            accumulate = int((ws_ is not None and ws_.writes > 0) or (bs_ is not None and bs_.writes > 0))
+            fresh = _zeros if accumulate else torch.empty
+            dw = ws_.grad if ws_ is not None else fresh(weight.shape, dtype=torch.float32, device=x.device)
+            db = (bs_.grad if bs_ is not None else fresh((Out,), dtype=torch.float32, device=x.device)) if ctx.has_bias else None
+            L.call("hesic_linear_wgrad", L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(db), B, In, Out, accumulate, L.dt(x), L.stream())
+            if ws_ is not None:
+                _slot_done(ws_)
+                dw = None
+            if bs_ is not None:
+                _slot_done(bs_)
+                db = None
+        return dx, dw, db, None
+
+
+def linear(x, weight, bias, act=L.ACT_NONE, packer=None):
+    """``F.linear`` (+ fused ReLU) on the HIP path.  Up to ``_lib.LINEAR_MAX_ROWS`` rows: the small-batch kernels over the fp32 master weight;
+    more rows: the 1x1 implicit-GEMM conv route (``conv2d`` with its packed weight copies), so that large batches still train."""
+    if x.shape[0] > L.LINEAR_MAX_ROWS:
+        B, In = x.shape
+        y = conv2d(x.reshape(B, In, 1, 1).contiguous(memory_format=_CL), weight.view(weight.shape[0], In, 1, 1), bias, kernel_size=1, stride=1,
+                   padding=0, act=act, packer=packer)
+        return y.reshape(B, -1)
+    return _apply(_LinearFn, x, weight, bias, act)
 
 
 def warp_perspective(src, M, dsize, align_corners=True, inverse_map=False):

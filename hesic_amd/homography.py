@@ -2,14 +2,26 @@
 ``_real`` scripts: ``Net`` of ``ywz/mywork/model.py:73-111`` and ``newtrain1_real.py:113-123``.
 
 Same module tree and state-dict keys as the reference (``cnn.N.layers.{0,2}.{weight,bias}``, ``fc.{2,5}.*``), so a
-``homo_best.pth.tar`` checkpoint loads strictly.  Inference only, like its use on the path (the reference keeps it
-frozen, ``newtrain1_real.py:78``): every layer runs on the HIP kernels of ``libhesic_hip.so`` --
+``homo_best.pth.tar`` checkpoint loads strictly.  Every layer runs on the HIP kernels of ``libhesic_hip.so``.
+
+Inference (eval mode under ``torch.no_grad()``, its use on the path: the reference keeps the net frozen, ``newtrain1_real.py:78``):
 
 * conv3x3 + ReLU: the narrow (Cin = 2) / implicit-GEMM conv kernels with the activation fused;
 * MaxPool2d(2,2): ``hesic_maxpool2_forward`` on the NHWC map;
 * Linear: a 1x1 implicit-GEMM conv over the NHWC-flattened map (the first Linear's columns are permuted once from the
   reference's NCHW flatten order; the low-resolution split-K launch spreads its 32768-deep contraction over the GPU);
 * corner deltas -> h_matrix: ``hesic_h_from_delta`` (4-point DLT, 3x3 inverse and the reference's ``h_adjust``).
+
+With grad mode on, or in training mode (``udh/udh/QHtrain.py:88-102``; ``train.HomographyTrainer``), the same conv blocks are followed by
+the kernels of include/hesic_homography_net.h: the max pools get their backward, the map is flattened into the reference's NCHW order with
+the first Dropout fused in (``hesic_flatten_dropout_*``: the ACTIVATION is permuted, so ``fc.2.weight`` is used -- and its gradient lands --
+in its own layout), and both Linear layers run on the small-batch kernels over the fp32 master weights (``hesic_linear_*``; more than 64
+rows fall back to the 1x1 conv route).  Dropout masks are a Philox4x32-10 stream of ``(seed, step, site, element index)``:
+``set_dropout_state`` / ``dropout_state``; every train-mode forward uses the current ``step`` for both sites and then increments it.
+Up to 64 rows per batch no gradient kernel on this route uses atomics (the conv blocks run under ``functional.deterministic_conv_grads``):
+the same inputs give the same bits in every run.  Larger batches train too, but the conv route of their fc layers sums biases with float
+atomics, so their last bits vary.
+Training mode needs ``dtype=torch.float32``, what the reference trains.
 
 Feature maps are fp32 by default (the deltas are pixel offsets that steer a full-resolution warp); pass
 ``dtype=torch.bfloat16`` for bf16 storage.
@@ -28,13 +40,8 @@ __all__ = ["Net", "Block", "Flatten", "max_pool2", "get_perspective_transform", 
 
 
 def max_pool2(x):
-    """nn.MaxPool2d(2, 2) on a channels_last map (model.py:62-63)."""
-    L.require_cuda(x)
-    x = x.contiguous(memory_format=torch.channels_last)
-    B, C, H, W = x.shape
-    y = torch.empty((B, C, H // 2, W // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    L.call("hesic_maxpool2_forward", L.ptr(x), L.ptr(y), B, H, W, C, L.dt(x), L.stream())
-    return y
+    """nn.MaxPool2d(2, 2) on a channels_last map (model.py:62-63); differentiable (``hesic_maxpool2_backward``)."""
+    return Fn.max_pool2(x)
 
 
 class _HipMaxPool2d(nn.MaxPool2d):
@@ -79,8 +86,9 @@ class Net(nn.Module):
         self.fc = nn.Sequential(Flatten(), nn.Dropout(p=0.5), nn.Linear(128 * self.side * self.side, 1024), nn.ReLU(),
                                 nn.Dropout(p=0.5), nn.Linear(1024, 4 * 2))
         self.dtype = dtype
-        self._fc_pack = [Fn.PackedWeight(), Fn.PackedWeight()]
+        self._fc_pack = [Fn.PackedWeight(), Fn.PackedWeight(), Fn.PackedWeight(), Fn.PackedWeight()]      # inference fc.2 / fc.5; the > 64-row training route
         self._fc1_nhwc = None
+        self._drop_seed, self._drop_step = 0, 0
 
     def _fc1_weight(self):
         """fc.2.weight with its columns moved from NCHW-flatten (c, y, x) to NHWC-flatten (y, x, c) order; cached."""
@@ -92,9 +100,17 @@ class Net(nn.Module):
             self._fc1_nhwc = (tag, wn)
         return self._fc1_nhwc[1]
 
+    def set_dropout_state(self, seed, step=0):
+        """Seed and step counter of the dropout masks (both sites of ``fc``)."""
+        self._drop_seed, self._drop_step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF
+
+    def dropout_state(self):
+        """(seed, step): ``step`` is what the NEXT train-mode forward uses."""
+        return self._drop_seed, self._drop_step
+
     def forward(self, a, b):
         if self.training or torch.is_grad_enabled():
-            raise RuntimeError("hesic_amd HomographyNet is inference-only (call under torch.no_grad() in eval mode)")
+            return self._forward_train(a, b)
         L.require_cuda(a, b)
         x = torch.cat((a, b), dim=1).to(self.dtype)
         prev = Fn.compute_dtype()
@@ -112,6 +128,31 @@ class Net(nn.Module):
             x = Fn._wide_conv(x, wp, self.fc[5].bias, B, 1, 1, w2.shape[1], 1, 1, w2.shape[0], 1, 1, 0, False)
         finally:
             Fn.set_compute_dtype(prev)
+        return x.reshape(-1, 4, 2).float()
+
+    def _forward_train(self, a, b):
+        """Grad mode on (eval: no dropout, differentiable) or training mode (dropout at ``fc[1].p`` / ``fc[4].p``, with or without grad)."""
+        if self.training and self.dtype != torch.float32:
+            raise NotImplementedError("hesic_amd HomographyNet: training mode needs dtype=torch.float32 (what the reference trains); "
+                                      f"this module stores its maps as {self.dtype}")
+        seed, step = self._drop_seed, self._drop_step
+        cfgs = [Fn.dropout_args(self.fc[i].p if self.training else 0.0, seed, step, site) for site, i in enumerate((1, 4))]
+        L.require_cuda(a, b)
+        x = torch.cat((a, b), dim=1).to(self.dtype)
+        prev = Fn.compute_dtype()
+        Fn.set_compute_dtype(self.dtype)
+        try:
+            with Fn.deterministic_conv_grads():      # no float atomics in the conv biases' / first layer's gradients: the same bits in every run
+                #   (up to 64 rows: above that fc takes the conv route, whose bias sums end in atomics)
+                x = self.cnn(x)
+            x = Fn.flatten_dropout(x, cfgs[0])       # (B, 128 side^2) in the reference's flatten order
+            x = Fn.linear(x, self.fc[2].weight, self.fc[2].bias, act=L.ACT_RELU, packer=self._fc_pack[2])
+            x = Fn.flatten_dropout(x, cfgs[1])
+            x = Fn.linear(x, self.fc[5].weight, self.fc[5].bias, packer=self._fc_pack[3])
+        finally:
+            Fn.set_compute_dtype(prev)
+        if self.training:
+            self._drop_step = (step + 1) & 0xFFFFFFFF
         return x.reshape(-1, 4, 2).float()
 
     def get_h(self, a, b, corners):

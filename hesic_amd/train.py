@@ -637,6 +637,104 @@ class GraphedTrainer(Trainer):
         return self._out
 
 
+class HomographyTrainer:
+    """HomographyNet's training loop (udh/udh/QHtrain.py:88-102) on the device: ``delta = net(patch_a, patch_b)`` in training mode,
+    ``homography.photometric_loss``, backward, ``Adam(net.parameters(), lr)`` -- one ``FlatGroup`` over the parameters, so a step is one fill
+    that clears every gradient, the forward and backward kernels (the weight gradients go straight into their flat slots) and one Adam
+    launch.  Nothing is read back to the host, and with up to 64 rows per batch a step -- and a run resumed from ``state_dict()`` -- repeats
+    its bits (larger batches take the fc layers' conv route, whose bias sums end in float atomics).  The compute dtype is fp32 for the duration of a step (``net`` must store fp32 maps).
+
+    ``clip_max_norm``, ``skip_nonfinite`` and ``live_lr`` are ``Trainer``'s step controls (``FlatAdam(controls=...)``): with any of them set
+    ``step`` also returns ``grad_norm`` (before clipping), ``clip_coef`` and ``skipped``.  ``seed`` seeds the dropout masks
+    (``net.set_dropout_state(seed, 0)``).
+
+    The trainer is EAGER: the dropout masks' step counter is a kernel argument passed by value, so a captured HIP graph would replay one
+    mask forever.  ``step`` raises while a stream is capturing."""
+
+    def __init__(self, net, lr=1e-4, seed=0, clip_max_norm=None, skip_nonfinite=False, live_lr=False):
+        if clip_max_norm is not None:
+            import math
+            ok = isinstance(clip_max_norm, (int, float)) and not isinstance(clip_max_norm, bool)
+            if not ok or not math.isfinite(clip_max_norm) or clip_max_norm <= 0:
+                raise ValueError(f"HomographyTrainer: clip_max_norm must be a finite positive number (or None: no clipping), got {clip_max_norm!r}")
+            clip_max_norm = float(clip_max_norm)
+        for name, flag in (("skip_nonfinite", skip_nonfinite), ("live_lr", live_lr)):
+            if not isinstance(flag, bool):
+                raise TypeError(f"HomographyTrainer: {name} must be a bool, got {type(flag).__name__}")
+        if getattr(net, "dtype", torch.float32) != torch.float32:
+            raise NotImplementedError("HomographyTrainer: the net must store fp32 maps (Net(dtype=torch.float32))")
+        self.net = net
+        self.group = FlatGroup(net.parameters())
+        if not self.group.flat_p.is_cuda:
+            raise RuntimeError("HomographyTrainer: the HIP path needs the net on a ROCm device (no CPU fallback)")
+        self.controls = clip_max_norm is not None or skip_nonfinite or live_lr
+        ctl = {"max_norm": clip_max_norm, "skip_nonfinite": skip_nonfinite, "also_require": None} if self.controls else None
+        self.optimizer = FlatAdam(self.group, lr=lr, controls=ctl)
+        net.set_dropout_state(seed, 0)
+
+    def set_lr(self, lr):
+        """The learning rate of every following step (``param_groups`` and, on the control path, the device control block)."""
+        self.optimizer.param_groups[0]["lr"] = float(lr)
+        self.optimizer.sync_lr()
+
+    def step(self, img_a, patch_a, patch_b, corners):
+        """zero the flat gradient -> train-mode forward -> photometric loss -> backward -> one Adam launch.  Returns device scalars."""
+        from . import _lib as L
+        from . import homography
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("HomographyTrainer.step is eager: the dropout step counter is passed to the kernels by value, a captured "
+                               "graph would replay one mask forever")
+        self.optimizer.sync_lr()
+        self.net.train()
+        self.group.zero_grad()
+        prev_dtype = Fn.compute_dtype()
+        Fn.set_compute_dtype(torch.float32)
+        try:
+            pack = Fn.train_pack_cache(True)          # packed conv weights persist across the step, one batched repack below
+            slots = Fn.grad_slots_active(True)        # gradient kernels write straight into the flat buffer (cleared above)
+            try:
+                with torch.enable_grad():
+                    delta = self.net(patch_a, patch_b)
+                    loss = homography.photometric_loss(delta, img_a, patch_b, corners)
+                loss.backward()
+            finally:
+                Fn.grad_slots_active(slots)
+                Fn.train_pack_cache(pack)
+            self.optimizer.step()
+            Fn.repack_all()
+        finally:
+            Fn.set_compute_dtype(prev_dtype)
+        out = {"loss": loss.detach()}
+        if self.controls:
+            ctl = self.optimizer.ctl
+            out["grad_norm"], out["clip_coef"], out["skipped"] = ctl[L.CTL_GRAD_NORM].clone(), ctl[L.CTL_CLIP_COEF].clone(), ctl[L.CTL_SKIPPED].clone()
+        return out
+
+    @torch.no_grad()
+    def evaluate(self, img_a, patch_a, patch_b, corners):
+        """The photometric loss of the net in eval mode (no dropout, no graph); the module's mode is left as it was."""
+        from . import homography
+        was, prev_dtype = self.net.training, Fn.compute_dtype()
+        self.net.eval()
+        Fn.set_compute_dtype(torch.float32)
+        try:
+            return homography.photometric_loss(self.net(patch_a, patch_b), img_a, patch_b, corners)
+        finally:
+            Fn.set_compute_dtype(prev_dtype)
+            self.net.train(was)
+
+    def state_dict(self):
+        return {"state_dict": {k: v.detach().clone() for k, v in self.net.state_dict().items()}, "optimizer": self.optimizer.state_dict(),
+                "dropout": tuple(self.net.dropout_state())}
+
+    def load_state_dict(self, sd):
+        """Parameters (copied into the flat buffer's views), Adam state and the dropout (seed, step): the next step continues bit for bit
+        (batches of up to 64 rows; see ``homography``'s module docstring)."""
+        self.net.load_state_dict(sd["state_dict"])
+        self.optimizer.load_state_dict(sd["optimizer"])
+        self.net.set_dropout_state(*sd["dropout"])
+
+
 def comm_report(reducer):
     """Per-bucket all-reduce timings of the steps run with ``reducer.timing = True`` (synchronises the device): a list of
     {mb, ms, gbps} per launch order, the total, and ``hidden_frac`` = the share of the communication time that lay before the end
