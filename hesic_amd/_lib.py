@@ -25,6 +25,7 @@ MSSSIM_LOSS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic
 TRAIN_CTL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_train_ctl.h")
 HOMOGRAPHY_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_train.h")
 HOMOGRAPHY_NET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_net.h")
+HOMOGRAPHY_PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_prep.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -304,6 +305,14 @@ _HOMOGRAPHY_NET_SIGS = {
 LINEAR_MAX_ROWS = 64            # HESIC_LINEAR_MAX_ROWS
 DET_MAX_BLOCKS = 256            # HESIC_DET_MAX_BLOCKS
 
+# include/hesic_homography_prep.h: a stereo pair on the device -> HomographyNet's inputs in one launch (functional.homonet_prepare,
+# homography.prepare_inputs / h_matrix_from_pair, train.HomographyTrainer.step_pairs), in both libraries
+_HOMOGRAPHY_PREP_SIGS = {
+    "hesic_homonet_prepare": ([_vp, _P(_i64), _vp, _P(_i64), _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+                              _i32),
+}
+PREP_U8, PREP_F32 = 0, 1        # HESIC_PREP_U8 / HESIC_PREP_F32
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -358,6 +367,13 @@ def declared_homography_net_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_homography_prep_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_homography_prep.h (used by the HomographyNet input-preparation ABI test)."""
+    with open(HOMOGRAPHY_PREP_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def _load(h16):
     l = _libs.get(h16)
     if l is None:
@@ -378,7 +394,8 @@ def _load(h16):
         if ver != ABI_VERSION:
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
         for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
-                + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()):
+                + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()) \
+                + list(_HOMOGRAPHY_PREP_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -1,6 +1,6 @@
 """``python -m hesic_amd.codec``: code a stereo folder to ``.hsd`` blobs and back, on the GPU.
 
-    encode ROOT OUT [--split test] [--batch 8] [--checkpoint PATH] [--model hesic|joint]
+    encode ROOT OUT [--split test] [--batch 8] [--checkpoint PATH] [--model hesic|joint] [--homography sidecar|net] [--homography-checkpoint PATH]
                                                                       ROOT/<split>/{left,right}/ + ROOT/<split>/H/<stem>.npy
                                                                       (the sidecars ``python -m hesic_amd.stereo_h`` writes)
                                                                       -> OUT/<stem>.hsd + OUT/<stem>.json, one JSON line of totals
@@ -12,6 +12,11 @@ the blob names its kind, and a decoder of the other model refuses it).  The homo
 in the reference's flow: it travels in ``<stem>.json`` next to the blob, with the original image size (images are zero-padded to
 multiples of 64 for coding and cropped back).  Pairs without a sidecar are skipped and counted.  Without ``--checkpoint`` the
 deterministic synthetic weights are used (both sides must use the same weights and the same ``--dtype``).
+
+``--homography net`` takes the matrix from HomographyNet instead, as the reference's final configuration does for every pair
+(``homography.h_matrix_from_pair``: the centre window of the unpadded images, on the device): no sidecars are needed and no pair is skipped.
+``--homography-checkpoint`` names the net's weights (a ``homo_best.pth.tar`` or what ``python -m hesic_amd.homography_train`` writes); without
+it the deterministic synthetic weights.  The decoder reads the matrix from ``<stem>.json`` either way.
 """
 from __future__ import annotations
 
@@ -45,6 +50,17 @@ def load_model(checkpoint=None, dtype=torch.float16, device="cuda", model="hesic
     return net
 
 
+def load_homography_net(checkpoint=None, device="cuda"):
+    """HomographyNet for ``encode --homography net``: fp32 maps, eval mode; the checkpoint's weights or the deterministic synthetic ones."""
+    from . import homography, synthetic
+    hnet = homography.Net()
+    if checkpoint:
+        homography.load_checkpoint(hnet, checkpoint)
+    else:
+        synthetic.fill_homography_state_dict_(hnet.state_dict())
+    return hnet.to(device).eval()
+
+
 def _pairs(root, split):
     """[(stem, left path, right path, H path or None)] of ROOT/<split>, in sorted order."""
     d = Path(root) / split
@@ -71,14 +87,16 @@ def quantise(x):
     return (x.float().clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
 
 
-def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, log=print):
+def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, log=print, homography_net=None):
+    """``homography_net=None``: the matrices come from the sidecars; a ``homography.Net``: from the net, for every pair."""
+    from . import homography
     from .models import pad_to_multiple
     from .stereo_h import _image_size
     out = Path(out)
     out.mkdir(parents=True, exist_ok=True)
     groups, skipped = {}, 0
     for stem, lf, rf, hp in _pairs(root, split):
-        if hp is None:
+        if hp is None and homography_net is None:
             skipped += 1
             continue
         sa, sb = _image_size(lf), _image_size(rf)
@@ -91,8 +109,12 @@ def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, 
             chunk = items[c0:c0 + batch]
             x1 = pad_to_multiple(torch.stack([read_image(lf) for _, lf, _, _ in chunk])).cuda()
             x2 = pad_to_multiple(torch.stack([read_image(rf) for _, _, rf, _ in chunk])).cuda()
-            Hs = [np.load(hp).astype(np.float64).reshape(3, 3) for _, _, _, hp in chunk]
-            Hm = torch.from_numpy(np.stack(Hs)).float().cuda()
+            if homography_net is not None:             # on the images as they are (a strided view): the padding is not part of the frame
+                Hm = homography.h_matrix_from_pair(homography_net, x1[..., :h, :w], x2[..., :h, :w], "centre")
+                Hs = list(Hm.double().cpu().numpy())
+            else:
+                Hs = [np.load(hp).astype(np.float64).reshape(3, 3) for _, _, _, hp in chunk]
+                Hm = torch.from_numpy(np.stack(Hs)).float().cuda()
             enc = net.compress_batch(x1, x2, Hm, channels_per_stream=channels_per_stream)
             for (stem, _, _, _), blob, Hn in zip(chunk, enc["blobs"], Hs):
                 (out / (stem + ".hsd")).write_bytes(blob)
@@ -144,6 +166,9 @@ def main(argv=None):
     e.add_argument("out")
     e.add_argument("--split", default="test")
     e.add_argument("--channels-per-stream", type=int, default=8)
+    e.add_argument("--homography", choices=("sidecar", "net"), default="sidecar",
+                   help="sidecar: ROOT/<split>/H/<stem>.npy (default); net: HomographyNet on every pair (no sidecars needed)")
+    e.add_argument("--homography-checkpoint", default=None, help="HomographyNet weights for --homography net (default: synthetic weights)")
     d = sub.add_parser("decode", help="OUT/<stem>.hsd -> RECON/<stem>_{left,right}.png")
     d.add_argument("out")
     d.add_argument("recon")
@@ -160,7 +185,10 @@ def main(argv=None):
         p.error("--batch must be positive")
     net = load_model(a.checkpoint, _DTYPES[a.dtype], model=a.model)
     if a.cmd == "encode":
-        encode_folder(net, a.root, a.out, a.split, a.batch, a.channels_per_stream)
+        if a.homography_checkpoint and a.homography != "net":
+            p.error("--homography-checkpoint needs --homography net")
+        hnet = load_homography_net(a.homography_checkpoint) if a.homography == "net" else None
+        encode_folder(net, a.root, a.out, a.split, a.batch, a.channels_per_stream, homography_net=hnet)
     else:
         decode_folder(net, a.out, a.recon, a.batch)
     return 0

@@ -1,0 +1,128 @@
+// HomographyNet's inputs from a stereo pair on the device (include/hesic_homography_prep.h): resize to S x S, quantise, normalise, average to
+// grey, cut the P x P window and write its corners -- both views in ONE launch.  It is the loader's host path (compressai.datasets:
+// _resize_bilinear + ImageFolder._homonet_inputs) written as an explicit fp32 sequence, so the two agree to the last grey level.
+//
+// Thread map: one grey element per thread, x fastest (a wave writes 256 contiguous bytes of grey and, inside the window, of the patch);
+// blockIdx.y = item, blockIdx.z = view.  The four taps of a thread are two pairs of neighbouring columns on two rows: when shrinking by k
+// a wave's reads cover 64 k consecutive columns per row and channel, every fetched line is used (by this wave or the next row's).  No LDS,
+// no atomics; memory- and latency-bound (12 gathered loads, ~9 IEEE divisions, 4 B + the window's share stored per thread).
+#include "common.h"
+#include "../../include/hesic_homography_prep.h"
+
+namespace {
+
+constexpr int PREP_THREADS = 256;
+
+struct PrepView {
+    const void* x;
+    int64_t sb, sc, sy, sx;
+    float* grey;
+    float* patch;
+};
+
+struct PrepAxis {
+    int i0, i1;
+    float l0, l1;
+};
+
+// every product, sum and difference below is an fp32 operation of its own: a fused multiply-add would move values that sit at k + 0.5
+// before the rounding to a level, and the host path (and the numpy restatement the tests hold this to) does not fuse
+__device__ __forceinline__ PrepAxis prep_axis(int d, int n, float scale) {
+#pragma clang fp contract(off)
+    float s = scale * ((float)d + 0.5f) - 0.5f;
+    s = s < 0.f ? 0.f : s;
+    PrepAxis a;
+    a.i0 = min((int)s, n - 1);
+    a.i1 = min(a.i0 + 1, n - 1);
+    a.l1 = s - (float)a.i0;
+    a.l0 = 1.f - a.l1;
+    return a;
+}
+
+template <bool F32> __device__ __forceinline__ float prep_level(const void* x, int64_t off) {
+    if (F32) {
+#pragma clang fp contract(off)
+        const float q = rintf(255.f * ((const float*)x)[off]);
+        return fminf(fmaxf(q, 0.f), 255.f);
+    }
+    return (float)((const uint8_t*)x)[off];
+}
+
+__device__ __forceinline__ float prep_resample(float a, float b, float c, float d, const PrepAxis& ax, const PrepAxis& ay) {
+#pragma clang fp contract(off)
+    const float top = ax.l0 * a + ax.l1 * b;
+    const float bot = ax.l0 * c + ax.l1 * d;
+    const float v = ay.l0 * top + ay.l1 * bot;
+    return fminf(fmaxf(rintf(v), 0.f), 255.f);          // rintf: ties to even
+}
+
+__device__ __forceinline__ float prep_normalise(float r, float mean, float std) {
+#pragma clang fp contract(off)
+    return __fdiv_rn(__fdiv_rn(r, 255.f) - mean, std);
+}
+
+template <bool F32>
+__global__ __launch_bounds__(PREP_THREADS) void homonet_prepare_kernel(const PrepView v1, const PrepView v2, const int32_t* __restrict__ xy,
+                                                                       float* __restrict__ corners, int H, int W, int S, int P, float scale_y,
+                                                                       float scale_x, float mean, float std) {
+    const int b = blockIdx.y;
+    const PrepView v = blockIdx.z == 0 ? v1 : v2;
+    const int wx = xy[2 * b], wy = xy[2 * b + 1];
+    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x < 8) {
+        // [[x, y], [x+P, y], [x+P, y+P], [x, y+P]]: corner k = threadIdx.x >> 1 adds P to x for k = 1, 2 and to y for k = 2, 3
+        const int k = threadIdx.x >> 1;
+        const int val = (threadIdx.x & 1) ? wy + (k >= 2 ? P : 0) : wx + ((k == 1 || k == 2) ? P : 0);
+        corners[(int64_t)b * 8 + threadIdx.x] = (float)val;
+    }
+    const int idx = blockIdx.x * PREP_THREADS + threadIdx.x;
+    if (idx >= S * S) return;
+    const int y = idx / S, x = idx - y * S;
+    const PrepAxis ay = prep_axis(y, H, scale_y), ax = prep_axis(x, W, scale_x);
+    const int64_t base = (int64_t)b * v.sb;
+    const int64_t r0 = base + (int64_t)ay.i0 * v.sy, r1 = base + (int64_t)ay.i1 * v.sy;
+    const int64_t c0 = (int64_t)ax.i0 * v.sx, c1 = (int64_t)ax.i1 * v.sx;
+    float n[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int64_t co = (int64_t)c * v.sc;
+        const float ta = prep_level<F32>(v.x, r0 + c0 + co), tb = prep_level<F32>(v.x, r0 + c1 + co);
+        const float tc = prep_level<F32>(v.x, r1 + c0 + co), td = prep_level<F32>(v.x, r1 + c1 + co);
+        n[c] = prep_normalise(prep_resample(ta, tb, tc, td, ax, ay), mean, std);
+    }
+    float g;
+    {
+#pragma clang fp contract(off)
+        g = __fdiv_rn((n[0] + n[1]) + n[2], 3.f);
+    }
+    v.grey[((int64_t)b * S + y) * S + x] = g;
+    // unsigned compares: inside the window AND inside the patch buffer whatever xy holds
+    const unsigned px = (unsigned)(x - wx), py = (unsigned)(y - wy);
+    if (px < (unsigned)P && py < (unsigned)P) v.patch[((int64_t)b * P + py) * P + px] = g;
+}
+
+}  // namespace
+
+extern "C" int hesic_homonet_prepare(const void* x1, const int64_t* xs1, const void* x2, const int64_t* xs2, const int32_t* xy, int B, int H, int W,
+                                     int S, int P, float mean, float std, int dtype, float* grey1, float* grey2, float* patch1, float* patch2,
+                                     float* corners, void* stream) {
+    HESIC_CHECK_ARG(x1 && x2 && xs1 && xs2 && xy && grey1 && grey2 && patch1 && patch2 && corners, "homonet_prepare: null pointer");
+    HESIC_CHECK_ARG(dtype == HESIC_PREP_U8 || dtype == HESIC_PREP_F32, "homonet_prepare: dtype %d (HESIC_PREP_U8 or HESIC_PREP_F32)", dtype);
+    HESIC_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "homonet_prepare: bad shape B=%d H=%d W=%d", B, H, W);
+    HESIC_CHECK_ARG(S >= 1 && S <= 16384 && P >= 1 && P <= S, "homonet_prepare: need 1 <= P <= S <= 16384, got S=%d P=%d", S, P);
+    HESIC_CHECK_ARG(std == std && mean == mean && std != 0.f, "homonet_prepare: std must be non-zero, mean and std not NaN");
+    for (int i = 0; i < 4; ++i) HESIC_CHECK_ARG(xs1[i] >= 0 && xs2[i] >= 0, "homonet_prepare: negative stride");
+    const int align = dtype == HESIC_PREP_F32 ? 3 : 0;
+    HESIC_CHECK_ARG((((uintptr_t)x1 | (uintptr_t)x2) & align) == 0 && (((uintptr_t)xy | (uintptr_t)grey1 | (uintptr_t)grey2 | (uintptr_t)patch1 |
+                                                                       (uintptr_t)patch2 | (uintptr_t)corners) & 3) == 0,
+                    "homonet_prepare: misaligned pointer");
+    const PrepView v1{x1, xs1[0], xs1[1], xs1[2], xs1[3], grey1, patch1}, v2{x2, xs2[0], xs2[1], xs2[2], xs2[3], grey2, patch2};
+    const float scale_y = (float)H / (float)S, scale_x = (float)W / (float)S;
+    const dim3 grid((unsigned)cdiv64((int64_t)S * S, PREP_THREADS), (unsigned)B, 2);
+    if (dtype == HESIC_PREP_F32)
+        hipLaunchKernelGGL(homonet_prepare_kernel<true>, grid, dim3(PREP_THREADS), 0, (hipStream_t)stream, v1, v2, xy, corners, H, W, S, P, scale_y,
+                           scale_x, mean, std);
+    else
+        hipLaunchKernelGGL(homonet_prepare_kernel<false>, grid, dim3(PREP_THREADS), 0, (hipStream_t)stream, v1, v2, xy, corners, H, W, S, P, scale_y,
+                           scale_x, mean, std);
+    HESIC_LAUNCH_RETURN("homonet_prepare");
+}

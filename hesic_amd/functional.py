@@ -1855,6 +1855,34 @@ def h_from_delta(corners, delta, ratio_a, ratio_b, subtract_origin):
     return _apply(_HFromDeltaFn, corners, delta, float(ratio_a), float(ratio_b), int(subtract_origin))
 
 
+def homonet_prepare(x1, x2, xy, pic_size, patch_size, mean, std, out=None):
+    """``hesic_homonet_prepare`` (include/hesic_homography_prep.h): ``x1``, ``x2`` (B,3,H,W) uint8 or float32 in [0, 1] with any non-negative
+    strides, ``xy`` (B,2) int32 window origins on the device (the CALLER checks 0 <= x, y <= pic_size - patch_size) ->
+    ``(grey1, grey2, patch1, patch2, corners)``, fp32, one launch.  ``out``: five preallocated dense fp32 tensors of those shapes."""
+    L.require_cuda(x1, x2, xy)
+    if x1.dim() != 4 or x1.shape[1] != 3 or x1.shape != x2.shape:
+        raise ValueError(f"homonet_prepare: expected two (B,3,H,W) tensors of one shape, got {tuple(x1.shape)}, {tuple(x2.shape)}")
+    if x1.dtype != x2.dtype:
+        raise TypeError(f"homonet_prepare: the two views differ in dtype ({x1.dtype} vs {x2.dtype})")
+    if x1.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"homonet_prepare: uint8 or float32 images, got {x1.dtype}")
+    B, _, H, W = x1.shape
+    S, P = int(pic_size), int(patch_size)
+    if xy.dtype != torch.int32 or tuple(xy.shape) != (B, 2) or not xy.is_contiguous():
+        raise ValueError(f"homonet_prepare: xy must be a contiguous int32 (B,2) tensor, got {xy.dtype} {tuple(xy.shape)}")
+    shapes = [(B, 1, S, S), (B, 1, S, S), (B, 1, P, P), (B, 1, P, P), (B, 4, 2)]
+    if out is None:
+        out = [torch.empty(s, dtype=torch.float32, device=x1.device) for s in shapes]
+    else:
+        L.require_cuda(*out)
+        for t, s in zip(out, shapes):
+            if tuple(t.shape) != s or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"homonet_prepare: out must be dense fp32 tensors of shapes {shapes}")
+    L.call("hesic_homonet_prepare", L.ptr(x1), (C.c_int64 * 4)(*x1.stride()), L.ptr(x2), (C.c_int64 * 4)(*x2.stride()), L.ptr(xy), B, H, W, S, P,
+           float(mean), float(std), L.PREP_F32 if x1.dtype == torch.float32 else L.PREP_U8, *[L.ptr(t) for t in out], L.stream())
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------ HomographyNet in training mode
 # include/hesic_homography_net.h: the pieces of ywz/mywork/model.py:73-101 that are not convolutions, with their gradients.
 class _MaxPool2Fn(torch.autograd.Function):

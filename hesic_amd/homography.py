@@ -23,6 +23,10 @@ the same inputs give the same bits in every run.  Larger batches train too, but 
 atomics, so their last bits vary.
 Training mode needs ``dtype=torch.float32``, what the reference trains.
 
+Image pairs that are already on the device become the net's inputs in one launch (``prepare_inputs``, include/hesic_homography_prep.h:
+the loader's ``ImageFolder._homonet_inputs`` -- resize to 256 x 256, quantise, normalise, grey, one 128 x 128 window with its corners -- for
+both views of a batch); ``h_matrix_from_pair`` goes from such a batch to its ``h_matrix``.
+
 Feature maps are fp32 by default (the deltas are pixel offsets that steer a full-resolution warp); pass
 ``dtype=torch.bfloat16`` for bf16 storage.
 """
@@ -36,7 +40,8 @@ from . import functional as Fn
 from . import geometry
 from .compressai.models.utils import HipConv2d
 
-__all__ = ["Net", "Block", "Flatten", "max_pool2", "get_perspective_transform", "h_matrix_from_delta", "h_matrix", "photometric_loss"]
+__all__ = ["Net", "Block", "Flatten", "max_pool2", "get_perspective_transform", "h_matrix_from_delta", "h_matrix", "photometric_loss",
+           "window_origins", "prepare_inputs", "h_matrix_from_pair", "load_checkpoint", "checkpoint_state_dict", "net_state_dict"]
 
 
 def max_pool2(x):
@@ -202,3 +207,98 @@ def h_matrix(net, homo_img1, homo_img2, homo_corners, img_h, img_w, pic_size=256
     with torch.no_grad():
         delta = net(homo_img1, homo_img2)
         return h_matrix_from_delta(homo_corners, delta, img_h, img_w, pic_size)
+
+
+def window_origins(batch, xy=None, pic_size=256, patch_size=128, rho=45, rng=None):
+    """The (x, y) window origins of ``batch`` items as a list of pairs.  ``xy=None``: the loader's rule and draw order
+    (``ImageFolder._homonet_inputs``) -- per item ``x`` then ``y`` from ``randint(rho, S - rho - P)`` when ``S - rho - P >= rho``, else 0, 0 --
+    from ``rng`` (a ``random.Random``; default: Python's global ``random``, so a seeded run reproduces the loader's windows).
+    ``xy="centre"``: ``(S - P) // 2`` for both.  A (B, 2) integer tensor or sequence is used as given.  Range violations raise ValueError."""
+    import random
+    S, P, rho, B = int(pic_size), int(patch_size), int(rho), int(batch)
+    if not 1 <= P <= S:
+        raise ValueError(f"prepare_inputs: need 1 <= patch_size <= pic_size, got patch_size={P}, pic_size={S}")
+    if isinstance(xy, str):
+        if xy != "centre":
+            raise ValueError(f"prepare_inputs: xy is None, 'centre' or (B,2) integers, got {xy!r}")
+        return [((S - P) // 2, (S - P) // 2)] * B
+    if xy is None:
+        if rho < 0:
+            raise ValueError(f"prepare_inputs: rho must not be negative, got {rho}")
+        r = rng if rng is not None else random
+        out = []
+        for _ in range(B):
+            if S - rho - P >= rho:
+                x = r.randint(rho, S - rho - P)
+                y = r.randint(rho, S - rho - P)
+            else:
+                x = y = 0
+            out.append((x, y))
+        return out
+    if torch.is_tensor(xy):
+        if xy.is_floating_point() or xy.is_complex() or xy.dtype == torch.bool:
+            raise TypeError(f"prepare_inputs: xy must hold integers, got {xy.dtype}")
+        vals = xy.detach().cpu().tolist()
+    else:
+        vals = [list(v) if hasattr(v, "__len__") else v for v in xy]
+    if len(vals) != B or any(not hasattr(v, "__len__") or len(v) != 2 for v in vals):
+        raise ValueError(f"prepare_inputs: xy must have shape ({B}, 2)")
+    out = []
+    for x, y in vals:
+        if int(x) != x or int(y) != y:
+            raise TypeError(f"prepare_inputs: xy must hold integers, got ({x!r}, {y!r})")
+        if not (0 <= x <= S - P and 0 <= y <= S - P):
+            raise ValueError(f"prepare_inputs: window origin ({x}, {y}) outside [0, {S - P}] (pic_size {S}, patch_size {P})")
+        out.append((int(x), int(y)))
+    return out
+
+
+def prepare_inputs(x1, x2, xy=None, pic_size=256, patch_size=128, rho=45, rng=None):
+    """HomographyNet's inputs of a stereo batch on the device, in one launch (``hesic_homonet_prepare``): what the loader's
+    ``ImageFolder._homonet_inputs`` computes per item on the host.  ``x1``, ``x2``: (B,3,H,W) of one shape and dtype, uint8 or float32 in
+    [0, 1], any non-negative strides.  ``xy``: see ``window_origins``.  Returns ``(grey1, grey2, patch1, patch2, corners)``: the normalised
+    grey frames (B,1,S,S), their windows (B,1,P,P) and the windows' corners (B,4,2), all fp32."""
+    from .compressai.datasets import MEAN, STD
+    for t in (x1, x2):
+        if not torch.is_tensor(t):
+            raise TypeError(f"prepare_inputs: tensors expected, got {type(t).__name__}")
+    if x1.dim() != 4 or x1.shape[1] != 3 or x1.shape != x2.shape:
+        raise ValueError(f"prepare_inputs: expected two (B,3,H,W) tensors of one shape, got {tuple(x1.shape)}, {tuple(x2.shape)}")
+    if x1.dtype != x2.dtype or x1.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"prepare_inputs: both views uint8 or both float32, got {x1.dtype}, {x2.dtype}")
+    origins = window_origins(x1.shape[0], xy, pic_size, patch_size, rho, rng)          # host checks come before any launch
+    L.require_cuda(x1, x2)
+    xy_dev = torch.tensor(origins, dtype=torch.int32).reshape(-1, 2).to(x1.device, non_blocking=True)
+    return Fn.homonet_prepare(x1, x2, xy_dev, int(pic_size), int(patch_size), float(MEAN), float(STD))
+
+
+def h_matrix_from_pair(net, x1, x2, xy="centre", pic_size=256):
+    """(B,3,3) ``h_matrix`` of a stereo batch on the device, for the images' own size: ``prepare_inputs`` (window side ``net.side * 8``),
+    then ``h_matrix`` -- the `_real` scripts' derivation for every pair (newtrain1_real.py:108-126), under ``no_grad``."""
+    with torch.no_grad():
+        _, _, p1, p2, corners = prepare_inputs(x1, x2, xy, pic_size, net.side * 8)
+        return h_matrix(net, p1, p2, corners, x1.shape[-2], x1.shape[-1], pic_size)
+
+
+_CKPT_PREFIX = "model."
+
+
+def checkpoint_state_dict(net):
+    """``net.state_dict()`` on the host under the reference's key names: ``HomographyModel`` wraps ``Net`` as ``.model``, so a
+    ``homo_best.pth.tar`` names every tensor ``model.<key>``."""
+    return {_CKPT_PREFIX + k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
+
+
+def net_state_dict(sd):
+    """A checkpoint's state dict under ``Net``'s own key names: the ``model.`` prefix is dropped where every key carries it."""
+    if sd and all(k.startswith(_CKPT_PREFIX) for k in sd):
+        return {k[len(_CKPT_PREFIX):]: v for k, v in sd.items()}
+    return dict(sd)
+
+
+def load_checkpoint(net, path):
+    """Load a HomographyNet checkpoint strictly: a file with a ``state_dict`` entry (what ``python -m hesic_amd.homography_train`` and the
+    reference's QHtrain write) or a bare state dict, its keys with or without the ``model.`` prefix.  Returns the loaded file's dict."""
+    ckpt = torch.load(path, map_location="cpu")
+    net.load_state_dict(net_state_dict(ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt), strict=True)
+    return ckpt

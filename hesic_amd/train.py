@@ -723,6 +723,20 @@ class HomographyTrainer:
             Fn.set_compute_dtype(prev_dtype)
             self.net.train(was)
 
+    def _prepare_pairs(self, x1, x2, xy, pic_size, rho, rng):
+        from . import homography
+        grey1, _, patch1, patch2, corners = homography.prepare_inputs(x1, x2, xy, pic_size, self.net.side * 8, rho, rng)
+        return grey1, patch1, patch2, corners
+
+    def step_pairs(self, x1, x2, xy=None, pic_size=256, rho=45, rng=None):
+        """``step`` on a stereo batch that is on the device: ``homography.prepare_inputs`` (one launch; the window side is the net's,
+        ``xy=None`` draws the loader's random windows) gives QHtrain's ``img_a, patch_a, patch_b, corners``."""
+        return self.step(*self._prepare_pairs(x1, x2, xy, pic_size, rho, rng))
+
+    def evaluate_pairs(self, x1, x2, xy=None, pic_size=256, rho=45, rng=None):
+        """``evaluate`` on a stereo batch that is on the device (see ``step_pairs``)."""
+        return self.evaluate(*self._prepare_pairs(x1, x2, xy, pic_size, rho, rng))
+
     def state_dict(self):
         return {"state_dict": {k: v.detach().clone() for k, v in self.net.state_dict().items()}, "optimizer": self.optimizer.state_dict(),
                 "dropout": tuple(self.net.dropout_state())}
