@@ -2147,22 +2147,42 @@ extern "C" int hesic_conv2d_set_phase_fusion(int mode) {
     if (mode < 0 || mode > 2) { hesic_set_error("conv2d_set_phase_fusion: mode must be 0 (off), 1 (auto) or 2 (always)"); return -1; }
     return g_phase4_mode.exchange(mode);
 }
-static thread_local int* g_plan_out = nullptr;
-static thread_local const void* g_gdn_gamma = nullptr;   // set by hesic_conv2d_gdn_forward around its call to the launcher
-static thread_local const float* g_gdn_beta = nullptr;
-static thread_local int g_gdn_mode = 0;
-static thread_local void* g_y_pre = nullptr;              // set by hesic_conv2d_gdn_forward_train
-static thread_local float* g_ws = nullptr;               // set by hesic_conv2d_forward_ws: split-K workspace
-static thread_local size_t g_ws_bytes = 0;
-static thread_local size_t* g_ws_need = nullptr;         // set by hesic_conv2d_ws_bytes: only report the workspace size
-static thread_local int g_groups = 1, g_x_group_step = 0, g_act2 = 0, g_act_split = 0;   // set by hesic_conv2d_forward_grouped
-static thread_local float* g_y32 = nullptr;              // set by hesic_conv2d_forward_f32out: fp32 copy of the output
-static thread_local int g_y32_ps = 0, g_y32_co = 0;
-static thread_local int g_hilo = 0;                      // set by hesic_conv2d_forward_hilo: bf16x3 operands
-static thread_local const void* g_gdn_gamma_lo = nullptr;
-static thread_local int g_y_hilo = 0, g_y_abs = 0;
 static thread_local float g_hilo_acc_scale = 1.f;      // hesic_conv2d_hilo_set_acc_scale: consumed by the next hi/lo launch of this thread
-static thread_local float g_hilo_acc_scale_active = 1.f;      // ... the value that launch runs with (set and cleared by conv2d_forward_hilo_n)
+
+namespace {
+// What an entry point asks of the implicit-GEMM launch beyond the descriptor.  The defaults are hesic_conv2d_forward's.
+struct IgemmOpts {
+    int gdn_mode = 0;                        // fused epilogue: 0 none, 1 GDN, 2 IGDN, 3 / 4 the same with hi/lo squares and gamma' (y = [hi | lo])
+    const void* gdn_gamma = nullptr;
+    const void* gdn_gamma_lo = nullptr;
+    const float* gdn_beta = nullptr;
+    void* y_pre = nullptr;                   // hesic_conv2d_gdn_forward_train: the conv output in front of the GDN
+    float* ws = nullptr;                     // split-K workspace
+    size_t ws_bytes = 0;
+    bool assume_ws = false;                  // the size queries: plan as if a workspace of any size were there
+    int groups = 1, x_group_step = 0, act2 = 0, act_split = 0;      // hesic_conv2d_forward_grouped
+    bool f32out = false;                     // an fp32 copy of the output is written (to y32; the size query has no buffer to name)
+    float* y32 = nullptr;
+    int y32_ps = 0, y32_co = 0;
+    int hilo = 0;                            // bf16x3 operands: 1 = three products per pair, 2 = single weights (two products)
+    int y_hilo = 0, y_abs = 0;
+    float acc_scale = 1.f;                   // hi/lo launches: hesic_conv2d_hilo_set_acc_scale
+
+    void set_ws(void* p, size_t bytes) { ws = (float*)p; ws_bytes = p ? bytes : 0; }
+    void set_y32(float* p, int ps, int co) { f32out = p != nullptr; y32 = p; y32_ps = ps; y32_co = co; }
+};
+
+// The launch igemm_plan chose for a descriptor and its options: everything but the data pointers.
+struct IgemmPlan {
+    IgemmArgs a;                             // geometry and launch constants; the pointers are igemm_launch's
+    bool fast;                               // 16-bit storage: the DMA kernels (igemm_glds_kernel and its kin)
+    int bm, BN, bk, ksplit;
+    size_t ws_need;
+    bool use_s1p, use_tr4, halo, deep;
+    int64_t nblocks;
+    int variant[4];                          // what hesic_conv2d_variant reports
+};
+}  // namespace
 
 extern "C" int hesic_gdn_pack_params(const float* beta, const float* gamma, float beta_min, void* gamma_packed, float* beta_packed,
                                      int C, void* stream) {
@@ -2171,7 +2191,7 @@ extern "C" int hesic_gdn_pack_params(const float* beta, const float* gamma, floa
     hipLaunchKernelGGL(gdn_pack_kernel, dim3(8), dim3(256), 0, (hipStream_t)stream, beta, gamma, sqrtf(beta_min + 1.0f / 68719476736.0f),
                        (h16_t*)gamma_packed, beta_packed);
     HESIC_LAUNCH_RETURN("gdn_pack_params");
-}   // when set, hesic_conv2d_forward only reports its tile choice
+}
 
 extern "C" int hesic_gdn_pack_params_batched(const hesic_gdn_pack_job* jobs_device, int n_jobs, void* stream) {
     HESIC_CHECK_ARG(jobs_device && n_jobs > 0 && n_jobs < (1 << 20), "gdn_pack_params_batched: bad arguments");
@@ -2186,44 +2206,12 @@ extern "C" int hesic_gdn_pack_params_lo(const float* gamma, void* gamma_lo_packe
     HESIC_LAUNCH_RETURN("gdn_pack_params_lo");
 }
 
-extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias,
-                                    void* y, void* stream);
-
-extern "C" int hesic_conv2d_variant(const hesic_conv_desc* d, int* bm_bn_bk_glds) {
-    HESIC_CHECK_ARG(d && bm_bn_bk_glds, "conv2d_variant: null pointer");
-    g_plan_out = bm_bn_bk_glds;
-    const int rc = hesic_conv2d_forward(d, (const void*)16, (const void*)16, nullptr, (void*)16, nullptr);
-    g_plan_out = nullptr;
-    return rc;
-}
-
-extern "C" int hesic_conv2d_gdn_forward(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias,
-                                        const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* stream) {
-    HESIC_CHECK_ARG(d && gamma_packed && beta_packed, "conv2d_gdn_forward: null pointer");
-    HESIC_CHECK_ARG(d->dtype == HESIC_H16 && d->Cout == 128 && d->act == HESIC_ACT_NONE && d->Cin % 32 == 0,
-                    "conv2d_gdn_forward: needs bf16 storage, Cout == 128, Cin %% 32 == 0 and no activation");
-    g_gdn_gamma = gamma_packed; g_gdn_beta = beta_packed; g_gdn_mode = inverse ? 2 : 1;
-    const int rc = hesic_conv2d_forward(d, x, w_packed, bias, y, stream);
-    g_gdn_gamma = nullptr; g_gdn_beta = nullptr; g_gdn_mode = 0;
-    return rc;
-}
-
-extern "C" int hesic_conv2d_gdn_forward_train(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias,
-                                              const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* y_pre,
-                                              void* stream) {
-    HESIC_CHECK_ARG(y_pre, "conv2d_gdn_forward_train: null pointer");
-    g_y_pre = y_pre;
-    const int rc = hesic_conv2d_gdn_forward(d, x, w_packed, bias, gamma_packed, beta_packed, inverse, y, stream);
-    g_y_pre = nullptr;
-    return rc;
-}
-
-extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias,
-                                    void* y, void* stream) {
-    HESIC_CHECK_ARG(d && x && w_packed && (y || g_y32), "conv2d_forward: null pointer");
+// The launch of one descriptor under one set of options: the argument checks that need no data pointer, then tile, K split and kernel family.
+// Host arithmetic on *d and o alone -- no HIP call, no data pointer read -- so the queries below run it on any machine.
+static int igemm_plan(const hesic_conv_desc* d, const IgemmOpts& o, IgemmPlan& pl) {
     HESIC_CHECK_ARG(d->Cin % BK == 0, "conv2d_forward: Cin=%d must be a multiple of %d (use hesic_sconv2d_forward)", d->Cin, BK);
-    HESIC_CHECK_ARG(!g_hilo || ((g_gdn_mode == 0 || g_gdn_mode >= 3) && g_groups == 1 && !g_act_split), "conv2d_forward_hilo: plain or hi/lo GDN epilogue, no groups");
-    const int hilo = g_hilo;                       // bf16x3 operands: x = [hi | lo] (2 Cin channels), weights [w_hi | w_lo] (2 Cin per tap and cout)
+    HESIC_CHECK_ARG(!o.hilo || ((o.gdn_mode == 0 || o.gdn_mode >= 3) && o.groups == 1 && !o.act_split), "conv2d_forward_hilo: plain or hi/lo GDN epilogue, no groups");
+    const int hilo = o.hilo;                       // bf16x3 operands: x = [hi | lo] (2 Cin channels), weights [w_hi | w_lo] (2 Cin per tap and cout)
     HESIC_CHECK_ARG(!hilo || d->Cin % 32 == 0, "conv2d_forward_hilo: Cin must be a multiple of 32");
     const int cin_k = hilo ? 2 * d->Cin : d->Cin;  // channels per tap of the packed weights; a stage of BK covers BK/2 logical channels then,
                                                    // so every "Cin % BK" tile-selection rule below applies to cin_k
@@ -2234,16 +2222,12 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
     HESIC_CHECK_ARG(d->KH * d->KW <= MAX_TAPS, "conv2d_forward: at most %d taps", MAX_TAPS);
     HESIC_CHECK_ARG(d->stride == 1 || d->stride == 2, "conv2d_forward: stride must be 1 or 2");
     HESIC_CHECK_ARG(d->dtype == HESIC_H16 || d->dtype == HESIC_F32, "conv2d_forward: bad dtype");
-    HESIC_CHECK_ARG(d->x_c_off + (hilo ? 2 : 1) * d->Cin <= d->x_pix_stride && d->y_c_off + ((g_gdn_mode >= 3 || (hilo && g_y_hilo)) ? 2 : 1) * d->Cout <= d->y_pix_stride,
+    HESIC_CHECK_ARG(d->x_c_off + (hilo ? 2 : 1) * d->Cin <= d->x_pix_stride && d->y_c_off + ((o.gdn_mode >= 3 || (hilo && o.y_hilo)) ? 2 : 1) * d->Cout <= d->y_pix_stride,
                     "conv2d_forward: channel slice out of range");
 
-    IgemmArgs a;
+    IgemmArgs& a = pl.a;
     memset(&a, 0, sizeof(a));
-    a.x = x; a.w = w_packed; a.bias = bias; a.y = y;
-    a.gdn_gamma = g_gdn_gamma; a.gdn_beta = g_gdn_beta; a.y_pre = g_y_pre; a.gdn_gamma_lo = g_gdn_gamma_lo; a.y_hilo = g_y_hilo; a.y_abs = g_y_abs;
-    a.acc_scale = hilo ? g_hilo_acc_scale_active : 1.f;
-    a.y32 = g_y32; a.y32_ps = g_y32_ps; a.y32_co = g_y32_co;
-    const int gdn = g_gdn_mode;
+    const int gdn = o.gdn_mode;
     a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = cin_k; a.x_ps = d->x_pix_stride; a.x_co = d->x_c_off;
     a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.y_ps = d->y_pix_stride; a.y_co = d->y_c_off;
     a.act = d->act; a.in_abs = d->in_abs;
@@ -2274,7 +2258,7 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
     const int BN = (pad128 - pad64) * 8 > pad128 ? 64 : 128;
     a.n_tiles = (d->Cout + BN - 1) / BN;
     const bool fast = d->dtype == HESIC_H16;
-    HESIC_CHECK_ARG(!g_y32 || (fast && !gdn), "conv2d_forward_f32out: bf16 storage without the fused GDN epilogue only");
+    HESIC_CHECK_ARG(!o.f32out || (fast && !gdn), "conv2d_forward_f32out: bf16 storage without the fused GDN epilogue only");
     // pixel tile: 128, shrunk to 64 / 32 (fast path only) until the grid has ~1.5 blocks per CU
     int bm = 128;
     auto count_blocks = [&](int m) {
@@ -2285,8 +2269,8 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
         return (int64_t)a.n_tiles * ((a.QW + tw - 1) / tw) * ((a.QH + th - 1) / th) * a.B * a.nphase;
     };
     // hesic_conv2d_set_phase_fusion(2): eligible transposed layers take the 128-pixel tile whatever the grid (the fused kernel's only tile)
-    const bool tr4_shape = d->dtype == HESIC_H16 && d->transposed && s == 2 && BN == 128 && cin_k % 64 == 0 && !hilo && !g_y32 && g_groups == 1 &&
-                           !g_act_split && !a.in_abs && d->Cout % 128 == 0 && gdn <= 2;
+    const bool tr4_shape = d->dtype == HESIC_H16 && d->transposed && s == 2 && BN == 128 && cin_k % 64 == 0 && !hilo && !o.f32out && o.groups == 1 &&
+                           !o.act_split && !a.in_abs && d->Cout % 128 == 0 && gdn <= 2;
     const bool tr4_forced = tr4_shape && g_phase4_mode.load(std::memory_order_relaxed) >= 2;
     if (fast && !tr4_forced) {
         if (count_blocks(128) < 384) bm = 64;
@@ -2297,14 +2281,14 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
     // into up to 8 slices (>= 4 stages each) on the largest pixel tile the map fills, partial tiles go to the workspace
     // in fp32 and splitk_reduce_kernel applies bias / activation / bf16 rounding.
     int ksplit = 1;
-    if (fast && !gdn && (g_ws || g_ws_need)) {
+    if (fast && !gdn && (o.ws || o.assume_ws)) {
         const int qpix = a.QH * a.QW;
         int bm_s = qpix >= 128 ? 128 : (qpix >= 64 ? 64 : 32);
         if (bm_s == 32 && !(BN == 128 && cin_k % 64 == 0)) bm_s = 64;
         // Launches whose output feeds round() or a likelihood (the pair layers and every fp32-latent launch) decide the split PER IMAGE: the
         // slice count fixes the summation order, and a pair's latents must not depend on what else is in the batch (round 4: pair 7 of 8
         // and the pair alone differed in the last bit of y -- 2 slices against 8 -- which flips a latent per ~3 pairs)
-        const int per_img = (hilo || g_y32) ? a.B : 1;
+        const int per_img = (hilo || o.f32out) ? a.B : 1;
         const int64_t nb = count_blocks(bm_s) / per_img;
         const int bk_ = cin_k % 64 == 0 ? 64 : 32;
         const int min_taps = d->transposed ? (d->KH / s) * (d->KW / s) : a.ntaps_live;
@@ -2331,18 +2315,17 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
     // transposed: no gain, one 8-wave block per CU marches through its barriers in lockstep), 4 waves of 64 couts x 128 pixels (359 us: a lone wave
     // per SIMD loses its latency cover), a ring of three 48 KB stages (332.2 / 337.9 us), loader waves next to the compute waves (144.0 vs 143.8 us).
     if (fast && hilo == 1 && gdn == 3 && bm == 128 && BN == 128 && cin_k % 64 == 0 && ksplit == 1 && count_blocks(256) >= 384) bm = 256;
-    if (g_groups > 1 || g_act_split) {
+    if (o.groups > 1 || o.act_split) {
         HESIC_CHECK_ARG(fast && !gdn, "conv2d_forward_grouped: bf16 storage, no fused GDN");
-        HESIC_CHECK_ARG(d->Cout % g_groups == 0 && (d->Cout / g_groups) % BN == 0 && g_act_split % BN == 0,
+        HESIC_CHECK_ARG(d->Cout % o.groups == 0 && (d->Cout / o.groups) % BN == 0 && o.act_split % BN == 0,
                         "conv2d_forward_grouped: couts per group and the activation split must be multiples of the cout tile (%d)", BN);
-        HESIC_CHECK_ARG(d->x_c_off + (g_groups - 1) * g_x_group_step + d->Cin <= d->x_pix_stride, "conv2d_forward_grouped: input slice out of range");
+        HESIC_CHECK_ARG(d->x_c_off + (o.groups - 1) * o.x_group_step + d->Cin <= d->x_pix_stride, "conv2d_forward_grouped: input slice out of range");
         ksplit = 1; bm = (bm == 256) ? 128 : bm;          // one block per output tile: the K-slice reduce knows neither groups nor two activations
-        a.x_group_step = g_groups > 1 ? g_x_group_step : 0;
-        a.tiles_per_group = (d->Cout / g_groups) / BN;
-        a.act2 = g_act2; a.act_split = g_act_split;
+        a.x_group_step = o.groups > 1 ? o.x_group_step : 0;
+        a.tiles_per_group = (d->Cout / o.groups) / BN;
+        a.act2 = o.act2; a.act_split = o.act_split;
     }
-    const size_t ws_need = ksplit > 1 ? (size_t)ksplit * d->B * d->Ho * d->Wo * d->Cout * sizeof(float) : 0;
-    if (g_ws_need) { *g_ws_need = ws_need; return 0; }
+    pl.ws_need = ksplit > 1 ? (size_t)ksplit * d->B * d->Ho * d->Wo * d->Cout * sizeof(float) : 0;
     // Stride-1 5 x 5 convs on 128 input channels with the input patch resident in LDS (igemm_s1p_kernel: 16 x 16 q-tile x 128 couts, one block
     // per CU).  HESIC_IGEMM_S1_PATCH = 0: never, 1 (default): auto, 2: whenever the shape is eligible; read on every call.
     // Auto, set by measurement: the 256-pixel grid must fill the chip (>= 256 blocks, rounds of the 256 CUs >= 70 % full),
@@ -2360,8 +2343,7 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
         use_s1p = shape && mode && (mode >= 2 || fills);
         if (use_s1p) bm = 256;
     }
-    HESIC_CHECK_ARG(ws_need <= g_ws_bytes, "conv2d_forward_ws: workspace too small (%zu < %zu bytes)", g_ws_bytes, ws_need);
-    a.ksplit = ksplit; a.ws = g_ws;
+    a.ksplit = ksplit;
     // 2-D pixel patch: as square as the q-grid allows
     int TW = 16;
     while (TW > 1 && TW / 2 >= a.QW) TW /= 2;
@@ -2385,18 +2367,49 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
         const bool fills = mode >= 2 || (nb4 >= 384 && nb4 * 10 >= rounds * 512 * 7);
         use_tr4 = fast && mode && fills && bm == 128 && tr4_shape && ksplit == 1 && (int64_t)d->Ho * d->Wo * a.y_ps * 2 < (1ll << 31);
     }
-    if (g_plan_out) {
-        if (use_tr4) { g_plan_out[0] = 128; g_plan_out[1] = 128; g_plan_out[2] = 64; g_plan_out[3] = 2; return 0; }
-        if (use_s1p) { g_plan_out[0] = 256; g_plan_out[1] = 128; g_plan_out[2] = 64; g_plan_out[3] = 1; return 0; }
-        g_plan_out[0] = bm; g_plan_out[1] = BN; g_plan_out[2] = fast ? (((bm == 32) || (bm == 64 && BN == 64)) && cin_k % 128 == 0 ? 128 : (cin_k % 64 == 0 ? 64 : 32)) : BK; g_plan_out[3] = fast ? 1 : 0;
-        return 0;
-    }
     a.tap_parity = (!d->transposed && s == 2 && d->KH >= 2 && d->KW >= 2 && a.ntaps_live == d->KH * d->KW && ksplit == 1) ? 1 : 0;
     // (a class -> channel chunk -> tap walk of the parity classes cut the pair launch's fetch traffic 800 -> 655 MB at equal time, 343 vs 346 us, but
     // the summation order then depends on the K step of the tile variant, and with it the last bit of y on the batch size: removed in round 6)
     a.fd_nt = make_fastdiv((uint32_t)a.n_tiles); a.fd_tx = make_fastdiv((uint32_t)a.tiles_x); a.fd_ty = make_fastdiv((uint32_t)a.tiles_y);
     a.fd_b = make_fastdiv((uint32_t)a.B); a.fd_ph = make_fastdiv((uint32_t)a.nphase);
-    const dim3 grid((unsigned)nblocks), block(NTHREADS);
+    int bk = BK;
+    bool deep = false;
+    if (fast) {
+        // ring depth: a 2-deep ring relies on 2-3 co-resident blocks per CU to hide the L2 latency; layers whose grid
+        // is too small for that (low resolutions) get a 4-deep ring instead, as long as every block of the grid still
+        // fits in LDS at once (160 KB per CU)
+        // the buffer-addressed DMA keeps 32-bit offsets relative to the tile's first input row and the packed weights
+        HESIC_CHECK_ARG(((int64_t)(TH * a.in_step + 2 * d->KH) * a.W + 2 * d->KW) * a.x_ps * 2 < (1ll << 31) &&
+                            (int64_t)d->KH * d->KW * d->Cout * cin_k * 2 < (1ll << 31),
+                        "conv2d_forward: image rows / weights too large for 32-bit tile offsets");
+        bk = cin_k % 64 == 0 ? 64 : 32;
+        const int stage = (bm + BN) * bk * 2;
+        const int64_t per_cu = (nblocks + 255) / 256;
+        deep = bm < 128 ? per_cu * 4 * stage <= 160 * 1024 : (bk == 32 && per_cu * 4 * stage <= 160 * 1024);
+    }
+    pl.fast = fast; pl.bm = bm; pl.BN = BN; pl.bk = bk; pl.ksplit = ksplit; pl.nblocks = nblocks;
+    pl.use_s1p = use_s1p; pl.use_tr4 = use_tr4; pl.deep = deep;
+    // the input patch staged once per fused block (HALO): 128 input channels, 5 x 5 taps at pad 2 (shifts -1 .. 1), the 8 x 16 q-tile
+    pl.halo = TR4_HALO && cin_k == 128 && d->KH == 5 && d->KW == 5 && d->pad == 2 && a.TW == 16 && a.TH == 8;
+    int* v = pl.variant;
+    if (use_tr4) { v[0] = 128; v[1] = 128; v[2] = 64; v[3] = 2; }
+    else if (use_s1p) { v[0] = 256; v[1] = 128; v[2] = 64; v[3] = 1; }
+    else { v[0] = bm; v[1] = BN; v[2] = fast ? (((bm == 32) || (bm == 64 && BN == 64)) && cin_k % 128 == 0 ? 128 : (cin_k % 64 == 0 ? 64 : 32)) : BK; v[3] = fast ? 1 : 0; }
+    return 0;
+}
+
+// Run a plan on the data (igemm_run has checked the pointers): the workspace check, the kernel dispatch, the K-slice reduce.
+static int igemm_launch(const IgemmPlan& pl, const IgemmOpts& o, const void* x, const void* w_packed, const float* bias, void* y, void* stream) {
+    HESIC_CHECK_ARG(pl.ws_need <= o.ws_bytes, "conv2d_forward_ws: workspace too small (%zu < %zu bytes)", o.ws_bytes, pl.ws_need);
+    IgemmArgs a = pl.a;
+    a.x = x; a.w = w_packed; a.bias = bias; a.y = y;
+    a.gdn_gamma = o.gdn_gamma; a.gdn_beta = o.gdn_beta; a.y_pre = o.y_pre; a.gdn_gamma_lo = o.gdn_gamma_lo; a.y_hilo = o.y_hilo; a.y_abs = o.y_abs;
+    a.acc_scale = o.acc_scale;
+    a.y32 = o.y32; a.y32_ps = o.y32_ps; a.y32_co = o.y32_co;
+    a.ws = o.ws;
+    const int hilo = o.hilo, gdn = o.gdn_mode, bm = pl.bm, BN = pl.BN, bk = pl.bk, ksplit = pl.ksplit;
+    const bool deep = pl.deep;
+    const dim3 grid((unsigned)pl.nblocks), block(NTHREADS);
     hipStream_t st = (hipStream_t)stream;
 #define LAUNCH_GLDS(M_, N_, K_, S_)                                                                          \
     do {                                                                                                    \
@@ -2421,19 +2434,8 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
         if (deep) LAUNCH_GLDS(M_, N_, K_, 4);                        \
         else LAUNCH_GLDS(M_, N_, K_, 2);                             \
     } while (0)
-    if (fast) {
-        // ring depth: a 2-deep ring relies on 2-3 co-resident blocks per CU to hide the L2 latency; layers whose grid
-        // is too small for that (low resolutions) get a 4-deep ring instead, as long as every block of the grid still
-        // fits in LDS at once (160 KB per CU)
-        // the buffer-addressed DMA keeps 32-bit offsets relative to the tile's first input row and the packed weights
-        HESIC_CHECK_ARG(((int64_t)(TH * a.in_step + 2 * d->KH) * a.W + 2 * d->KW) * a.x_ps * 2 < (1ll << 31) &&
-                            (int64_t)d->KH * d->KW * d->Cout * cin_k * 2 < (1ll << 31),
-                        "conv2d_forward: image rows / weights too large for 32-bit tile offsets");
-        const int bk = cin_k % 64 == 0 ? 64 : 32;
-        const int stage = (bm + BN) * bk * 2;
-        const int64_t per_cu = (nblocks + 255) / 256;
-        const bool deep = bm < 128 ? per_cu * 4 * stage <= 160 * 1024 : (bk == 32 && per_cu * 4 * stage <= 160 * 1024);
-        if (use_s1p) {
+    if (pl.fast) {
+        if (pl.use_s1p) {
             // resident input patch, weights-only ring (igemm_s1p_kernel): more than the 64 KB of static LDS, requested once per device
             constexpr int NS = IGEMM_S1P_NS, LDS = s1p_lds_bytes(NS);
             static std::atomic<uint64_t> attr_done{0};
@@ -2446,14 +2448,12 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
             }
             hipLaunchKernelGGL((igemm_s1p_kernel<NS>), grid, dim3(512), LDS, st, a);
         } else if (bm == 256) {
-            // pair conv + GDN on 256 pixels x 128 couts: 8 waves of 64 x 64, one block per CU (see the tile choice above)
+            // pair conv + GDN on 256 pixels x 128 couts: 8 waves of 64 x 64, one block per CU (see the tile choice in igemm_plan)
             hipLaunchKernelGGL((igemm_glds_kernel<256, 128, 64, 2, 3, 8, 0, 1>), grid, dim3(512), 0, st, a);
-        } else if (use_tr4) {
+        } else if (pl.use_tr4) {
             // the four output phases of a tile in one block (igemm_tr4_kernel): a quarter of the blocks, one 50-stage pipeline each
-            const dim3 grid4((unsigned)(nblocks / 4));
-            // the input patch staged once per block (HALO): 128 input channels, 5 x 5 taps at pad 2 (shifts -1 .. 1), the 8 x 16 q-tile
-            const bool halo = TR4_HALO && cin_k == 128 && d->KH == 5 && d->KW == 5 && d->pad == 2 && a.TW == 16 && a.TH == 8;
-            if (halo) {
+            const dim3 grid4((unsigned)(pl.nblocks / 4));
+            if (pl.halo) {
                 if (gdn == 1) hipLaunchKernelGGL((igemm_tr4_kernel<1, 1>), grid4, block, 0, st, a);
                 else if (gdn == 2) hipLaunchKernelGGL((igemm_tr4_kernel<2, 1>), grid4, block, 0, st, a);
                 else hipLaunchKernelGGL((igemm_tr4_kernel<0, 1>), grid4, block, 0, st, a);
@@ -2467,54 +2467,97 @@ extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, con
         } else if (bm == 64) {
             // same lever as for the 32-pixel tile: BK = 128 where two 2-stage blocks still fit a CU (64 x 64 tiles: 64 KB; 128 ->
             // 192 5x5 s2 @64x64 B=8: 28.4 -> 22.3 us) or where the grid is one block per CU anyway (64 x 128 tiles, 96 KB)
-            if (bk == 64 && BN == 64 && cin_k % 128 == 0) LAUNCH_GLDS(64, 64, 128, 2);
+            if (bk == 64 && BN == 64 && a.Cin % 128 == 0) LAUNCH_GLDS(64, 64, 128, 2);
             else if (bk == 64) { if (BN == 128) LAUNCH_GLDS_NS(64, 128, 64); else LAUNCH_GLDS_NS(64, 64, 64); }
             else { if (BN == 128) LAUNCH_GLDS_NS(64, 128, 32); else LAUNCH_GLDS_NS(64, 64, 32); }
         } else {
             // 32-pixel tiles are bound by per-stage bookkeeping and barrier waits (PMC: ~95 scalar/vector instructions per 4
             // MFMAs): BK = 128 halves the stage count (8 MFMAs per wave and stage, 2-deep ring of 40 KB stages) --
             // 128 -> 128 5x5 s1 @32x32 B=8: 23.4 -> 18.8 us; a 3-deep ring was slower (20.7).
-            if (cin_k % 128 == 0) LAUNCH_GLDS(32, 128, 128, 2);
+            if (a.Cin % 128 == 0) LAUNCH_GLDS(32, 128, 128, 2);
             else LAUNCH_GLDS_NS(32, 128, 64);
         }
     } else {
         if (BN == 128) hipLaunchKernelGGL((igemm_conv_kernel<float, 128>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((igemm_conv_kernel<float, 64>), grid, block, 0, st, a);
     }
+#undef LAUNCH_GLDS_NS
+#undef LAUNCH_GLDS
     if (ksplit > 1) {
-        const int64_t npix = (int64_t)d->B * d->Ho * d->Wo;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid_for(npix * (d->Cout / 8), 256)), dim3(256), 0, st, (const float*)g_ws, ksplit,
-                           npix, d->Cout, bias, d->act, (h16_t*)y, d->y_pix_stride, d->y_c_off, g_y32, g_y32_ps, g_y32_co, g_y_hilo, g_y_abs);
+        const int64_t npix = (int64_t)a.B * a.Ho * a.Wo;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid_for(npix * (a.Cout / 8), 256)), dim3(256), 0, st, (const float*)o.ws, ksplit,
+                           npix, a.Cout, bias, a.act, (h16_t*)y, a.y_ps, a.y_co, o.y32, o.y32_ps, o.y32_co, o.y_hilo, o.y_abs);
     }
     HESIC_LAUNCH_RETURN("conv2d_forward");
 }
 
-extern "C" size_t hesic_conv2d_ws_bytes(const hesic_conv_desc* d) {
-    size_t need = 0;
-    if (!d) return 0;
-    g_ws_need = &need;
-    const int rc = hesic_conv2d_forward(d, (const void*)16, (const void*)16, nullptr, (void*)16, nullptr);
-    g_ws_need = nullptr;
-    return rc == 0 ? need : 0;
+// What every launching entry point does behind its own checks.  The null-pointer check stands in front of the planner's, as it always has.
+static int igemm_run(const hesic_conv_desc* d, const IgemmOpts& o, const void* x, const void* w_packed, const float* bias, void* y, void* stream) {
+    HESIC_CHECK_ARG(d && x && w_packed && (y || o.y32), "conv2d_forward: null pointer");
+    IgemmPlan pl;
+    if (int rc = igemm_plan(d, o, pl)) return rc;
+    return igemm_launch(pl, o, x, w_packed, bias, y, stream);
 }
+
+extern "C" int hesic_conv2d_forward(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias,
+                                    void* y, void* stream) {
+    return igemm_run(d, IgemmOpts(), x, w_packed, bias, y, stream);
+}
+
+extern "C" int hesic_conv2d_variant(const hesic_conv_desc* d, int* bm_bn_bk_glds) {
+    HESIC_CHECK_ARG(d && bm_bn_bk_glds, "conv2d_variant: null pointer");
+    IgemmPlan pl;
+    if (int rc = igemm_plan(d, IgemmOpts(), pl)) return rc;
+    memcpy(bm_bn_bk_glds, pl.variant, sizeof(pl.variant));
+    return 0;
+}
+
+static int conv2d_gdn_forward_impl(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias, const void* gamma_packed,
+                                   const float* beta_packed, int inverse, void* y, void* y_pre, void* stream) {
+    HESIC_CHECK_ARG(d && gamma_packed && beta_packed, "conv2d_gdn_forward: null pointer");
+    HESIC_CHECK_ARG(d->dtype == HESIC_H16 && d->Cout == 128 && d->act == HESIC_ACT_NONE && d->Cin % 32 == 0,
+                    "conv2d_gdn_forward: needs bf16 storage, Cout == 128, Cin %% 32 == 0 and no activation");
+    IgemmOpts o;
+    o.gdn_gamma = gamma_packed; o.gdn_beta = beta_packed; o.gdn_mode = inverse ? 2 : 1;
+    o.y_pre = y_pre;
+    return igemm_run(d, o, x, w_packed, bias, y, stream);
+}
+
+extern "C" int hesic_conv2d_gdn_forward(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias,
+                                        const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* stream) {
+    return conv2d_gdn_forward_impl(d, x, w_packed, bias, gamma_packed, beta_packed, inverse, y, nullptr, stream);
+}
+
+extern "C" int hesic_conv2d_gdn_forward_train(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias,
+                                              const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* y_pre,
+                                              void* stream) {
+    HESIC_CHECK_ARG(y_pre, "conv2d_gdn_forward_train: null pointer");
+    return conv2d_gdn_forward_impl(d, x, w_packed, bias, gamma_packed, beta_packed, inverse, y, y_pre, stream);
+}
+
+// the split-K scratch a launch with these options would ask for (0: no split, or a descriptor the planner refuses)
+static size_t igemm_ws_query(const hesic_conv_desc* d, IgemmOpts o) {
+    if (!d) return 0;
+    o.assume_ws = true;
+    IgemmPlan pl;
+    return igemm_plan(d, o, pl) == 0 ? pl.ws_need : 0;
+}
+
+extern "C" size_t hesic_conv2d_ws_bytes(const hesic_conv_desc* d) { return igemm_ws_query(d, IgemmOpts()); }
 
 /* The same query for hesic_conv2d_forward_f32out: a launch with an fp32 latent output decides its K split per image (a pair's latents
  * must not depend on the batch), so its scratch can differ from the plain launch's. */
 extern "C" size_t hesic_conv2d_f32out_ws_bytes(const hesic_conv_desc* d) {
-    size_t need = 0;
-    if (!d) return 0;
-    g_ws_need = &need; g_y32 = (float*)16; g_y32_ps = d->Cout; g_y32_co = 0;
-    const int rc = hesic_conv2d_forward(d, (const void*)16, (const void*)16, nullptr, (void*)16, nullptr);
-    g_ws_need = nullptr; g_y32 = nullptr; g_y32_ps = g_y32_co = 0;
-    return rc == 0 ? need : 0;
+    IgemmOpts o;
+    o.f32out = true;
+    return igemm_ws_query(d, o);
 }
 
 extern "C" int hesic_conv2d_forward_ws(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias,
                                        void* y, void* ws, size_t ws_bytes, void* stream) {
-    g_ws = (float*)ws; g_ws_bytes = ws ? ws_bytes : 0;
-    const int rc = hesic_conv2d_forward(d, x, w_packed, bias, y, stream);
-    g_ws = nullptr; g_ws_bytes = 0;
-    return rc;
+    IgemmOpts o;
+    o.set_ws(ws, ws_bytes);
+    return igemm_run(d, o, x, w_packed, bias, y, stream);
 }
 
 extern "C" int hesic_conv2d_forward_f32out(const hesic_conv_desc* d, const void* x, const void* w_packed, const float* bias,
@@ -2524,12 +2567,10 @@ extern "C" int hesic_conv2d_forward_f32out(const hesic_conv_desc* d, const void*
     HESIC_CHECK_ARG(d->dtype == HESIC_H16, "conv2d_forward_f32out: the fp32 copy exists for bf16 storage (fp32 storage is fp32 already)");
     HESIC_CHECK_ARG(y32_c_off % 4 == 0 && y32_pix_stride % 4 == 0 && y32_c_off + d->Cout <= y32_pix_stride,
                     "conv2d_forward_f32out: fp32 channel slice must be 16-byte aligned and in range");
-    g_y32 = y_f32; g_y32_ps = y32_pix_stride; g_y32_co = y32_c_off;
-    g_ws = (float*)ws; g_ws_bytes = ws ? ws_bytes : 0;
-    const int rc = hesic_conv2d_forward(d, x, w_packed, bias, y, stream);
-    g_ws = nullptr; g_ws_bytes = 0;
-    g_y32 = nullptr; g_y32_ps = g_y32_co = 0;
-    return rc;
+    IgemmOpts o;
+    o.set_y32(y_f32, y32_pix_stride, y32_c_off);
+    o.set_ws(ws, ws_bytes);
+    return igemm_run(d, o, x, w_packed, bias, y, stream);
 }
 
 extern "C" int hesic_conv2d_forward_grouped(const hesic_conv_desc* d, int groups, int x_group_step, int act2, int act_split, const void* x,
@@ -2539,12 +2580,10 @@ extern "C" int hesic_conv2d_forward_grouped(const hesic_conv_desc* d, int groups
     HESIC_CHECK_ARG(d->dtype == HESIC_H16, "conv2d_forward_grouped: bf16 storage");
     HESIC_CHECK_ARG(!y_f32 || (y32_c_off % 4 == 0 && y32_pix_stride % 4 == 0 && y32_c_off + d->Cout <= y32_pix_stride),
                     "conv2d_forward_grouped: fp32 channel slice must be 16-byte aligned and in range");
-    g_groups = groups; g_x_group_step = x_group_step; g_act2 = act2; g_act_split = act_split;
-    g_y32 = y_f32; g_y32_ps = y32_pix_stride; g_y32_co = y32_c_off;
-    const int rc = hesic_conv2d_forward(d, x, w_packed, bias, y, stream);
-    g_groups = 1; g_x_group_step = g_act2 = g_act_split = 0;
-    g_y32 = nullptr; g_y32_ps = g_y32_co = 0;
-    return rc;
+    IgemmOpts o;
+    o.groups = groups; o.x_group_step = x_group_step; o.act2 = act2; o.act_split = act_split;
+    o.set_y32(y_f32, y32_pix_stride, y32_c_off);
+    return igemm_run(d, o, x, w_packed, bias, y, stream);
 }
 
 // One weight of a grouped launch into its cout slice [co_off, co_off + Cout) of a packed buffer [KH*KW][Cout_total][Cin].
@@ -2578,7 +2617,8 @@ static int conv2d_forward_hilo_n(int products, const hesic_conv_desc* d, const v
                                          void* y_hilo, int y_abs, float* y_f32, int y32_pix_stride, int y32_c_off, void* ws, size_t ws_bytes, void* stream) {
     // the accumulator scale named for THIS launch (hesic_conv2d_hilo_set_acc_scale) is taken and cleared first: a call refused by one of the
     // checks below must not leave it behind for an unrelated later launch
-    const float acc_scale_now = g_hilo_acc_scale;
+    IgemmOpts o;
+    o.acc_scale = g_hilo_acc_scale;
     g_hilo_acc_scale = 1.f;
     HESIC_CHECK_ARG(d && x_hilo && w_packed_hilo && (y_hilo || y_f32), "conv2d_forward_hilo: null pointer");
     HESIC_CHECK_ARG(d->dtype == HESIC_H16 && !d->in_abs, "conv2d_forward_hilo: bf16 storage, no |x| on load (use y_abs on the producer)");
@@ -2589,19 +2629,12 @@ static int conv2d_forward_hilo_n(int products, const hesic_conv_desc* d, const v
     }
     HESIC_CHECK_ARG(!y_f32 || (y32_c_off % 4 == 0 && y32_pix_stride % 4 == 0 && y32_c_off + d->Cout <= y32_pix_stride),
                     "conv2d_forward_hilo: fp32 channel slice must be 16-byte aligned and in range");
-    g_hilo = products == 2 ? 2 : 1;
-    g_hilo_acc_scale_active = acc_scale_now;
-    g_gdn_gamma = gamma_packed; g_gdn_gamma_lo = gamma_lo_packed; g_gdn_beta = beta_packed; g_gdn_mode = gdn ? (inverse ? 4 : 3) : 0;
-    g_y32 = y_f32; g_y32_ps = y32_pix_stride; g_y32_co = y32_c_off;
-    g_y_hilo = (!gdn && y_hilo) ? 1 : 0; g_y_abs = y_abs ? 1 : 0;
-    g_ws = (float*)ws; g_ws_bytes = ws ? ws_bytes : 0;
-    const int rc = hesic_conv2d_forward(d, x_hilo, w_packed_hilo, bias, y_hilo, stream);
-    g_ws = nullptr; g_ws_bytes = 0;
-    g_hilo = 0; g_y_hilo = g_y_abs = 0;
-    g_gdn_gamma = nullptr; g_gdn_gamma_lo = nullptr; g_gdn_beta = nullptr; g_gdn_mode = 0;
-    g_y32 = nullptr; g_y32_ps = g_y32_co = 0;
-    g_hilo_acc_scale_active = 1.f;                        // one launch only
-    return rc;
+    o.hilo = products == 2 ? 2 : 1;
+    o.gdn_gamma = gamma_packed; o.gdn_gamma_lo = gamma_lo_packed; o.gdn_beta = beta_packed; o.gdn_mode = gdn ? (inverse ? 4 : 3) : 0;
+    o.set_y32(y_f32, y32_pix_stride, y32_c_off);
+    o.y_hilo = (!gdn && y_hilo) ? 1 : 0; o.y_abs = y_abs ? 1 : 0;
+    o.set_ws(ws, ws_bytes);
+    return igemm_run(d, o, x_hilo, w_packed_hilo, bias, y_hilo, stream);
 }
 
 extern "C" int hesic_conv2d_hilo_set_acc_scale(float scale) {
@@ -2635,17 +2668,13 @@ extern "C" int hesic_conv2d_gdn_forward_hilo_out(const hesic_conv_desc* d, const
     HESIC_CHECK_ARG(d && x && w_packed && gamma_packed && gamma_lo_packed && beta_packed && y_hilo, "conv2d_gdn_forward_hilo_out: null pointer");
     HESIC_CHECK_ARG(d->dtype == HESIC_H16 && !d->in_abs && d->Cout == 128 && d->act == HESIC_ACT_NONE && d->Cin % 32 == 0 && !d->transposed,
                     "conv2d_gdn_forward_hilo_out: 16-bit storage, Conv2d, Cout == 128, Cin %% 32 == 0, no activation");
-    g_gdn_gamma = gamma_packed; g_gdn_gamma_lo = gamma_lo_packed; g_gdn_beta = beta_packed; g_gdn_mode = inverse ? 4 : 3;
-    const int rc = hesic_conv2d_forward(d, x, w_packed, bias, y_hilo, stream);
-    g_gdn_gamma = nullptr; g_gdn_gamma_lo = nullptr; g_gdn_beta = nullptr; g_gdn_mode = 0;
-    return rc;
+    IgemmOpts o;
+    o.gdn_gamma = gamma_packed; o.gdn_gamma_lo = gamma_lo_packed; o.gdn_beta = beta_packed; o.gdn_mode = inverse ? 4 : 3;
+    return igemm_run(d, o, x, w_packed, bias, y_hilo, stream);
 }
 
 extern "C" size_t hesic_conv2d_hilo_ws_bytes(const hesic_conv_desc* d) {
-    size_t need = 0;
-    if (!d) return 0;
-    g_ws_need = &need; g_hilo = 1;
-    const int rc = hesic_conv2d_forward(d, (const void*)16, (const void*)16, nullptr, (void*)16, nullptr);
-    g_ws_need = nullptr; g_hilo = 0;
-    return rc == 0 ? need : 0;
+    IgemmOpts o;
+    o.hilo = 1;
+    return igemm_ws_query(d, o);
 }

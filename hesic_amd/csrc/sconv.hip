@@ -1217,30 +1217,16 @@ SArgs make_args(const hesic_sconv_desc* d) {
 
 }  // namespace
 
-static thread_local const void* g_w_img = nullptr;       // set by the *_prepacked entry points around the ordinary launchers
+// the (I)GDN of hesic_sconv2d_forward_cat_gdn (SArgs::gdn_*); mode 0: none
+struct CatGdn {
+    const float* beta = nullptr;
+    const float* gamma = nullptr;
+    float bound = 0.f;
+    int mode = 0, inverse = 0;
+};
 
-static thread_local const float* g_cat_beta = nullptr;    // set by hesic_sconv2d_forward_cat_gdn around the ordinary launcher
-static thread_local const float* g_cat_gamma = nullptr;
-static thread_local float g_cat_bound = 0.f;
-static thread_local int g_cat_mode = 0, g_cat_inverse = 0;
-
-extern "C" int hesic_sconv2d_forward_cat(const hesic_sconv_desc* d, const void* xa, const void* xb, const int64_t xb_strides[4],
-                                         int xb_dtype, int ca, const float* w, const float* bias, void* y, void* stream);
-
-extern "C" int hesic_sconv2d_forward_cat_gdn(const hesic_sconv_desc* d, const void* xa, const void* xb, const int64_t xb_strides[4],
-                                             int xb_dtype, int ca, const float* w, const float* bias, const float* gdn_beta,
-                                             const float* gdn_gamma, float beta_min, int inverse, int gdn_on_input, void* y, void* stream) {
-    HESIC_CHECK_ARG(gdn_beta && gdn_gamma, "sconv2d_forward_cat_gdn: null pointer");
-    HESIC_CHECK_ARG(!gdn_on_input || ca == 3, "sconv2d_forward_cat_gdn: the input-side (I)GDN covers the first tensor's three channels");
-    g_cat_beta = gdn_beta; g_cat_gamma = gdn_gamma; g_cat_bound = sqrtf(beta_min + 1.0f / 68719476736.0f);
-    g_cat_mode = gdn_on_input ? 2 : 1; g_cat_inverse = inverse ? 1 : 0;
-    const int rc = hesic_sconv2d_forward_cat(d, xa, xb, xb_strides, xb_dtype, ca, w, bias, y, stream);
-    g_cat_beta = g_cat_gamma = nullptr; g_cat_mode = 0;
-    return rc;
-}
-
-extern "C" int hesic_sconv2d_forward_cat(const hesic_sconv_desc* d, const void* xa, const void* xb, const int64_t xb_strides[4],
-                                         int xb_dtype, int ca, const float* w, const float* bias, void* y, void* stream) {
+static int sconv_cat_launch(const hesic_sconv_desc* d, const void* xa, const void* xb, const int64_t xb_strides[4], int xb_dtype, int ca,
+                            const float* w, const float* bias, const CatGdn& g, void* y, void* stream) {
     if (int e = check_desc(d, "sconv2d_forward_cat")) return e;
     HESIC_CHECK_ARG(xa && xb && xb_strides && w && y, "sconv2d_forward_cat: null pointer");
     HESIC_CHECK_ARG(d->Cin == 6 && d->Cout == 3 && d->KH == 5 && d->KW == 5 && d->stride == 1 && d->pad == 2 && d->Wo >= 128 &&
@@ -1251,7 +1237,7 @@ extern "C" int hesic_sconv2d_forward_cat(const hesic_sconv_desc* d, const void* 
     a.x = xa; a.w = w; a.bias = bias; a.y = y;
     a.x2 = xb; a.x2s_b = xb_strides[0]; a.x2s_c = xb_strides[1]; a.x2s_y = xb_strides[2]; a.x2s_x = xb_strides[3];
     a.x2_dtype = xb_dtype; a.c_split = ca;
-    a.gdn_beta = g_cat_beta; a.gdn_gamma = g_cat_gamma; a.gdn_bound = g_cat_bound; a.gdn_mode = g_cat_mode; a.gdn_inverse = g_cat_inverse;
+    a.gdn_beta = g.beta; a.gdn_gamma = g.gamma; a.gdn_bound = g.bound; a.gdn_mode = g.mode; a.gdn_inverse = g.inverse;
     constexpr int px = 4;           // A/B switch
     if (px == 8) {
         const int tiles = ((a.Wo + 127) / 128) * ((a.Ho + 15) / 16) * a.B;
@@ -1263,25 +1249,44 @@ extern "C" int hesic_sconv2d_forward_cat(const hesic_sconv_desc* d, const void* 
     HESIC_LAUNCH_RETURN("sconv2d_forward_cat");
 }
 
-extern "C" int hesic_sconv2d_forward(const hesic_sconv_desc* d, const void* x, const float* w, const float* bias, void* y,
-                                     void* stream) {
+extern "C" int hesic_sconv2d_forward_cat(const hesic_sconv_desc* d, const void* xa, const void* xb, const int64_t xb_strides[4],
+                                         int xb_dtype, int ca, const float* w, const float* bias, void* y, void* stream) {
+    return sconv_cat_launch(d, xa, xb, xb_strides, xb_dtype, ca, w, bias, CatGdn(), y, stream);
+}
+
+extern "C" int hesic_sconv2d_forward_cat_gdn(const hesic_sconv_desc* d, const void* xa, const void* xb, const int64_t xb_strides[4],
+                                             int xb_dtype, int ca, const float* w, const float* bias, const float* gdn_beta,
+                                             const float* gdn_gamma, float beta_min, int inverse, int gdn_on_input, void* y, void* stream) {
+    HESIC_CHECK_ARG(gdn_beta && gdn_gamma, "sconv2d_forward_cat_gdn: null pointer");
+    HESIC_CHECK_ARG(!gdn_on_input || ca == 3, "sconv2d_forward_cat_gdn: the input-side (I)GDN covers the first tensor's three channels");
+    CatGdn g;
+    g.beta = gdn_beta; g.gamma = gdn_gamma; g.bound = sqrtf(beta_min + 1.0f / 68719476736.0f);
+    g.mode = gdn_on_input ? 2 : 1; g.inverse = inverse ? 1 : 0;
+    return sconv_cat_launch(d, xa, xb, xb_strides, xb_dtype, ca, w, bias, g, y, stream);
+}
+
+// w_image: the prepacked LDS weight image of the *_prepacked entry points (hesic_sconv_pack_weight_image), or null
+static int sconv_forward_launch(const hesic_sconv_desc* d, const void* x, const float* w, const void* w_image, const float* bias, void* y,
+                                void* stream) {
     if (int e = check_desc(d, "sconv2d_forward")) return e;
     HESIC_CHECK_ARG(x && w && y, "sconv2d_forward: null pointer");
     SArgs a = make_args(d);
     a.x = x; a.w = w; a.bias = bias; a.y = y;
-    a.w_img = g_w_img;
+    a.w_img = w_image;
     launch_forward(a, (hipStream_t)stream);
     HESIC_LAUNCH_RETURN("sconv2d_forward");
+}
+
+extern "C" int hesic_sconv2d_forward(const hesic_sconv_desc* d, const void* x, const float* w, const float* bias, void* y,
+                                     void* stream) {
+    return sconv_forward_launch(d, x, w, nullptr, bias, y, stream);
 }
 
 extern "C" int hesic_sconv2d_forward_prepacked(const hesic_sconv_desc* d, const void* x, const float* w, const void* w_image, const float* bias,
                                                void* y, void* stream) {
     HESIC_CHECK_ARG(d && d->transposed && d->Cin == 128 && d->Cout == 3 && d->KH == 5 && d->KW == 5 && d->stride == 2,
                     "sconv2d_forward_prepacked: the image is the weight panel of the 128 -> 3 transposed 5x5 stride-2 stage");
-    g_w_img = w_image;
-    const int rc = hesic_sconv2d_forward(d, x, w, bias, y, stream);
-    g_w_img = nullptr;
-    return rc;
+    return sconv_forward_launch(d, x, w, w_image, bias, y, stream);
 }
 
 // conv (3 -> 128, 5x5 s2) + GDN fused; gamma_packed / beta_packed from hesic_gdn_pack_params.
@@ -1358,8 +1363,8 @@ extern "C" int hesic_sconv_pack_weight_image(int kind, const float* w, const voi
     HESIC_LAUNCH_RETURN("sconv_pack_weight_image");
 }
 
-static int sconv_gdn_launch(const hesic_sconv_desc* d, const void* x, const float* w, const float* bias, const void* gamma_packed,
-                            const float* beta_packed, int inverse, void* y, void* y_pre, void* stream) {
+static int sconv_gdn_launch(const hesic_sconv_desc* d, const void* x, const float* w, const void* w_image, const float* bias,
+                            const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* y_pre, void* stream) {
     if (int e = check_desc(d, "sconv2d_gdn_forward")) return e;
     HESIC_CHECK_ARG(x && w && y && gamma_packed && beta_packed, "sconv2d_gdn_forward: null pointer");
     HESIC_CHECK_ARG(!d->transposed && d->Cin == 3 && d->Cout == 128 && d->KH == 5 && d->KW == 5 && d->stride == 2 && d->pad == 2 &&
@@ -1370,7 +1375,7 @@ static int sconv_gdn_launch(const hesic_sconv_desc* d, const void* x, const floa
     a.x = x; a.w = w; a.bias = bias; a.y = y;
     constexpr int n2w_dbg = 0;
     a.dbg = n2w_dbg;
-    a.w_img = g_w_img;
+    a.w_img = w_image;
     const size_t lds = 65536 + 1024 + 8 * 32 * (128 * 2 + 16);
     const int64_t tiles = (int64_t)((d->Wo + 15) / 16) * ((d->Ho + 1) / 2) * d->B;
     const unsigned grid = (unsigned)((tiles + 7) / 8 < 256 ? (tiles + 7) / 8 : 256);
@@ -1406,14 +1411,14 @@ static int sconv_gdn_launch(const hesic_sconv_desc* d, const void* x, const floa
 
 extern "C" int hesic_sconv2d_gdn_forward(const hesic_sconv_desc* d, const void* x, const float* w, const float* bias,
                                          const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* stream) {
-    return sconv_gdn_launch(d, x, w, bias, gamma_packed, beta_packed, inverse, y, nullptr, stream);
+    return sconv_gdn_launch(d, x, w, nullptr, bias, gamma_packed, beta_packed, inverse, y, nullptr, stream);
 }
 
 extern "C" int hesic_sconv2d_gdn_forward_train(const hesic_sconv_desc* d, const void* x, const float* w, const float* bias,
                                                const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* y_pre,
                                                void* stream) {
     HESIC_CHECK_ARG(y_pre, "sconv2d_gdn_forward_train: null pointer");
-    return sconv_gdn_launch(d, x, w, bias, gamma_packed, beta_packed, inverse, y, y_pre, stream);
+    return sconv_gdn_launch(d, x, w, nullptr, bias, gamma_packed, beta_packed, inverse, y, y_pre, stream);
 }
 
 // dx of y = op(x): the opposite op (conv <-> transposed conv) applied to dy with the same weight tensor:
@@ -1445,8 +1450,5 @@ extern "C" int hesic_sconv2d_dgrad(const hesic_sconv_desc* d, const void* dy, co
 extern "C" int hesic_sconv2d_gdn_forward_prepacked(const hesic_sconv_desc* d, const void* x, const float* w, const void* w_image, const float* bias,
                                                    const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* y_pre,
                                                    void* stream) {
-    g_w_img = w_image;
-    const int rc = sconv_gdn_launch(d, x, w, bias, gamma_packed, beta_packed, inverse, y, y_pre, stream);
-    g_w_img = nullptr;
-    return rc;
+    return sconv_gdn_launch(d, x, w, w_image, bias, gamma_packed, beta_packed, inverse, y, y_pre, stream);
 }

@@ -2475,7 +2475,6 @@ static int make_finish(const hesic_conv_desc* d, const WgArgs& a, const void* ws
     return with_bias ? (int)((P + rpb - 1) / rpb) : 0;
 }
 
-static thread_local int g_wgrad_partial_only = 0;      // set by hesic_conv2d_wgrad_partial: stop after the split-K MFMA launch
 // workspace layout of the direct / partial / finish_batched route (WgArgs::ws_layout).  A/B switch, OFF: HESIC_WGRAD_WS_LAYOUT=1 puts the
 // slices of a (tap, cout) row next to each other.  Measured neutral on the training step (same box, alternating runs: 9.579 / 9.583 ms
 // with it, 9.586 / 9.596 without): the finishing pass still reads 128-byte pieces (its 8 cout x 32 cin tiles) -- contiguity across
@@ -2484,9 +2483,10 @@ static thread_local int g_wgrad_partial_only = 0;      // set by hesic_conv2d_wg
 // adjacent 8.895 / 8.892; the 512-byte-wide finishing pass 9.037 / 9.049; both 9.027 / 9.042 -- the finishing pass's layout is not a lever)
 static int direct_ws_layout() { return 0; }
 
-extern "C" int hesic_conv2d_wgrad_direct(const hesic_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias,
-                                         int accumulate, void* ws, int64_t ws_bytes, void* stream) {
-    HESIC_CHECK_ARG(d && x && dy && (dw || g_wgrad_partial_only), "conv2d_wgrad_direct: null pointer");
+// partial_only (hesic_conv2d_wgrad_partial): stop after the split-K MFMA launch
+static int wgrad_direct_launch(const hesic_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias, int accumulate, void* ws,
+                               int64_t ws_bytes, bool partial_only, void* stream) {
+    HESIC_CHECK_ARG(d && x && dy && (dw || partial_only), "conv2d_wgrad_direct: null pointer");
     const int ce = d->dtype == HESIC_H16 ? 8 : 4;
     HESIC_CHECK_ARG(d->Cin % ce == 0 && d->Cout % ce == 0 && d->x_pix_stride % ce == 0 && d->y_pix_stride % ce == 0 &&
                         d->x_c_off % ce == 0 && d->y_c_off % ce == 0,
@@ -2513,7 +2513,7 @@ extern "C" int hesic_conv2d_wgrad_direct(const hesic_conv_desc* d, const void* x
         db_zeroed = true;
     } else if (d->dtype == HESIC_H16) hipLaunchKernelGGL(wgrad_kernel<h16_t>, dim3((unsigned)blocks), dim3(NT), 0, st, a);
     else hipLaunchKernelGGL(wgrad_kernel<float>, dim3((unsigned)blocks), dim3(NT), 0, st, a);
-    if (g_wgrad_partial_only) HESIC_LAUNCH_RETURN("conv2d_wgrad_partial");
+    if (partial_only) HESIC_LAUNCH_RETURN("conv2d_wgrad_partial");
     if (zero_me && !db_zeroed) zero_async(dbias, d->Cout, st);
     const int T_all = d->KH * d->KW;
     if (a.ntaps < T_all && !accumulate) zero_async(dw, (int64_t)T_all * d->Cout * d->Cin, st);      // dead taps of a masked conv
@@ -2527,6 +2527,15 @@ extern "C" int hesic_conv2d_wgrad_direct(const hesic_conv_desc* d, const void* x
         hipLaunchKernelGGL(wgrad_finish_kernel<float>, dim3((unsigned)(f.n_red + n_col)), dim3(256), 0, st, f, (const float*)dy, dbias, P,
                            d->y_pix_stride, d->y_c_off, rpb);
     HESIC_LAUNCH_RETURN("conv2d_wgrad_direct");
+}
+
+extern "C" int hesic_conv2d_wgrad_direct(const hesic_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias,
+                                         int accumulate, void* ws, int64_t ws_bytes, void* stream) {
+    return wgrad_direct_launch(d, x, dy, dw, dbias, accumulate, ws, ws_bytes, false, stream);
+}
+
+extern "C" int hesic_conv2d_wgrad_partial(const hesic_conv_desc* d, const void* x, const void* dy, void* ws, int64_t ws_bytes, void* stream) {
+    return wgrad_direct_launch(d, x, dy, nullptr, nullptr, 1, ws, ws_bytes, true, stream);
 }
 
 static bool nw_fast_case(const hesic_sconv_desc* d, bool& conv1) {
@@ -2740,9 +2749,6 @@ extern "C" int64_t hesic_gdn_backward_ws_bytes(int64_t P, int C) {
     return generic;
 }
 
-extern "C" int hesic_conv2d_wgrad(const hesic_conv_desc* d, const void* x, const void* dy, float* dw_packed, float* dbias,
-                                  void* ws, int64_t ws_bytes, void* stream);
-
 // ---- the parameter-gradient finishing passes of SEVERAL fused GDN backwards in one launch (round 5): a training step ran 15 of them, 6 us
 // each, one behind every gdn128_bwd_kernel.  hesic_gdn_backward_partial leaves the block partials in the caller's workspace;
 // hesic_gdn_param_finish_batched sums them (the order of gdn_param_finish_kernel: bit-identical) for up to GDN_FIN_NB layers per launch.
@@ -2788,18 +2794,19 @@ __global__ __launch_bounds__(256) void gdn_param_finish_batched_kernel(const Gdn
 }
 }  // namespace
 
-static thread_local int g_gdn_partial_only = 0;    // set by hesic_gdn_backward_partial: stop behind gdn128_bwd_kernel
-extern "C" int hesic_gdn_backward_partial_ok(int64_t P, int C, int dtype);
-static thread_local int g_gdn_accumulate = 0;      // set by hesic_gdn_backward_acc around its call
+extern "C" int hesic_gdn_backward_partial_ok(int64_t P, int C, int dtype) {
+    constexpr bool legacy = false, split_params = false;
+    return (!legacy && !split_params && C == 128 && dtype == HESIC_H16 && P > 0 && P < (1ll << 22)) ? 1 : 0;
+}
 
-extern "C" int hesic_gdn_backward(const void* x, const void* dy, const float* beta, const float* gamma, void* dx, float* dbeta,
-                                  float* dgamma, void* ws, int64_t P, int C, int inverse, float beta_min, int dtype, void* stream) {
-    const int accumulate = g_gdn_accumulate;
-    HESIC_CHECK_ARG(x && dy && beta && gamma && dx && (g_gdn_partial_only || (dbeta && dgamma)) && ws && P > 0 && C > 0, "gdn_backward: bad arguments");
+// accumulate (hesic_gdn_backward_acc): add into dbeta / dgamma; partial_only (hesic_gdn_backward_partial): stop behind gdn128_bwd_kernel
+static int gdn_backward_launch(const void* x, const void* dy, const float* beta, const float* gamma, void* dx, float* dbeta, float* dgamma,
+                               int accumulate, bool partial_only, void* ws, int64_t P, int C, int inverse, float beta_min, int dtype, void* stream) {
+    HESIC_CHECK_ARG(x && dy && beta && gamma && dx && (partial_only || (dbeta && dgamma)) && ws && P > 0 && C > 0, "gdn_backward: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     const float bound = sqrtf(beta_min + kPedestal);
     constexpr bool legacy = false;
-    HESIC_CHECK_ARG(!g_gdn_partial_only || hesic_gdn_backward_partial_ok(P, C, dtype), "gdn_backward_partial: only the fused 128-channel 16-bit form leaves block partials");
+    HESIC_CHECK_ARG(!partial_only || hesic_gdn_backward_partial_ok(P, C, dtype), "gdn_backward_partial: only the fused 128-channel 16-bit form leaves block partials");
     if (!legacy && C == 128 && dtype == HESIC_H16 && P < (1ll << 22)) {
         hesic_conv_desc d;
         gdn_fast_desc(P, d);
@@ -2836,7 +2843,7 @@ extern "C" int hesic_gdn_backward(const void* x, const void* dy, const float* be
                 hipError_t e = hipGetLastError();
                 if (e != hipSuccess) { hesic_set_error("gdn_backward: %s", hipGetErrorString(e)); return (int)e; }
             }
-            if (g_gdn_partial_only) HESIC_LAUNCH_RETURN("gdn_backward_partial");
+            if (partial_only) HESIC_LAUNCH_RETURN("gdn_backward_partial");
             hipLaunchKernelGGL(gdn_param_finish_kernel, dim3((unsigned)(NP / 64)), dim3(256), 0, st, (const float*)part, nb, beta, gamma, dgamma, dbeta, bound, accumulate);
             HESIC_LAUNCH_RETURN("gdn_backward");
         }
@@ -2892,26 +2899,20 @@ extern "C" int hesic_gdn_backward(const void* x, const void* dy, const float* be
     HESIC_LAUNCH_RETURN("gdn_backward");
 }
 
+extern "C" int hesic_gdn_backward(const void* x, const void* dy, const float* beta, const float* gamma, void* dx, float* dbeta,
+                                  float* dgamma, void* ws, int64_t P, int C, int inverse, float beta_min, int dtype, void* stream) {
+    return gdn_backward_launch(x, dy, beta, gamma, dx, dbeta, dgamma, 0, false, ws, P, C, inverse, beta_min, dtype, stream);
+}
+
 extern "C" int hesic_gdn_backward_acc(const void* x, const void* dy, const float* beta, const float* gamma, void* dx, float* dbeta,
                                       float* dgamma, int accumulate, void* ws, int64_t P, int C, int inverse, float beta_min, int dtype,
                                       void* stream) {
-    g_gdn_accumulate = accumulate ? 1 : 0;
-    const int rc = hesic_gdn_backward(x, dy, beta, gamma, dx, dbeta, dgamma, ws, P, C, inverse, beta_min, dtype, stream);
-    g_gdn_accumulate = 0;
-    return rc;
-}
-
-extern "C" int hesic_gdn_backward_partial_ok(int64_t P, int C, int dtype) {
-    constexpr bool legacy = false, split_params = false;
-    return (!legacy && !split_params && C == 128 && dtype == HESIC_H16 && P > 0 && P < (1ll << 22)) ? 1 : 0;
+    return gdn_backward_launch(x, dy, beta, gamma, dx, dbeta, dgamma, accumulate ? 1 : 0, false, ws, P, C, inverse, beta_min, dtype, stream);
 }
 
 extern "C" int hesic_gdn_backward_partial(const void* x, const void* dy, const float* beta, const float* gamma, void* dx, void* ws, int64_t P,
                                           int C, int inverse, float beta_min, int dtype, void* stream) {
-    g_gdn_partial_only = 1;
-    const int rc = hesic_gdn_backward(x, dy, beta, gamma, dx, nullptr, nullptr, ws, P, C, inverse, beta_min, dtype, stream);
-    g_gdn_partial_only = 0;
-    return rc;
+    return gdn_backward_launch(x, dy, beta, gamma, dx, nullptr, nullptr, 0, true, ws, P, C, inverse, beta_min, dtype, stream);
 }
 
 extern "C" int hesic_gdn_param_finish_batched(int n, const void* const* ws, const int64_t* P, const float* const* beta, const float* const* gamma,
@@ -2960,13 +2961,6 @@ extern "C" int hesic_gdn_backward_planar_acc(const void* x, const void* dy, cons
     HESIC_LAUNCH_RETURN("gdn_backward_planar");
 }
 
-extern "C" int hesic_conv2d_wgrad_partial(const hesic_conv_desc* d, const void* x, const void* dy, void* ws, int64_t ws_bytes, void* stream) {
-    g_wgrad_partial_only = 1;
-    const int rc = hesic_conv2d_wgrad_direct(d, x, dy, nullptr, nullptr, 1, ws, ws_bytes, stream);
-    g_wgrad_partial_only = 0;
-    return rc;
-}
-
 // The split-K launches of n layers (what hesic_conv2d_wgrad_partial does for one), the 128-channel-tile MFMA ones among them sharing grids of
 // up to WB_MAX jobs (wgrad_tr_batched_kernel); layers on another kernel (wgrad_row_kernel, the VALU fallback) are launched one by one.  The
 // partials land in each job's own workspace exactly as hesic_conv2d_wgrad_partial leaves them: hesic_conv2d_wgrad_finish_batched follows.
@@ -2994,7 +2988,7 @@ extern "C" int hesic_conv2d_wgrad_partial_batched(int n, const hesic_conv_desc* 
                 fill_args(d, a0);
                 HESIC_CHECK_ARG(a0.nsplit == nsplit[i], "conv2d_wgrad_partial_batched: job %d: %d K slices named, this layer's kernel takes %d", i, nsplit[i], a0.nsplit);
             }
-            if (int rc = hesic_conv2d_wgrad_partial(d, x[i], dy[i], ws[i], ws_bytes[i], stream)) return rc;
+            if (int rc = wgrad_direct_launch(d, x[i], dy[i], nullptr, nullptr, 1, ws[i], ws_bytes[i], true, stream)) return rc;
             continue;
         }
         const int ce = 8;
@@ -3022,13 +3016,6 @@ extern "C" int hesic_conv2d_wgrad_partial_batched(int n, const hesic_conv_desc* 
         hipLaunchKernelGGL((wgrad_tr_batched_kernel<64, 2>), dim3((unsigned)B.start[B.n]), dim3(NT), 2 * 64 * 512, st, B);
     }
     HESIC_LAUNCH_RETURN("conv2d_wgrad_partial_batched");
-}
-
-extern "C" int hesic_conv2d_wgrad_finish_batched_n(int n, const hesic_conv_desc* descs, const void* const* ws, const void* const* dy, float* const* dw,
-                                                   float* const* dbias, int accumulate, const int32_t* nsplit, void* stream);
-extern "C" int hesic_conv2d_wgrad_finish_batched(int n, const hesic_conv_desc* descs, const void* const* ws, const void* const* dy, float* const* dw,
-                                                 float* const* dbias, int accumulate, void* stream) {
-    return hesic_conv2d_wgrad_finish_batched_n(n, descs, ws, dy, dw, dbias, accumulate, nullptr, stream);
 }
 
 extern "C" int hesic_conv2d_wgrad_finish_batched_n(int n, const hesic_conv_desc* descs, const void* const* ws, const void* const* dy, float* const* dw,
@@ -3060,4 +3047,9 @@ extern "C" int hesic_conv2d_wgrad_finish_batched_n(int n, const hesic_conv_desc*
         else hipLaunchKernelGGL(wgrad_finish_batched_kernel<float>, dim3((unsigned)fb.start[fb.n]), dim3(256), 0, st, fb);
     }
     HESIC_LAUNCH_RETURN("conv2d_wgrad_finish_batched");
+}
+
+extern "C" int hesic_conv2d_wgrad_finish_batched(int n, const hesic_conv_desc* descs, const void* const* ws, const void* const* dy, float* const* dw,
+                                                 float* const* dbias, int accumulate, void* stream) {
+    return hesic_conv2d_wgrad_finish_batched_n(n, descs, ws, dy, dw, dbias, accumulate, nullptr, stream);
 }
