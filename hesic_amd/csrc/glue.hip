@@ -196,6 +196,7 @@ __global__ void fill_neg_inf_kernel(float* __restrict__ p, int n) {
     if (i < n) p[i] = -INFINITY;
 }
 __device__ __forceinline__ void atomic_max_float(float* addr, float v) {
+    v += 0.0f;          // -0.0 -> +0.0: as an int -0.0 is INT_MIN and would lose against the -inf fill (0xFF800000)
     if (v >= 0.f) atomicMax((int*)addr, __float_as_int(v));
     else atomicMin((unsigned int*)addr, __float_as_uint(v));
 }
@@ -727,7 +728,9 @@ extern "C" int hesic_sum_sq_diff(const void* a, int a_dtype, const int64_t a_str
     SqArgs q;
     q.a = a; q.b = b; q.a_dt = a_dtype; q.b_dt = b_dtype; q.B = B; q.C = C; q.H = H; q.W = W; q.out = out;
     for (int i = 0; i < 4; ++i) { q.as[i] = a_strides[i]; q.bs[i] = b_strides[i]; }
-    // few blocks: every block ends in one fp64 atomic on the same address, and those serialise in L2
+    // few blocks: every block ends in one fp64 atomic on the same address, and those serialise in L2.  tests/glue_ref.py
+    // (remainder_pixels) restates this block rule -- 256 lanes, 1024 pixels a block, at most 512 blocks -- to name the pixels the C == 3
+    // remainder loop handles, and tests/test_glue_ref_cpu.py holds the resulting counts.  Change them together (hesic_rd_sums below too).
     hipLaunchKernelGGL(sum_sq_diff_kernel, dim3(grid_for((int64_t)B * H * W, 256 * 4, 512)), dim3(256), 0, (hipStream_t)stream, q);
     HESIC_LAUNCH_RETURN("sum_sq_diff");
 }
