@@ -661,8 +661,7 @@ extern "C" int hesic_gmm_forward(const hesic_gmm_desc* d, const void* y, const v
     const int64_t total = (int64_t)d->B * d->HW * d->M;
     const dim3 grid(grid_for(total, 256));
     // pair form: even channel geometry (4-byte bf16 pairs, 8-byte fp32 pairs), 32-bit pair index
-    constexpr bool no_pair = false;                  // A/B switch for profiling
-    const bool pair = !no_pair && d->dtype == HESIC_H16 && (d->K == 5 || d->K == 1) && d->M % 2 == 0 && d->sm_pix_stride % 2 == 0 &&
+    const bool pair = d->dtype == HESIC_H16 && (d->K == 5 || d->K == 1) && d->M % 2 == 0 && d->sm_pix_stride % 2 == 0 &&
                       d->s_c_off % 2 == 0 && d->m_c_off % 2 == 0 && total / 2 < (1ll << 31) && !((uintptr_t)y & 3) &&
                       !((uintptr_t)scales & 3) && !((uintptr_t)means & 3) && !((uintptr_t)noise & 3) && !((uintptr_t)y_hat & 3) &&
                       !((uintptr_t)lik & 7) && !((uintptr_t)weights & 7);
@@ -700,8 +699,7 @@ extern "C" int hesic_gmm_cdf_rows(const hesic_gmm_desc* d, int b, const void* sc
                     "gmm_cdf: bad arguments");
     HESIC_CHECK_ARG(weights || d->K == 1, "gmm_cdf: weights required for K > 1");
     const int64_t total = (int64_t)n_channels * d->HW;
-    constexpr bool thread_rows = false;          // A/B switch: the one-thread-per-row kernel for every alphabet
-    if (2 * minmax + 1 <= CDF_WAVE_MAX && !thread_rows) {
+    if (2 * minmax + 1 <= CDF_WAVE_MAX) {
         const dim3 gw(grid_for(total, 4, 256 * 16));
         if (d->dtype == HESIC_H16)
             hipLaunchKernelGGL(gmm_cdf_wave_kernel<h16_t>, gw, dim3(256), 0, (hipStream_t)stream, *d, b, (const h16_t*)scales, (const h16_t*)means, weights,
@@ -754,8 +752,7 @@ extern "C" int hesic_gmm_backward(const hesic_gmm_desc* d, const void* y, const 
     if (ppb < 4) ppb = 4;
     if (ppb > 64) ppb = 64;
     const dim3 grid((d->M + 63) / 64, (d->HW + ppb - 1) / ppb, d->B);
-    constexpr bool slow_bwd = false;                  // A/B switch for profiling
-    if (d->dtype == HESIC_H16 && !slow_bwd && (d->K == 5 || d->K == 1)) {
+    if (d->dtype == HESIC_H16 && (d->K == 5 || d->K == 1)) {
         if (d->K == 5)
             hipLaunchKernelGGL((gmm_bwd_kernel<h16_t, 5>), grid, dim3(256), 0, (hipStream_t)stream, *d, (const h16_t*)y,
                                (const h16_t*)scales, (const h16_t*)means, weights, (const h16_t*)noise, g_lik,

@@ -1139,8 +1139,7 @@ __global__ __launch_bounds__(256) void sconv_small_s1_kernel(const SArgs a) {
 }
 
 int launch_forward(const SArgs& a, hipStream_t st) {
-    constexpr bool legacy = false;   // A/B switch for profiling
-    if (!legacy && !a.transposed && a.y_dtype == HESIC_H16 && a.Cin == 3 && a.KH == 5 && a.KW == 5 && a.stride == 2 && a.pad == 2 &&
+    if (!a.transposed && a.y_dtype == HESIC_H16 && a.Cin == 3 && a.KH == 5 && a.KW == 5 && a.stride == 2 && a.pad == 2 &&
         a.Cout % 8 == 0 && a.ys_c == 1 && (a.ys_x % 8) == 0 && (a.ys_y % 8) == 0 && (a.ys_b % 8) == 0) {
         const int64_t tiles = (int64_t)((a.Wo + 15) / 16) * ((a.Ho + 7) / 8) * a.B;
         const dim3 grid((unsigned)(tiles < 512 ? tiles : 512));      // 2 resident blocks per CU, each loops over tiles
@@ -1151,7 +1150,7 @@ int launch_forward(const SArgs& a, hipStream_t st) {
         const int tiles = ((a.Wo + 7) / 8) * ((a.Ho + 7) / 8) * a.B;
         const size_t lds = (size_t)a.KH * a.KW * a.Cin * a.Cout * 4;
         hipLaunchKernelGGL(sconv_narrow_to_wide_kernel, dim3(tiles), dim3(256), lds, st, a);
-    } else if (!legacy && a.transposed && a.x_dtype == HESIC_H16 && a.stride == 2 && a.KH == 5 && a.KW == 5 && a.pad == 2 &&
+    } else if (a.transposed && a.x_dtype == HESIC_H16 && a.stride == 2 && a.KH == 5 && a.KW == 5 && a.pad == 2 &&
                a.Cout == 3 && a.Cin == 128 && a.xs_c == 1 && (a.xs_x % 8) == 0 && (a.xs_y % 8) == 0 && (a.xs_b % 8) == 0 &&
                a.Ho == 2 * a.H && a.Wo == 2 * a.W && (int64_t)a.H * a.xs_y * 2 < (1ll << 31) && (int64_t)a.B * a.H * a.W < (1ll << 31)) {
         const int64_t tiles = (int64_t)((a.W + W2N_TW - 1) / W2N_TW) * ((a.H + W2N_TH - 1) / W2N_TH) * a.B;
@@ -1165,17 +1164,11 @@ int launch_forward(const SArgs& a, hipStream_t st) {
             hipLaunchKernelGGL(sconv_wide_to_narrow_kernel<h16_t>, dim3((unsigned)cdiv64(total, 256)), dim3(256), lds, st, a);
         else
             hipLaunchKernelGGL(sconv_wide_to_narrow_kernel<float>, dim3((unsigned)cdiv64(total, 256)), dim3(256), lds, st, a);
-    } else if (!legacy && a.stride == 1 && a.Cin == 6 && a.Cout == 3 && a.KH == 5 && a.KW == 5 && a.pad == 2 && a.Ho == a.H &&
+    } else if (a.stride == 1 && a.Cin == 6 && a.Cout == 3 && a.KH == 5 && a.KW == 5 && a.pad == 2 && a.Ho == a.H &&
                a.Wo == a.W && a.Wo >= 128) {
-        constexpr int px = 4;       // A/B switch
-        if (px == 8) {
-            const int tiles = ((a.Wo + 127) / 128) * ((a.Ho + 15) / 16) * a.B;
-            hipLaunchKernelGGL((sconv_6to3_s1_kernel<5, 8>), dim3(tiles), dim3(256), 0, st, a);
-        } else {
-            const int tiles = ((a.Wo + 63) / 64) * ((a.Ho + 15) / 16) * a.B;
-            hipLaunchKernelGGL((sconv_6to3_s1_kernel<5, 4>), dim3(tiles), dim3(256), 0, st, a);
-        }
-    } else if (!legacy && a.stride == 1 && ((a.Cin == 6 && a.Cout == 3) || (a.Cin == 3 && a.Cout == 6)) && a.KH == 5 && a.KW == 5 &&
+        const int tiles = ((a.Wo + 63) / 64) * ((a.Ho + 15) / 16) * a.B;
+        hipLaunchKernelGGL((sconv_6to3_s1_kernel<5, 4>), dim3(tiles), dim3(256), 0, st, a);
+    } else if (a.stride == 1 && ((a.Cin == 6 && a.Cout == 3) || (a.Cin == 3 && a.Cout == 6)) && a.KH == 5 && a.KW == 5 &&
                a.pad == 2 && a.Ho == a.H && a.Wo == a.W && a.Wo >= 64) {
         const int tiles = ((a.Wo + 63) / 64) * ((a.Ho + 15) / 16) * a.B;
         if (a.Cin == 6) hipLaunchKernelGGL((sconv_small_s1_lds_kernel<6, 3, 5>), dim3(tiles), dim3(256), 0, st, a);
@@ -1238,14 +1231,8 @@ static int sconv_cat_launch(const hesic_sconv_desc* d, const void* xa, const voi
     a.x2 = xb; a.x2s_b = xb_strides[0]; a.x2s_c = xb_strides[1]; a.x2s_y = xb_strides[2]; a.x2s_x = xb_strides[3];
     a.x2_dtype = xb_dtype; a.c_split = ca;
     a.gdn_beta = g.beta; a.gdn_gamma = g.gamma; a.gdn_bound = g.bound; a.gdn_mode = g.mode; a.gdn_inverse = g.inverse;
-    constexpr int px = 4;           // A/B switch
-    if (px == 8) {
-        const int tiles = ((a.Wo + 127) / 128) * ((a.Ho + 15) / 16) * a.B;
-        hipLaunchKernelGGL((sconv_6to3_s1_kernel<5, 8>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        const int tiles = ((a.Wo + 63) / 64) * ((a.Ho + 15) / 16) * a.B;
-        hipLaunchKernelGGL((sconv_6to3_s1_kernel<5, 4>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
-    }
+    const int tiles = ((a.Wo + 63) / 64) * ((a.Ho + 15) / 16) * a.B;
+    hipLaunchKernelGGL((sconv_6to3_s1_kernel<5, 4>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
     HESIC_LAUNCH_RETURN("sconv2d_forward_cat");
 }
 
@@ -1386,8 +1373,7 @@ static int sconv_gdn_launch(const hesic_sconv_desc* d, const void* x, const floa
         attr = true;
     }
     // fp32 planes, unit pixel stride, even width, everything addressable with 32-bit byte offsets inside one image
-    constexpr bool no_fast = false;              // A/B switch for profiling
-    const bool fastx = !no_fast && d->x_dtype == HESIC_F32 && d->xs_x == 1 && d->W % 2 == 0 && tiles < (1ll << 30) &&
+    const bool fastx = d->x_dtype == HESIC_F32 && d->xs_x == 1 && d->W % 2 == 0 && tiles < (1ll << 30) &&
                        (2 * d->xs_c + (int64_t)(d->H + 4) * d->xs_y + d->W) * 4 < (1ll << 31) &&
                        ((int64_t)d->Ho * d->ys_y + (int64_t)d->Wo * d->ys_x) * 2 < (1ll << 31) && d->xs_c >= 0 && d->xs_y >= 0;
     if (fastx) {

@@ -41,11 +41,11 @@ struct WgArgs {
     int QH, QW, transposed, stride, pad, KW, in_abs, in_sq;
     int64_t Q, chunk;
     int co_tiles, ci_tiles, ntaps, nsplit;
-    int rowk;                                      // wgrad_row_kernel takes this layer (fill_args): blocks = KH x tiles x nsplit
-    // split-K workspace layout: 0 = [split][tap][Cout][Cin] (rounds 1-4; the reduce kernels of the packed-layout API and the 1x1 GEMM users
-    // read it), 1 = [tap][Cout][split][Cin] (round 5, the direct / partial / finish_batched route): the slices of one (tap, cout) row are
-    // ADJACENT 512-byte rows, so the finishing pass streams nsplit * Cin * 4 contiguous bytes per row instead of nsplit 128-byte runs that
-    // lie ntaps * Cout * Cin * 4 = 1.6 MB apart (365 us per step for ~1 GB of partials = 2.9 TB/s, profiles/r05_d_train_step_timeline.txt)
+    int rowk;                                      // wgrad_row_kernel takes this layer (wgrad_plan): blocks = KH x tiles x nsplit
+    // in_sq (X squared on load) and ws_layout (1 = [tap][Cout][split][Cin]) are always 0: no launcher sets them any more (the three-launch GDN
+    // backward and the slice-adjacent workspace, measured neutral at 9.579 / 9.583 vs 9.586 / 9.596 ms per training step, are gone).  The
+    // kernels still read both; taking them out of the argument block was tried and left the finishing kernels with 72 instead of 52 - 56
+    // VGPRs (profiles/wgrad_cleanup.json), so the block keeps its shape.
     int ws_layout;
     int8_t tap_id[25];
     // bias gradient on the matrix cores (wgrad_tr_kernel only): the blocks of the taps listed in b_tap (indices into the live taps)
@@ -265,12 +265,7 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const WgArgs a) {
 // rows 0/1 and 2/3 of a half shared their banks -- SQ_LDS_BANK_CONFLICT = 50 % of the kernel's LDS cycles, profiles/r04_e_pmc_sq_train.json.)
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
-#ifndef WG_SWZ
-#define WG_SWZ 2
-#endif
-#ifndef WGRAD_RING_DEFAULT
-#define WGRAD_RING_DEFAULT 0
-#endif
+constexpr int WG_SWZ = 2;         // log2 of the slot distance the XOR above moves a pixel row by: (pixel & 3) << 2
 
 struct WgTrArgs {
     WgArgs w;
@@ -282,11 +277,15 @@ struct WgTrArgs {
 // BK pixels per stage, a ring of NST stages: NST - 1 stages are in flight while one is consumed.  <64, 2> (64 KB, two blocks per CU) is the
 // form of rounds 2-4; <32, 5> (80 KB) keeps twice the bytes in flight per CU for the same two blocks (round 4: the kernel sits parked at
 // its vmcnt / barrier half of its cycles with ONE 32 KB stage per block in flight).
+// The ring stays <64, 2>.  Measured and dropped (training step, same box, ms; round 5): <64, 2> 9.89 / 9.91 | <32, 5> 11.30 | <32, 4> 11.32 | <64, 3>
+// (96 KB: one block per CU) 12.36 | <64, 2> with the stage's DMA instructions spread behind the k-steps' MFMAs 10.58 -- more bytes in flight, or
+// cheaper issue slots for the DMA instructions, are not what the loop is short of.
+constexpr int TR_BK = 64, TR_NST = 2, TR_LDS = TR_NST * TR_BK * 512;
 // hw_bid / nb: this block's hardware id inside its job and the job's block count (the launch's own blockIdx / gridDim for the one-job form;
 // its 8-aligned range of a batched launch, whose surplus ids the caller has already sent home)
-template <int BK, int NST, bool SPREAD = false>
 __device__ __forceinline__ void wgrad_tr_body(const WgTrArgs& A, const int hw_bid, const int nb) {
     const WgArgs& a = A.w;
+    constexpr int BK = TR_BK, NST = TR_NST;
     constexpr int TILE = BK * 256, STAGE = 2 * TILE;       // BK pixels x 128 channels x 2 B per operand
     constexpr int NI = BK / 16;                            // DMA instructions per wave, operand and stage (4 pixel rows each)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -334,13 +333,11 @@ __device__ __forceinline__ void wgrad_tr_body(const WgTrArgs& A, const int hw_bi
         qb[i] = (int)b;
         lin_off[i] = q * lin_ps;
     }
-    // i0 .. i1: which of the stage's NI instruction pairs (the spread form issues one pair behind each k-step's MFMAs)
-    auto issue_slow = [&](int buf, int i0, int i1) {
+    auto issue_slow = [&](int buf) {
         unsigned char* dt = smem + buf * STAGE;
         unsigned char* xt = dt + TILE;
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            if (i < i0 || i >= i1) continue;
             const bool inq = qi[i] < (uint32_t)q_end;
             const int sy = qy[i] * a.stride + sh_y, sx = qx[i] * a.stride + sh_x;
             const bool sok = inq && (unsigned)sy < (unsigned)SH && (unsigned)sx < (unsigned)SW;
@@ -388,7 +385,7 @@ __device__ __forceinline__ void wgrad_tr_body(const WgTrArgs& A, const int hw_bi
         sqy = (int)(r1 - b * (uint32_t)a.QH);
         sqb = (int)b;
     }
-    auto issue_fast = [&](int buf, int i0, int i1) {
+    auto issue_fast = [&](int buf) {
         unsigned char* dt = smem + buf * STAGE;
         unsigned char* xt = dt + TILE;
         unsigned char* lt = a.transposed ? xt : dt;
@@ -401,7 +398,6 @@ __device__ __forceinline__ void wgrad_tr_body(const WgTrArgs& A, const int hw_bi
         const uint32_t vl = inq ? v_lin : OOB;
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            if (i < i0 || i >= i1) continue;
             const bool okx = rowok && (unsigned)(sxw + 4 * i * a.stride + lx) < (unsigned)SW;
             const uint32_t vs = okx ? v_sft : OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(lr, (__attribute__((address_space(3))) void*)(lt + (wave * NI + i) * 1024), 16, (int)vl,
@@ -409,7 +405,6 @@ __device__ __forceinline__ void wgrad_tr_body(const WgTrArgs& A, const int hw_bi
             __builtin_amdgcn_raw_ptr_buffer_load_lds(sr, (__attribute__((address_space(3))) void*)(stt + (wave * NI + i) * 1024), 16, (int)vs,
                                                      (int)(so_s + (uint32_t)(4 * i * a.stride) * sh_ps), 0, 0);
         }
-        if (i1 < NI) return;              // the stage's bookkeeping advances with its last pair
         sq_w += BK;
         sqx += BK;
         if (sqx >= a.QW) {
@@ -457,15 +452,15 @@ __device__ __forceinline__ void wgrad_tr_body(const WgTrArgs& A, const int hw_bi
         constexpr bool ABS = decltype(abs_tag)::value, SQ = decltype(sq_tag)::value, FASTQ = decltype(fast_tag)::value, BIAS = decltype(bias_tag)::value;
         const u32x4 ones_u = {H16_ONE_PAIR, H16_ONE_PAIR, H16_ONE_PAIR, H16_ONE_PAIR};
         const h16x8 ones = __builtin_bit_cast(h16x8, ones_u);
-        auto issue = [&](int buf, int i0, int i1) {
-            if constexpr (FASTQ) issue_fast(buf, i0, i1);
-            else issue_slow(buf, i0, i1);
+        auto issue = [&](int buf) {
+            if constexpr (FASTQ) issue_fast(buf);
+            else issue_slow(buf);
         };
         // stages 0 .. NST-2 go out first; every step then issues stage step + NST - 1 (past the end: out-of-range offsets, zeros into a
         // stage nobody reads -- the count of outstanding DMA instructions stays what the vmcnt below assumes)
         if (nsteps > 0) {
 #pragma unroll
-            for (int p = 0; p < NST - 1; ++p) issue(p, 0, NI);
+            for (int p = 0; p < NST - 1; ++p) issue(p);
         }
         int buf = 0;
         for (int64_t step = 0; step < nsteps; ++step) {
@@ -488,7 +483,7 @@ __device__ __forceinline__ void wgrad_tr_body(const WgTrArgs& A, const int hw_bi
                 }
             };
             const int nbuf = buf == 0 ? NST - 1 : buf - 1;      // the stage consumed one step ago
-            if constexpr (!SPREAD) issue(nbuf, 0, NI);           // in front of the first fragment reads (behind them: 9.71 vs 9.675 ms per step, same box)
+            issue(nbuf);                                         // in front of the first fragment reads (behind them: 9.71 vs 9.675 ms per step, same box)
             __builtin_amdgcn_sched_barrier(0);
             ldf(0, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -526,7 +521,6 @@ __device__ __forceinline__ void wgrad_tr_body(const WgTrArgs& A, const int hw_bi
 #pragma unroll
                     for (int i = 0; i < 2; ++i) bacc[i] = mfma_32x32x16_h16(df[i], ones, bacc[i], 0, 0, 0);
                 }
-                if constexpr (SPREAD) issue(nbuf, ks, ks + 1);       // one instruction pair in the shadow of this k-step's MFMAs
                 __builtin_amdgcn_sched_barrier(0);
             }
             buf = buf + 1 == NST ? 0 : buf + 1;
@@ -574,9 +568,8 @@ __device__ __forceinline__ void wgrad_tr_body(const WgTrArgs& A, const int hw_bi
             }
         }
 }
-template <int BK, int NST, bool SPREAD = false>
 __global__ __launch_bounds__(NT) void wgrad_tr_kernel(const WgTrArgs A) {
-    wgrad_tr_body<BK, NST, SPREAD>(A, (int)blockIdx.x, (int)gridDim.x);
+    wgrad_tr_body(A, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // Several layers' split-K launches in ONE grid (hesic_conv2d_wgrad_partial_batched; round 5).  One launch per layer costs each of the ~30
@@ -594,14 +587,13 @@ struct WgTrBatch {
 };
 static_assert(sizeof(WgTrBatch) <= 4096, "kernel arguments: 4 KB");
 
-template <int BK, int NST>
 __global__ __launch_bounds__(NT) void wgrad_tr_batched_kernel(const WgTrBatch B) {
     int j = 0;
     while (j + 1 < B.n && (int)blockIdx.x >= B.start[j + 1]) ++j;       // uniform: scalar loop over <= 14 entries
     const int local = (int)blockIdx.x - B.start[j], nb8 = B.start[j + 1] - B.start[j];
     if (xcd_remap(local, nb8) >= B.blocks[j]) return;
     // the body reads its job through scalar loads of the argument block; the logical id is recomputed inside from the same (local, nb8)
-    wgrad_tr_body<BK, NST, false>(B.job[j], local, nb8);
+    wgrad_tr_body(B.job[j], local, nb8);
 }
 
 
@@ -728,7 +720,7 @@ __global__ __launch_bounds__(512) void wgrad_row_kernel(const WgRowArgs A) {
             for (int r = 0; r < 16; ++r) acc[kx][i][r] = 0.f;
     // bias column sums: a conv's dY is the linear operand (every block sees all of it: the ky = 0 blocks of ci tile 0 sum it, in the two
     // waves of shifted-quarter 0); a transposed conv's dY is the shifted one: rows 2 qy + ky - 2 and pixels 2 qx + kx - 2 with ky, kx in
-    // {2, 3} cover every dY pixel exactly once (slots (ky - 2) * 2 + (kx - 2), the order setup_bias_part lists them)
+    // {2, 3} cover every dY pixel exactly once (slots (ky - 2) * 2 + (kx - 2), the order wgrad_plan lists them)
     const bool bias_blk = a.bias_part && cit == 0 && (TR ? (ky == 2 || ky == 3) : ky == 0);
     const bool bias_wave = bias_blk && (TR ? wl == 0 : wsd == 0);
     float bsum[2] = {0.f, 0.f};
@@ -942,18 +934,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_colsum_kernel(const float* _
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void wgrad_reduce_wide_colsum_kernel(const float* __restrict__ ws, float* __restrict__ dw, int nsplit, int ntaps,
-                                                                       int64_t per_tap, const WgArgs a, int n_red, const T* __restrict__ dy,
-                                                                       float* __restrict__ db, int64_t P, int C, int ps, int co, int64_t rows_per_block) {
-    __shared__ __attribute__((aligned(16))) float scratch[256 * (16 / (int)sizeof(T)) > 1024 ? 256 * (16 / (int)sizeof(T)) : 1024];
-    if ((int)blockIdx.x >= n_red) {
-        colsum_body<T>(dy, db, P, C, ps, co, rows_per_block, (int)blockIdx.x - n_red, scratch);
-        return;
-    }
-    reduce_wide_body(ws, dw, nsplit, ntaps, per_tap, a, (int)blockIdx.x, (f32x4(*)[16])scratch);
-}
-
 // K-slice reduce straight into the PyTorch weight layout, optionally ACCUMULATING (dw += ...), + the bias column sums, one
 // launch.  A training step used to run reduce (packed layout) -> unpack (PyTorch layout) -> AccumulateGrad copy / add per
 // layer; with the gradients of all parameters living in one flat buffer (train.FlatGroup) this kernel adds the layer's
@@ -965,8 +945,7 @@ struct FinishArgs {
     int tiles_ci, tiles_co, tap_groups, taps_per_group, n_red;
     int8_t tap_id[25];
     const float* bias_part; int nb_parts, accumulate_bias;      // bias column sums left by wgrad_tr_kernel: [nb_parts][Cout], summed in order by ONE block
-    int ws_layout;                                              // WgArgs::ws_layout of the launch that wrote ws
-    int wide;                                                   // round 5: block = 8 couts x 128 cins x ONE tap, 512-byte row reads (finish_body)
+    int ws_layout, wide;                                        // always 0 (see WgArgs::ws_layout; wide: blocks of 8 couts x 128 cins x ONE tap, measured slower)
 };
 
 template <typename T>
@@ -1797,58 +1776,12 @@ __global__ __launch_bounds__(256) void gdn_bwd_param_kernel(const void* __restri
     atomicAdd(dgp + e, acc);
     if (j == 0) atomicAdd(dbp + i, accb);
 }
-// few channels (the 3-channel image-side GDNs): thread = pixel, all C*C + C sums in registers, wave reduction, then one atomic
-// per wave and value -- the (i, j)-per-thread kernel above would run 9 lanes per block
-template <int C>
-__global__ __launch_bounds__(256) void gdn_bwd_param_small_kernel(const void* __restrict__ x, const float* __restrict__ dn,
-                                                                  float* __restrict__ dgp, float* __restrict__ dbp, int64_t P, int dtype) {
-    float g[C][C], bsum[C];
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-        bsum[i] = 0.f;
-#pragma unroll
-        for (int j = 0; j < C; ++j) g[i][j] = 0.f;
-    }
-    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < P; p += (int64_t)gridDim.x * blockDim.x) {
-        float d[C], sq[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            d[c] = dn[p * C + c];
-            const float xv = ld_any(x, p * C + c, dtype);
-            sq[c] = xv * xv;
-        }
-#pragma unroll
-        for (int i = 0; i < C; ++i) {
-            bsum[i] += d[i];
-#pragma unroll
-            for (int j = 0; j < C; ++j) g[i][j] = fmaf(d[i], sq[j], g[i][j]);
-        }
-    }
-    // wave sums -> LDS -> one atomic per block and value (same-address atomics serialise in L2: keep them few)
-    __shared__ float red[4][C * C + C];
-    const int wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-        const float b = wave_sum(bsum[i]);
-        if ((threadIdx.x & 63) == 0) red[wv][C * C + i] = b;
-#pragma unroll
-        for (int j = 0; j < C; ++j) {
-            const float v = wave_sum(g[i][j]);
-            if ((threadIdx.x & 63) == 0) red[wv][i * C + j] = v;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < C * C + C) {
-        const float v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (threadIdx.x < C * C) atomicAdd(dgp + threadIdx.x, v);
-        else atomicAdd(dbp + (threadIdx.x - C * C), v);
-    }
-}
 
 // The three passes above in ONE for the 3-channel image-side GDNs (pre_gdn / after_gdn, newnet1.py:630,669, under autograd): thread = pixel,
 // gamma' / beta' in registers, dn never leaves them -- dx and the C*C + C parameter sums come out of one read of x and gy (the passes
 // took 42 + ~30 + 31 us per GDN on a 512^2 batch-8 image and wrote / re-read two fp32 workspaces).  Same formulas in the same order:
-// dx is bit-identical; the parameter sums keep the per-thread accumulation and the one-atomic-per-block finish of the kernel above.
+// dx is bit-identical; the parameter sums are accumulated per thread (all C*C + C in registers), summed per wave, then per block in LDS, and
+// leave as one atomic per block and value (same-address atomics serialise in L2: keep them few).
 // PL: planar (B, C, HW) tensors -- blockIdx.y = image, P = HW, channel stride HW; otherwise NHWC with P = all pixels.
 template <int C, typename T, bool PL = false>
 __global__ __launch_bounds__(256) void gdn_bwd_small_fused_kernel(const T* __restrict__ x, const T* __restrict__ gy, const float* __restrict__ beta,
@@ -1977,20 +1910,14 @@ __global__ __launch_bounds__(256) void gdn_param_finish_kernel(const float* __re
 // ---- GDN backward, bf16 storage, C = 128: one pass over (x, gy) on the matrix cores.
 //   GEMM1  n = beta' + gamma' x^2          -> r = n^-1/2 | n^1/2,  t1 = g r,  dn = -1/2 g x r^3 | +1/2 g x / r
 //   GEMM2  s_j = sum_i gamma'[i,j] dn_i     -> dx = t1 + 2 x s
-// dn (bf16) also goes to a workspace; dgamma' = dn^T x^2 and dbeta' = colsum(dn) are then produced by the 1x1
-// weight-gradient MFMA kernel (x squared on load).  After the tile load every wave owns its 32 pixel rows of both
-// LDS tiles, so no block barrier is needed inside the tile loop.
+// After the tile load every wave owns its 32 pixel rows of both LDS tiles, so GEMM1 and GEMM2 need no block barrier inside the tile loop.
 // 256-byte rows, 16-byte slots XOR-ed with the row's low four bits, the two bit pairs swapped: any 16 consecutive rows put one logical slot
 // on 16 different physical slots (the row-wise ds_read_b128 fragment reads), AND the rows 4k .. 4k+3 put the logical slots c .. c+3 on four
 // different aligned groups of four (the transposing reads of the third GEMM: 4 pixel rows x 64 bytes per LDS cycle).  The plain
 // slot ^ (row & 15) of rounds 2-3 served only the first: 52 % of the kernel's LDS cycles were bank conflicts.
-#ifndef GB_SWZ_PLAIN
 __device__ __forceinline__ int gb_off(int row, int slot) { return (row * 16 + (slot ^ (((row & 3) << 2) | ((row >> 2) & 3)))) * 16; }
-#else
-__device__ __forceinline__ int gb_off(int row, int slot) { return (row * 16 + (slot ^ (row & 15))) * 16; }
-#endif
 
-// PAR = 1 (the default path): the parameter gradients ride on the same pass.  dgamma'[i][j] = sum_p dn[p][i] x[p][j]^2 is a third GEMM
+// The parameter gradients ride on the same pass.  dgamma'[i][j] = sum_p dn[p][i] x[p][j]^2 is a third GEMM
 // with the PIXELS as K: both operands come out of the two LDS tiles through transposing reads
 // (ds_read_b64_tr_b16: lane = one channel, 4 consecutive pixels per read), 8 k-steps x 4 MFMAs per wave and tile into a 128 x 128 fp32
 // accumulator per block -- wave w owns columns 32 w .. 32 w + 31 (64 accumulation registers) and walks all 128 pixels of the tile, so the
@@ -2001,7 +1928,8 @@ __device__ __forceinline__ int gb_off(int row, int slot) { return (row * 16 + (s
 // are dropped by the range check, no branches), so the compiler can count the outstanding memory operations exactly -- the loop top
 // waits for the next tile's loads only, not for the stores of the tile before (the branchy form waited vmcnt(0): a store round trip
 // per tile) -- and can batch the LDS reads of the epilogues across channel groups.
-template <bool PAR, bool INV>
+// dn_out is not used (the dn workspace of the three-launch form); it keeps its place in the kernel's argument block.
+template <bool INV>
 __global__ __launch_bounds__(256) void gdn128_bwd_kernel(const h16_t* __restrict__ x, const h16_t* __restrict__ gy,
                                                          const float* __restrict__ beta, const float* __restrict__ gamma,
                                                          h16_t* __restrict__ dx, h16_t* __restrict__ dn_out, float* __restrict__ part,
@@ -2041,7 +1969,6 @@ __global__ __launch_bounds__(256) void gdn128_bwd_kernel(const h16_t* __restrict
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, nbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc((void*)gy, 0, nbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t dxr = __builtin_amdgcn_make_buffer_rsrc((void*)dx, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t dnr = __builtin_amdgcn_make_buffer_rsrc((void*)(PAR ? dx : dn_out), 0, nbytes, 0x00020000);
     const int lofs = (r0 + (lane >> 4)) * 256 + (lane & 15) * 16;      // this lane's first row / slot, bytes
     auto fetch = [&](int64_t t) {
         const int o = (int)t * 32768 + lofs;
@@ -2060,12 +1987,10 @@ __global__ __launch_bounds__(256) void gdn128_bwd_kernel(const h16_t* __restrict
     __builtin_amdgcn_sched_barrier(0);
     f32x16 g3[4];                               // dgamma' partial of this block's pixels, columns 32 wave .. + 31: [i block]
     float cs = 0.f;                             // dbeta' partial: channel 32 wave + (lane & 31), this lane's pixel halves
-    if constexpr (PAR) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) g3[j][r] = 0.f;
-    }
+        for (int r = 0; r < 16; ++r) g3[j][r] = 0.f;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         // wave-private 32 rows x 16 slots of x and gy: registers -> LDS, then the next tile's loads go out
 #pragma unroll
@@ -2138,44 +2063,42 @@ __global__ __launch_bounds__(256) void gdn128_bwd_kernel(const h16_t* __restrict
                 s2[i] = mfma_32x32x16_h16(gf, df, s2[i], 0, 0, 0);
             }
         }
-        if constexpr (PAR) {
-            // GEMM3: A[i][p] = dn (ds tile), B[p][j] = x^2 (xs tile, still x here), K = the tile's 128 pixels; wave w owns the columns
-            // j = 32 w .. 32 w + 31 of the result.  It reads every wave's rows: a barrier after dn is complete, another one before the
-            // x tile turns into dx.  Rows past P are zero-filled on load (gy = 0 -> dn = 0): they add nothing.
-            typedef __attribute__((ext_vector_type(8))) short s16x8;
-            const int tg = lane >> 4, tt = lane & 15, wv = __builtin_amdgcn_readfirstlane(wave);
-            __syncthreads();
+        // GEMM3: A[i][p] = dn (ds tile), B[p][j] = x^2 (xs tile, still x here), K = the tile's 128 pixels; wave w owns the columns
+        // j = 32 w .. 32 w + 31 of the result.  It reads every wave's rows: a barrier after dn is complete, another one before the
+        // x tile turns into dx.  Rows past P are zero-filled on load (gy = 0 -> dn = 0): they add nothing.
+        typedef __attribute__((ext_vector_type(8))) short s16x8;
+        const int tg = lane >> 4, tt = lane & 15, wv = __builtin_amdgcn_readfirstlane(wave);
+        __syncthreads();
 #pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const int pix = ks * 16 + (tg >> 1) * 8 + (tt >> 2);
-                auto tr = [&](const unsigned char* tile_, int cb, int px_) {
-                    const int ch = cb + (tg & 1) * 16 + 4 * (tt & 3);
-                    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(tile_ + gb_off(px_, ch >> 3) + (ch & 7) * 2));
-                };
-                // B: x^2 for the wave's own column block (squared once per block and element, not once per wave)
-                const s16x8 vx = __builtin_shufflevector(tr(xs, wv * 32, pix), tr(xs, wv * 32, pix + 4), 0, 1, 2, 3, 4, 5, 6, 7);
-                u32x4 ux = __builtin_bit_cast(u32x4, vx);
-                uint32_t* w4 = (uint32_t*)&ux;
+        for (int ks = 0; ks < 8; ++ks) {
+            const int pix = ks * 16 + (tg >> 1) * 8 + (tt >> 2);
+            auto tr = [&](const unsigned char* tile_, int cb, int px_) {
+                const int ch = cb + (tg & 1) * 16 + 4 * (tt & 3);
+                return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(tile_ + gb_off(px_, ch >> 3) + (ch & 7) * 2));
+            };
+            // B: x^2 for the wave's own column block (squared once per block and element, not once per wave)
+            const s16x8 vx = __builtin_shufflevector(tr(xs, wv * 32, pix), tr(xs, wv * 32, pix + 4), 0, 1, 2, 3, 4, 5, 6, 7);
+            u32x4 ux = __builtin_bit_cast(u32x4, vx);
+            uint32_t* w4 = (uint32_t*)&ux;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float l2 = h2f_lo(w4[q]), h2 = h2f_hi(w4[q]);
-                    w4[q] = pack_h2(l2 * l2, h2 * h2);
-                }
-                const h16x8 xf = __builtin_bit_cast(h16x8, ux);
-                {   // the column sums of dn: channel block `wave` by this wave (its own pair of reads: no wave-dependent branch in the loop)
-                    const s16x8 vc = __builtin_shufflevector(tr(ds, wv * 32, pix), tr(ds, wv * 32, pix + 4), 0, 1, 2, 3, 4, 5, 6, 7);
-                    const u32x4 ua = __builtin_bit_cast(u32x4, vc);
-                    cs += ((h2f_lo(ua.x) + h2f_hi(ua.x)) + (h2f_lo(ua.y) + h2f_hi(ua.y))) +
-                          ((h2f_lo(ua.z) + h2f_hi(ua.z)) + (h2f_lo(ua.w) + h2f_hi(ua.w)));
-                }
-#pragma unroll
-                for (int ib = 0; ib < 4; ++ib) {
-                    const s16x8 va = __builtin_shufflevector(tr(ds, ib * 32, pix), tr(ds, ib * 32, pix + 4), 0, 1, 2, 3, 4, 5, 6, 7);
-                    g3[ib] = mfma_32x32x16_h16(__builtin_bit_cast(h16x8, va), xf, g3[ib], 0, 0, 0);
-                }
+            for (int q = 0; q < 4; ++q) {
+                const float l2 = h2f_lo(w4[q]), h2 = h2f_hi(w4[q]);
+                w4[q] = pack_h2(l2 * l2, h2 * h2);
             }
-            __syncthreads();
+            const h16x8 xf = __builtin_bit_cast(h16x8, ux);
+            {   // the column sums of dn: channel block `wave` by this wave (its own pair of reads: no wave-dependent branch in the loop)
+                const s16x8 vc = __builtin_shufflevector(tr(ds, wv * 32, pix), tr(ds, wv * 32, pix + 4), 0, 1, 2, 3, 4, 5, 6, 7);
+                const u32x4 ua = __builtin_bit_cast(u32x4, vc);
+                cs += ((h2f_lo(ua.x) + h2f_hi(ua.x)) + (h2f_lo(ua.y) + h2f_hi(ua.y))) +
+                      ((h2f_lo(ua.z) + h2f_hi(ua.z)) + (h2f_lo(ua.w) + h2f_hi(ua.w)));
+            }
+#pragma unroll
+            for (int ib = 0; ib < 4; ++ib) {
+                const s16x8 va = __builtin_shufflevector(tr(ds, ib * 32, pix), tr(ds, ib * 32, pix + 4), 0, 1, 2, 3, 4, 5, 6, 7);
+                g3[ib] = mfma_32x32x16_h16(__builtin_bit_cast(h16x8, va), xf, g3[ib], 0, 0, 0);
+            }
         }
+        __syncthreads();
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -2189,24 +2112,21 @@ __global__ __launch_bounds__(256) void gdn128_bwd_kernel(const h16_t* __restrict
                 for (int e = 0; e < 4; ++e) o[e] = acc[i][4 * g + e] + 2.f * xv[e] * s2[i][4 * g + e];
                 *(u32x2*)(xs + off) = u32x2{pack_h2(o[0], o[1]), pack_h2(o[2], o[3])};
             }
-        // wave-private copy-out of dx and dn (full 256-byte rows)
+        // wave-private copy-out of dx (full 256-byte rows)
         const int so = (int)tile * 32768 + lofs;
 #pragma unroll
         for (int it = 0; it < 8; ++it) {
             const int c = it * 64 + lane, row = c >> 4, slot = c & 15;
             __builtin_amdgcn_raw_buffer_store_b128(*(const u32x4*)(xs + gb_off(r0 + row, slot)), dxr, so + it * 1024, 0, 0);
-            if constexpr (!PAR) __builtin_amdgcn_raw_buffer_store_b128(*(const u32x4*)(ds + gb_off(r0 + row, slot)), dnr, so + it * 1024, 0, 0);
         }
     }
-    if constexpr (PAR) {
-        float* out = part + (int64_t)blockIdx.x * (128 * 128 + 128);
+    float* out = part + (int64_t)blockIdx.x * (128 * 128 + 128);
 #pragma unroll
-        for (int ib = 0; ib < 4; ++ib)
+    for (int ib = 0; ib < 4; ++ib)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) out[(ib * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * 128 + wave * 32 + frow] = g3[ib][r];
-        cs += __shfl_xor(cs, 32);
-        if (fh == 0) out[128 * 128 + wave * 32 + frow] = cs;
-    }
+        for (int r = 0; r < 16; ++r) out[(ib * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * 128 + wave * 32 + frow] = g3[ib][r];
+    cs += __shfl_xor(cs, 32);
+    if (fh == 0) out[128 * 128 + wave * 32 + frow] = cs;
 }
 
 // (Round 5 built a two-pipelines-per-CU form of this pass, gdn128_bwd2_kernel: correct, 12 - 20 % slower -- the block barrier is the only cheap
@@ -2219,52 +2139,27 @@ static WgTrArgs make_tr_args(const WgArgs& a, float* zero_me, int zero_n) {
     A.zero_me = zero_me; A.zero_n = zero_n;
     A.dqw = make_fastdiv((uint32_t)a.QW);
     A.dqh = make_fastdiv((uint32_t)a.QH);
-    constexpr bool slow = false;          // A/B switch for profiling
-    A.fastq = (!slow && a.QW % 16 == 0 && a.chunk % 64 == 0) ? 1 : 0;
+    A.fastq = (a.QW % 16 == 0 && a.chunk % 64 == 0) ? 1 : 0;
     return A;
-}
-
-void launch_wgrad_tr(const WgArgs& a, int64_t blocks, hipStream_t st, float* zero_me = nullptr, int zero_n = 0) {
-    if (a.rowk) {
-        WgRowArgs R;
-        R.w = a; R.zero_me = zero_me; R.zero_n = zero_n;
-        R.dqw = make_fastdiv((uint32_t)a.QW); R.dqh = make_fastdiv((uint32_t)a.QH);
-        static bool rattr = false;
-        if (!rattr) {
-            (void)hipFuncSetAttribute((const void*)wgrad_row_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ROW_LDS);
-            (void)hipFuncSetAttribute((const void*)wgrad_row_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ROW_LDS);
-            rattr = true;
-        }
-        const dim3 g((unsigned)(5 * a.co_tiles * a.ci_tiles * a.nsplit)), b(512);
-        if (a.transposed) hipLaunchKernelGGL(wgrad_row_kernel<true>, g, b, ROW_LDS, st, R);
-        else hipLaunchKernelGGL(wgrad_row_kernel<false>, g, b, ROW_LDS, st, R);
-        return;
-    }
-    const WgTrArgs A = make_tr_args(a, zero_me, zero_n);
-    // the stage ring is <64, 2>.  Measured and dropped (training step, same box, ms; round 5): <64, 2> 9.89 / 9.91 | <32, 5> 11.30 | <32, 4> 11.32 | <64, 3>
-    // (96 KB: one block per CU) 12.36 | <64, 2> with the stage's DMA instructions spread behind the k-steps' MFMAs 10.58 -- more bytes in flight, or
-    // cheaper issue slots for the DMA instructions, are not what the loop is short of.
-    const dim3 g((unsigned)blocks), b(NT);
-    hipLaunchKernelGGL((wgrad_tr_kernel<64, 2>), g, b, 2 * 64 * 512, st, A);
 }
 
 int pick_splits(int64_t Q, int bk, int tiles, bool batched = false) {
     // aim at ~384 blocks (measured best on MI355X for the step as a whole: every extra slice is another fp32 partial tile
     // to write and reduce), at least 4 K-steps per block
-    constexpr int target0 = 384;   // A/B switch
+    constexpr int target0 = 384;
     // The layers with many pixels (first measured from Q >= 100000 on: 128 -> 128 5x5 on 256^2 inputs at B=8, 25 tap blocks per slice): 16 slices = 400 blocks leave 22 % of
     // the 512 block slots (256 CUs x 2) empty for the whole launch, 21 slices = 525 blocks run a second round for 13 of them; 20 slices = 500
     // blocks fill one round.  Training step, same box, alternating runs (ms): 384: 10.65 / 10.66 / 10.48 | 448: 10.70 (earlier box) | 475: 10.57 |
-    // 500: 10.53 / 10.53 / 10.33 / 10.33 | 512: 11.01 (earlier box) | 1000: 10.64; 500 for EVERY layer: 10.48 (no gain).  0 = off (A/B).
+    // 500: 10.53 / 10.53 / 10.33 / 10.33 | 512: 11.01 (earlier box) | 1000: 10.64; 500 for EVERY layer: 10.48 (no gain).
     constexpr int big_target = 500;
     // from which pixel count on (same box, alternating runs, ms): 100000: 10.62 / 10.61 | 30000 (adds the 128 -> 128 layers on 128^2 inputs): 10.57 / 10.59 | 8000: 10.71
-    constexpr int64_t big_q = 30000;      // A/B switch
+    constexpr int64_t big_q = 30000;
     // batched route (hesic_conv2d_wgrad_nsplit(d, 1)): the grid is shared with the other queued layers, so a layer need not fill the 512 block
     // slots by itself -- fewer slices = fewer fp32 partial tiles to write and reduce.  Training step, same box, alternating runs (ms), small /
     // large-layer targets: 384 / 500: 9.187 / 9.189 | 256 / 500: 9.140 | 200 / 250: 9.077 / 9.074 | 128 / 250: 9.076 | 100 / 125: 9.308
     constexpr int bt_small = 200;
     constexpr int bt_big = 250;
-    const int target = batched ? (Q >= big_q ? bt_big : bt_small) : ((big_target && Q >= big_q) ? big_target : target0);
+    const int target = batched ? (Q >= big_q ? bt_big : bt_small) : (Q >= big_q ? big_target : target0);
     int64_t s = (target + tiles - 1) / tiles;
     const int64_t maxs = Q / (4 * bk) > 0 ? Q / (4 * bk) : 1;
     if (s > maxs) s = maxs;
@@ -2273,10 +2168,53 @@ int pick_splits(int64_t Q, int bk, int tiles, bool batched = false) {
     return (int)s;
 }
 
+// ---------------------------------------------------------------- the plan of one wide-layer weight gradient
+// Everything the entry points and the size queries decide about a layer, from its descriptor (and the two environment switches) alone: host
+// arithmetic, no data pointer, no launch.  wgrad_plan() is the only place these decisions are made; wg_bind() / finish_bind() add a call's
+// pointers to the kernel arguments the plan prepared.
+enum WgRoute {
+    WG_ROW,       // wgrad_row_kernel: a kernel row of taps per block
+    WG_TR,        // wgrad_tr_kernel, alone or in a shared grid (wgrad_tr_batched_kernel): LDS-DMA staging, transposing reads
+    WG_VALU       // wgrad_kernel<T>: register staging; fp32, live taps that are no prefix, offsets beyond 32 bits
+};
+
+struct WgPlan {
+    // the descriptor checks of the entry points (WG_CHECK_PLAN reports them in this order); without taps_ok nothing below is filled in
+    bool chan_ok, taps_ok;
+    int ce, dtype;
+    WgArgs a;                  // geometry, live taps, K slices (nsplit, chunk), bias taps (nb_taps, b_tap); the pointers are null
+    WgRoute route;
+    int64_t blocks;            // grid of the split-K launch
+    int nsplit_shared;         // the K-slice count for a launch that shares its grid (hesic_conv2d_wgrad_nsplit(d, 1)); a.nsplit unless WG_TR
+    // workspace: [nsplit][ntaps][Cout][Cin] fp32 partials, then room for the bias column sums [nsplit][stride^2 <= 4][Cout] (see
+    // WgArgs::bias_part; reserved for every layer, so a size does not depend on the route)
+    int64_t part_bytes, bias_bytes;
+    bool bias_in_gemm;         // the split-K launch leaves dY's column sums in the bias part (taps a.b_tap); otherwise the finishing pass sums dY
+    // the finishing pass (wgrad_finish_kernel): block layout, and the blocks behind the f.n_red reduce blocks when a bias gradient is asked for
+    FinishArgs fin;
+    int64_t P, rpb;            // dY's pixel count and the rows per column-sum block
+    int n_col;
+};
+
+// K slices of `want` (or fewer) whole stages of bk pixels
+static void set_slices(WgArgs& a, int want, int bk) {
+    a.chunk = ((a.Q + want - 1) / want + bk - 1) / bk * bk;
+    a.nsplit = (int)((a.Q + a.chunk - 1) / a.chunk);
+}
+
 // nsplit_override > 0: the caller names the K-slice count of a one-tap-per-block layer (the batched route, whose shared grids want fewer,
 // longer slices than a launch that has to fill the machine by itself); the row kernel keeps its own count
-int fill_args(const hesic_conv_desc* d, WgArgs& a, int nsplit_override = 0) {
-    memset(&a, 0, sizeof(a));
+static WgPlan wgrad_plan(const hesic_conv_desc* d, int nsplit_override) {
+    WgPlan p;
+    memset(&p, 0, sizeof(p));
+    p.dtype = d->dtype;
+    p.ce = d->dtype == HESIC_H16 ? 8 : 4;
+    p.chan_ok = d->Cin % p.ce == 0 && d->Cout % p.ce == 0 && d->x_pix_stride % p.ce == 0 && d->y_pix_stride % p.ce == 0 &&
+                d->x_c_off % p.ce == 0 && d->y_c_off % p.ce == 0;
+    p.taps_ok = d->KH * d->KW <= 25;
+    p.route = WG_VALU;
+    if (!p.taps_ok) return p;               // WgArgs::tap_id holds 25
+    WgArgs& a = p.a;
     a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.x_ps = d->x_pix_stride; a.x_co = d->x_c_off;
     a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.y_ps = d->y_pix_stride; a.y_co = d->y_c_off;
     a.transposed = d->transposed; a.stride = d->stride; a.pad = d->pad; a.KW = d->KW; a.in_abs = d->in_abs;
@@ -2288,17 +2226,22 @@ int fill_args(const hesic_conv_desc* d, WgArgs& a, int nsplit_override = 0) {
         if (!d->tap_mask_lo || ((d->tap_mask_lo >> t) & 1)) a.tap_id[n++] = (int8_t)t;
     a.ntaps = n;
     const int bk = d->dtype == HESIC_H16 ? WC<h16_t>::BK : WC<float>::BK;
+    const int tiles = n * a.co_tiles * a.ci_tiles;
+
+    // the LDS-DMA kernels: 16-bit storage, live taps tap_id[0] + 0, 1, 2, ... (the blocks compute their tap from the first), 32-bit pixel
+    // index and 32-bit byte offsets into both tensors
+    bool prefix = true;
+    for (int i = 0; i < n; ++i) prefix = prefix && a.tap_id[i] == a.tap_id[0] + i;
+    const bool off32 = ((int64_t)a.B * a.H * a.W + 64) * a.x_ps * 2 < (1ll << 31) && ((int64_t)a.B * a.Ho * a.Wo + 64) * a.y_ps * 2 < (1ll << 31);
+    const bool dma_ok = d->dtype == HESIC_H16 && prefix && a.Q < (1ll << 31) && off32;
     // wgrad_row_kernel: 5x5, stride 2, pad 2, every tap live, 64-pixel stages that stay inside one image row, and enough pixels that a
     // K slice per CU outweighs the 5-tap partial tiles every block leaves (HESIC_WGRAD_ROW=0: off, A/B; HESIC_WGRAD_ROW_MINQ)
-    {
-        const char* e = getenv("HESIC_WGRAD_ROW");
-        const char* mq = getenv("HESIC_WGRAD_ROW_MINQ");
-        const int64_t minq = mq ? atoll(mq) : 100000;
-        const bool off32 = ((int64_t)a.B * a.H * a.W + 64) * a.x_ps * 2 < (1ll << 31) && ((int64_t)a.B * a.Ho * a.Wo + 64) * a.y_ps * 2 < (1ll << 31);
-        a.rowk = (!e || atoi(e) != 0) && d->dtype == HESIC_H16 && d->KH == 5 && d->KW == 5 && d->stride == 2 && d->pad == 2 && n == 25 && !d->in_abs &&
-                 a.QW % 64 == 0 && a.Q >= minq && a.Q < (1ll << 31) && off32;
-    }
-    if (a.rowk) {
+    const char* e = getenv("HESIC_WGRAD_ROW");
+    const char* mq = getenv("HESIC_WGRAD_ROW_MINQ");
+    const int64_t minq = mq ? atoll(mq) : 100000;
+    const bool row = (!e || atoi(e) != 0) && dma_ok && d->KH == 5 && d->KW == 5 && d->stride == 2 && d->pad == 2 && n == 25 && !d->in_abs &&
+                     a.QW % 64 == 0 && a.Q >= minq;
+    if (row) {
         const int target = 256;                 // one block per CU (150 KB of LDS)
         const int64_t stages = a.Q / 64;
         int64_t s = target / (5 * a.co_tiles * a.ci_tiles);
@@ -2307,225 +2250,181 @@ int fill_args(const hesic_conv_desc* d, WgArgs& a, int nsplit_override = 0) {
         const int64_t per = (stages + s - 1) / s;
         a.chunk = per * 64;
         a.nsplit = (int)((stages + per - 1) / per);
-        return 0;
+        a.rowk = 1;
+        p.route = WG_ROW;
+        p.blocks = (int64_t)5 * a.co_tiles * a.ci_tiles * a.nsplit;
+        p.nsplit_shared = a.nsplit;
+    } else {
+        set_slices(a, nsplit_override > 0 ? nsplit_override : pick_splits(a.Q, bk, tiles), bk);
+        p.route = dma_ok ? WG_TR : WG_VALU;
+        p.blocks = (int64_t)tiles * a.nsplit;
+        p.nsplit_shared = a.nsplit;
+        if (dma_ok) {                           // only the shared-grid kernel's layers take another count
+            WgArgs s = a;
+            set_slices(s, pick_splits(a.Q, bk, tiles, true), bk);
+            p.nsplit_shared = s.nsplit;
+        }
     }
-    a.nsplit = nsplit_override > 0 ? nsplit_override : pick_splits(a.Q, bk, n * a.co_tiles * a.ci_tiles);
-    a.chunk = ((a.Q + a.nsplit - 1) / a.nsplit + bk - 1) / bk * bk;
-    a.nsplit = (int)((a.Q + a.chunk - 1) / a.chunk);
-    return 0;
+    p.part_bytes = (int64_t)a.nsplit * n * d->Cout * d->Cin * 4;
+    p.bias_bytes = (int64_t)a.nsplit * 4 * d->Cout * 4;
+
+    // who sums dY's columns: the DMA kernels' blocks of the taps that together read every dY pixel once, where such a tap set exists
+    if (dma_ok && n >= 1) {
+        if (!d->transposed) { a.nb_taps = 1; a.b_tap[0] = 0; }
+        // the tap set {pad + r : r < stride} covers dY only up to H * stride: other geometries (stride > 2, or an output larger than
+        // H * stride, e.g. k = 4, p = 0, s = 2) take the column-sum blocks -- and b_tap holds stride^2 <= 4 entries
+        else if (!(d->tap_mask_lo || d->stride > 2 || d->stride < 1 || d->pad + d->stride > d->KH || d->pad + d->stride > d->KW ||
+                   d->Ho > d->H * d->stride || d->Wo > d->W * d->stride))
+            for (int ry = 0; ry < d->stride; ++ry)
+                for (int rx = 0; rx < d->stride; ++rx) a.b_tap[a.nb_taps++] = (int8_t)((d->pad + ry) * d->KW + d->pad + rx);
+    }
+    p.bias_in_gemm = a.nb_taps > 0;
+
+    FinishArgs& f = p.fin;
+    f.nsplit = a.nsplit; f.ntaps = n; f.T_all = d->KH * d->KW; f.Cout = d->Cout; f.Cin = d->Cin; f.transposed = d->transposed;
+    memcpy(f.tap_id, a.tap_id, sizeof(f.tap_id));
+    // Blocks of 8 couts x 32 cins x a group of taps.  Measured and dropped: blocks of 8 couts x 128 cins x one tap that read whole 512-byte rows
+    // and write their four sums straight to the PyTorch layout were SLOWER on the training step (same box, alternating: 9.534 / 9.539 ms with
+    // them, 9.350 / 9.352 without): the tap-strided 4-byte writes cost more than the wider reads save -- the 8 x 32 x taps tiles turn a tile
+    // round in LDS and write runs along the destination's fastest index.  So was a workspace with the slices of a (tap, cout) row next to each
+    // other: neutral (9.579 / 9.583 ms with it, 9.586 / 9.596 without; round 6, two alternating runs each: this layout + this finishing pass
+    // 8.887 / 8.897; slices adjacent 8.895 / 8.892; the 512-byte-wide pass 9.037 / 9.049; both 9.027 / 9.042) -- the finishing pass still reads
+    // 128-byte pieces, and its layout is not a lever.
+    f.tiles_ci = (d->Cin + 31) / 32; f.tiles_co = (d->Cout + 7) / 8;
+    const int ftiles = f.tiles_ci * f.tiles_co;
+    int groups = (512 + ftiles - 1) / ftiles;                    // enough blocks to cover the chip twice
+    if (groups > n) groups = n;
+    if (groups < 1) groups = 1;
+    f.taps_per_group = (n + groups - 1) / groups;
+    f.tap_groups = (n + f.taps_per_group - 1) / f.taps_per_group;
+    f.n_red = ftiles * f.tap_groups;
+    p.P = (int64_t)d->B * d->Ho * d->Wo;
+    p.rpb = p.P / 256 > 0 ? (p.P + 255) / 256 : 1;               // <= 256 column-sum blocks: each ends in C atomics
+    p.n_col = p.bias_in_gemm ? 1 : (int)((p.P + p.rpb - 1) / p.rpb);      // the GEMM left the column sums: one block adds them up
+    return p;
+}
+
+#define WG_CHECK_PLAN(p, ...)                                                                  \
+    do {                                                                                       \
+        HESIC_CHECK_ARG((p).chan_ok, __VA_ARGS__ "channels must be multiples of %d", (p).ce);  \
+        HESIC_CHECK_ARG((p).taps_ok, __VA_ARGS__ "at most 25 taps");                           \
+    } while (0)
+
+// the split-K launch's arguments for one call; bias: the launch also leaves dY's column sums in the bias part (where the plan has such a tap set)
+static WgArgs wg_bind(const WgPlan& p, const void* x, const void* dy, void* ws, bool bias) {
+    WgArgs a = p.a;
+    a.x = x; a.dy = dy; a.out = (float*)ws;
+    if (bias && p.bias_in_gemm) a.bias_part = (float*)ws + p.part_bytes / 4;
+    return a;
+}
+
+// the split-K launch.  zero_me: an array the DMA kernels' block 0 clears on the way (the VALU kernel does not: false is returned)
+static bool wg_launch(const WgPlan& p, const WgArgs& a, hipStream_t st, float* zero_me = nullptr, int zero_n = 0) {
+    const dim3 g((unsigned)p.blocks);
+    if (p.route == WG_ROW) {
+        WgRowArgs R;
+        R.w = a; R.zero_me = zero_me; R.zero_n = zero_n;
+        R.dqw = make_fastdiv((uint32_t)a.QW); R.dqh = make_fastdiv((uint32_t)a.QH);
+        static bool rattr = false;
+        if (!rattr) {
+            (void)hipFuncSetAttribute((const void*)wgrad_row_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ROW_LDS);
+            (void)hipFuncSetAttribute((const void*)wgrad_row_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ROW_LDS);
+            rattr = true;
+        }
+        if (a.transposed) hipLaunchKernelGGL(wgrad_row_kernel<true>, g, dim3(512), ROW_LDS, st, R);
+        else hipLaunchKernelGGL(wgrad_row_kernel<false>, g, dim3(512), ROW_LDS, st, R);
+        return true;
+    }
+    if (p.route == WG_TR) {
+        hipLaunchKernelGGL(wgrad_tr_kernel, g, dim3(NT), TR_LDS, st, make_tr_args(a, zero_me, zero_n));
+        return true;
+    }
+    if (p.dtype == HESIC_H16) hipLaunchKernelGGL(wgrad_kernel<h16_t>, g, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL(wgrad_kernel<float>, g, dim3(NT), 0, st, a);
+    return false;
+}
+
+// the finishing pass's arguments for one call
+static FinishArgs finish_bind(const WgPlan& p, const void* ws, float* dw, int accumulate, bool with_bias) {
+    FinishArgs f = p.fin;
+    f.ws = (const float*)ws; f.dw = dw;
+    f.accumulate = (accumulate || f.ntaps < f.T_all) ? 1 : 0;      // the dead taps of a masked conv were zero-filled: the live ones add into them
+    if (with_bias && p.bias_in_gemm) {
+        f.bias_part = (const float*)ws + p.part_bytes / 4; f.nb_parts = p.a.nsplit * p.a.nb_taps; f.accumulate_bias = accumulate;
+    }
+    return f;
 }
 
 }  // namespace
 
-// ---- bias gradient through wgrad_tr_kernel (see WgArgs::bias_part): room for [nsplit][stride^2][Cout] floats behind the K-slice partials
-static int64_t bias_part_bytes(const hesic_conv_desc* d, const WgArgs& a) { return (int64_t)a.nsplit * 4 * d->Cout * 4; }
-// the launch conditions of wgrad_tr_kernel, shared by the callers that have to agree on who produced the bias sums
-static bool wgrad_tr_path(const hesic_conv_desc* d, const WgArgs& a) {
-    bool prefix = true;                               // live taps must be tap_id[0] + 0,1,2,... for the fast kernel
-    for (int i = 0; i < a.ntaps; ++i) prefix = prefix && a.tap_id[i] == a.tap_id[0] + i;
-    const bool off32 = ((int64_t)a.B * a.H * a.W + 64) * a.x_ps * 2 < (1ll << 31) && ((int64_t)a.B * a.Ho * a.Wo + 64) * a.y_ps * 2 < (1ll << 31);
-    return d->dtype == HESIC_H16 && prefix && a.Q < (1ll << 31) && off32;
-}
 extern "C" int hesic_conv2d_wgrad_nsplit(const hesic_conv_desc* d, int batched) {
-    if (!d || d->KH * d->KW > 25) return 0;
-    WgArgs a;
-    fill_args(d, a);
-    constexpr int ring = WGRAD_RING_DEFAULT;
-    if (a.rowk || !batched || ring != 0 || !wgrad_tr_path(d, a)) return a.nsplit;      // only the shared-grid kernel's layers take another count
-    const int bk = d->dtype == HESIC_H16 ? WC<h16_t>::BK : WC<float>::BK;
-    fill_args(d, a, pick_splits(a.Q, bk, a.ntaps * a.co_tiles * a.ci_tiles, true));
-    return a.nsplit;
+    if (!d) return 0;
+    const WgPlan p = wgrad_plan(d, 0);
+    return !p.taps_ok ? 0 : batched ? p.nsplit_shared : p.a.nsplit;
 }
 
-// point a.bias_part behind the weight partials in ws and list the taps whose blocks sum dY's columns; false: no such tap set
-static bool setup_bias_part(const hesic_conv_desc* d, WgArgs& a, void* ws) {
-    constexpr bool off = false;      // A/B switch: the separate column-sum blocks of rounds 1-3
-    a.bias_part = nullptr; a.nb_taps = 0;
-    if (off || !wgrad_tr_path(d, a) || a.ntaps < 1) return false;
-    if (!d->transposed) { a.nb_taps = 1; a.b_tap[0] = 0; }
-    else {
-        // the tap set {pad + r : r < stride} covers dY only up to H * stride: other geometries (stride > 2, or an output larger than
-        // H * stride, e.g. k = 4, p = 0, s = 2) take the column-sum blocks -- and b_tap holds stride^2 <= 4 entries
-        if (d->tap_mask_lo || d->stride > 2 || d->stride < 1 || d->pad + d->stride > d->KH || d->pad + d->stride > d->KW ||
-            d->Ho > d->H * d->stride || d->Wo > d->W * d->stride) return false;
-        for (int ry = 0; ry < d->stride; ++ry)
-            for (int rx = 0; rx < d->stride; ++rx) a.b_tap[a.nb_taps++] = (int8_t)((d->pad + ry) * d->KW + d->pad + rx);
-        if (a.nb_taps > 4) { a.nb_taps = 0; return false; }
-    }
-    a.bias_part = (float*)ws + (int64_t)a.nsplit * a.ntaps * d->Cout * d->Cin;
-    return true;
-}
-
-extern "C" int64_t hesic_conv2d_wgrad_ws_bytes(const hesic_conv_desc* d) {
-    if (!d || d->KH * d->KW > 25) return 0;
-    WgArgs a;
-    fill_args(d, a);
-    return (int64_t)a.nsplit * a.ntaps * d->Cout * d->Cin * 4 + bias_part_bytes(d, a);
-}
+extern "C" int64_t hesic_conv2d_wgrad_ws_bytes(const hesic_conv_desc* d) { return hesic_conv2d_wgrad_ws_bytes_n(d, 0); }
 
 extern "C" int64_t hesic_conv2d_wgrad_ws_bytes_n(const hesic_conv_desc* d, int nsplit) {
-    if (!d || d->KH * d->KW > 25) return 0;
-    WgArgs a;
-    fill_args(d, a, nsplit);
-    return (int64_t)a.nsplit * a.ntaps * d->Cout * d->Cin * 4 + bias_part_bytes(d, a);
+    if (!d) return 0;
+    const WgPlan p = wgrad_plan(d, nsplit);
+    return p.taps_ok ? p.part_bytes + p.bias_bytes : 0;
 }
 
 extern "C" int hesic_conv2d_wgrad(const hesic_conv_desc* d, const void* x, const void* dy, float* dw_packed, float* dbias,
                                   void* ws, int64_t ws_bytes, void* stream) {
     HESIC_CHECK_ARG(d && x && dy && dw_packed, "conv2d_wgrad: null pointer");
-    const int ce = d->dtype == HESIC_H16 ? 8 : 4;
-    HESIC_CHECK_ARG(d->Cin % ce == 0 && d->Cout % ce == 0 && d->x_pix_stride % ce == 0 && d->y_pix_stride % ce == 0 &&
-                        d->x_c_off % ce == 0 && d->y_c_off % ce == 0,
-                    "conv2d_wgrad: channels must be multiples of %d", ce);
-    HESIC_CHECK_ARG(d->KH * d->KW <= 25, "conv2d_wgrad: at most 25 taps");
-    WgArgs a;
-    fill_args(d, a);
-    const int64_t need = (int64_t)a.nsplit * a.ntaps * d->Cout * d->Cin * 4;
-    HESIC_CHECK_ARG(ws && ws_bytes >= need, "conv2d_wgrad: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)need);
+    const WgPlan p = wgrad_plan(d, 0);
+    WG_CHECK_PLAN(p, "conv2d_wgrad: ");
+    // This entry writes the PACKED layout [tap][Cout][Cin] (hesic_unpack_conv_wgrad follows), so it has reduce kernels of its own, and those
+    // sum dY's columns themselves: the bias part of the workspace is never touched and is not asked for here, although
+    // hesic_conv2d_wgrad_ws_bytes, the one size query of this entry and of hesic_conv2d_wgrad_direct, reports it.
+    HESIC_CHECK_ARG(ws && ws_bytes >= p.part_bytes, "conv2d_wgrad: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)p.part_bytes);
     hipStream_t st = (hipStream_t)stream;
-    a.x = x; a.dy = dy; a.out = (float*)ws;
-    const int64_t blocks = (int64_t)a.ntaps * a.co_tiles * a.ci_tiles * a.nsplit;
-    constexpr bool wg_legacy = false;
-    bool prefix = true;                               // live taps must be tap_id[0] + 0,1,2,... for the fast kernel
-    for (int i = 0; i < a.ntaps; ++i) prefix = prefix && a.tap_id[i] == a.tap_id[0] + i;
-    const bool off32 = ((int64_t)a.B * a.H * a.W + 64) * a.x_ps * 2 < (1ll << 31) && ((int64_t)a.B * a.Ho * a.Wo + 64) * a.y_ps * 2 < (1ll << 31);
-    bool db_zeroed = false;
-    if (d->dtype == HESIC_H16 && !wg_legacy && prefix && a.Q < (1ll << 31) && off32) {
-        launch_wgrad_tr(a, blocks, st, dbias, dbias ? d->Cout : 0);
-        db_zeroed = dbias != nullptr;
-    }
-    else if (d->dtype == HESIC_H16) hipLaunchKernelGGL(wgrad_kernel<h16_t>, dim3((unsigned)blocks), dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL(wgrad_kernel<float>, dim3((unsigned)blocks), dim3(NT), 0, st, a);
+    const WgArgs a = wg_bind(p, x, dy, ws, false);
+    const bool db_zeroed = wg_launch(p, a, st, dbias, dbias ? d->Cout : 0);
     const int64_t per_tap = (int64_t)d->Cout * d->Cin;
     if (a.ntaps < d->KH * d->KW) zero_async(dw_packed, (int64_t)d->KH * d->KW * per_tap, st);
-    constexpr bool split_launch = false;     // A/B switch for profiling
-    if (dbias && !split_launch) {
+    if (dbias) {
         if (!db_zeroed) zero_async(dbias, d->Cout, st);
-        const int64_t P = (int64_t)d->B * d->Ho * d->Wo;
-        const int64_t rpb = P / 256 > 0 ? (P + 255) / 256 : 1;      // <= 256 column-sum blocks: each ends in C atomics
-        const int n_col = (int)((P + rpb - 1) / rpb), n_red = grid_for(a.ntaps * per_tap / 4, 256);
+        const int n_col = (int)((p.P + p.rpb - 1) / p.rpb), n_red = grid_for(a.ntaps * per_tap / 4, 256);
         if (d->dtype == HESIC_H16)
             hipLaunchKernelGGL(wgrad_reduce_colsum_kernel<h16_t>, dim3((unsigned)(n_red + n_col)), dim3(256), 0, st, (const float*)ws, dw_packed,
-                               a.nsplit, a.ntaps, per_tap, a, n_red, (const h16_t*)dy, dbias, P, rpb);
+                               a.nsplit, a.ntaps, per_tap, a, n_red, (const h16_t*)dy, dbias, p.P, p.rpb);
         else
             hipLaunchKernelGGL(wgrad_reduce_colsum_kernel<float>, dim3((unsigned)(n_red + n_col)), dim3(256), 0, st, (const float*)ws, dw_packed,
-                               a.nsplit, a.ntaps, per_tap, a, n_red, (const float*)dy, dbias, P, rpb);
-        HESIC_LAUNCH_RETURN("conv2d_wgrad");
-    }
-    if (a.nsplit >= 32 && a.ntaps * per_tap / 64 < 4096)
+                               a.nsplit, a.ntaps, per_tap, a, n_red, (const float*)dy, dbias, p.P, p.rpb);
+    } else if (a.nsplit >= 32 && a.ntaps * per_tap / 64 < 4096)
         hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((a.ntaps * per_tap / 4 + 15) / 16)), dim3(256), 0, st, (const float*)ws, dw_packed,
                            a.nsplit, a.ntaps, per_tap, a);
     else
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(a.ntaps * per_tap / 4, 256)), dim3(256), 0, st, (const float*)ws, dw_packed,
                            a.nsplit, a.ntaps, per_tap, a);
-    if (dbias) {
-        zero_async(dbias, d->Cout, st);
-        const int64_t P = (int64_t)d->B * d->Ho * d->Wo;
-        const int64_t rpb = P / 256 > 0 ? (P + 255) / 256 : 1;      // <= 256 blocks: every block ends in C atomics
-        const unsigned g = (unsigned)((P + rpb - 1) / rpb);
-        if (d->dtype == HESIC_H16)
-            hipLaunchKernelGGL(colsum_kernel<h16_t>, dim3(g), dim3(256), 0, st, (const h16_t*)dy, dbias, P, d->Cout, d->y_pix_stride, d->y_c_off, rpb);
-        else
-            hipLaunchKernelGGL(colsum_kernel<float>, dim3(g), dim3(256), 0, st, (const float*)dy, dbias, P, d->Cout, d->y_pix_stride, d->y_c_off, rpb);
-    }
     HESIC_LAUNCH_RETURN("conv2d_wgrad");
 }
-
-// finishing pass of one layer: the block layout of wgrad_finish_kernel; returns the number of bias column-sum blocks behind the n_red reduce blocks
-static int make_finish(const hesic_conv_desc* d, const WgArgs& a, const void* ws, float* dw, int accumulate, bool with_bias, FinishArgs& f,
-                       int64_t& P, int64_t& rpb, int accumulate_bias = 1) {
-    const int T_all = d->KH * d->KW;
-    memset(&f, 0, sizeof(f));
-    f.ws = (const float*)ws; f.dw = dw; f.nsplit = a.nsplit; f.ntaps = a.ntaps; f.T_all = T_all; f.Cout = d->Cout; f.Cin = d->Cin;
-    f.transposed = d->transposed; f.accumulate = (accumulate || a.ntaps < T_all) ? 1 : 0;
-    f.ws_layout = a.ws_layout;
-    memcpy(f.tap_id, a.tap_id, sizeof(f.tap_id));
-    // A/B switch, OFF: HESIC_WGRAD_FINISH_WIDE=1 = blocks of 8 couts x 128 cins x one tap that read whole 512-byte rows and write their four
-    // sums straight to the PyTorch layout.  Measured SLOWER on the training step (same box, alternating: 9.534 / 9.539 ms with it, 9.350 /
-    // 9.352 without): the tap-strided 4-byte writes cost more than the wider reads save -- the 8 x 32 x taps tiles turn a tile round in LDS
-    // and write runs along the destination's fastest index.
-    constexpr bool wide_on = false;
-    if (wide_on && (d->Cin & 3) == 0) {
-        f.wide = 1;
-        f.tiles_ci = (d->Cin + 127) / 128; f.tiles_co = (d->Cout + 7) / 8;
-        f.taps_per_group = 1; f.tap_groups = a.ntaps;
-        f.n_red = f.tiles_ci * f.tiles_co * a.ntaps;
-        P = (int64_t)d->B * d->Ho * d->Wo;
-        rpb = P / 256 > 0 ? (P + 255) / 256 : 1;
-        if (with_bias && a.bias_part) {
-            f.bias_part = a.bias_part; f.nb_parts = a.nsplit * a.nb_taps; f.accumulate_bias = accumulate_bias;
-            return 1;
-        }
-        return with_bias ? (int)((P + rpb - 1) / rpb) : 0;
-    }
-    f.tiles_ci = (d->Cin + 31) / 32; f.tiles_co = (d->Cout + 7) / 8;
-    const int tiles = f.tiles_ci * f.tiles_co;
-    int groups = (512 + tiles - 1) / tiles;                      // enough blocks to cover the chip twice
-    if (groups > a.ntaps) groups = a.ntaps;
-    if (groups < 1) groups = 1;
-    f.taps_per_group = (a.ntaps + groups - 1) / groups;
-    f.tap_groups = (a.ntaps + f.taps_per_group - 1) / f.taps_per_group;
-    f.n_red = tiles * f.tap_groups;
-    P = (int64_t)d->B * d->Ho * d->Wo;
-    rpb = P / 256 > 0 ? (P + 255) / 256 : 1;
-    if (with_bias && a.bias_part) {                   // wgrad_tr_kernel left the column sums: one block adds them up
-        f.bias_part = a.bias_part; f.nb_parts = a.nsplit * a.nb_taps; f.accumulate_bias = accumulate_bias;
-        return 1;
-    }
-    return with_bias ? (int)((P + rpb - 1) / rpb) : 0;
-}
-
-// workspace layout of the direct / partial / finish_batched route (WgArgs::ws_layout).  A/B switch, OFF: HESIC_WGRAD_WS_LAYOUT=1 puts the
-// slices of a (tap, cout) row next to each other.  Measured neutral on the training step (same box, alternating runs: 9.579 / 9.583 ms
-// with it, 9.586 / 9.596 without): the finishing pass still reads 128-byte pieces (its 8 cout x 32 cin tiles) -- contiguity across
-// slices alone does not raise its 2.9 TB/s; a 512-byte-wide tile would be the next step.
-// (round 6, same box, two alternating runs each, ms per training step: this layout + the narrow finishing pass 8.887 / 8.897; slices of a (tap, cout) row
-// adjacent 8.895 / 8.892; the 512-byte-wide finishing pass 9.037 / 9.049; both 9.027 / 9.042 -- the finishing pass's layout is not a lever)
-static int direct_ws_layout() { return 0; }
 
 // partial_only (hesic_conv2d_wgrad_partial): stop after the split-K MFMA launch
 static int wgrad_direct_launch(const hesic_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias, int accumulate, void* ws,
                                int64_t ws_bytes, bool partial_only, void* stream) {
     HESIC_CHECK_ARG(d && x && dy && (dw || partial_only), "conv2d_wgrad_direct: null pointer");
-    const int ce = d->dtype == HESIC_H16 ? 8 : 4;
-    HESIC_CHECK_ARG(d->Cin % ce == 0 && d->Cout % ce == 0 && d->x_pix_stride % ce == 0 && d->y_pix_stride % ce == 0 &&
-                        d->x_c_off % ce == 0 && d->y_c_off % ce == 0,
-                    "conv2d_wgrad_direct: channels must be multiples of %d", ce);
-    HESIC_CHECK_ARG(d->KH * d->KW <= 25, "conv2d_wgrad_direct: at most 25 taps");
-    WgArgs a;
-    fill_args(d, a);
-    a.ws_layout = direct_ws_layout();
-    const int64_t need = (int64_t)a.nsplit * a.ntaps * d->Cout * d->Cin * 4 + bias_part_bytes(d, a);
+    const WgPlan p = wgrad_plan(d, 0);
+    WG_CHECK_PLAN(p, "conv2d_wgrad_direct: ");
+    const int64_t need = p.part_bytes + p.bias_bytes;
     HESIC_CHECK_ARG(ws && ws_bytes >= need, "conv2d_wgrad_direct: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)need);
     hipStream_t st = (hipStream_t)stream;
-    a.x = x; a.dy = dy; a.out = (float*)ws;
-    const int64_t blocks = (int64_t)a.ntaps * a.co_tiles * a.ci_tiles * a.nsplit;
-    constexpr bool wlog = false;     // diagnostic: one line per weight-gradient launch (geometry, K slices)
-    if (wlog)
-        fprintf(stderr, "[hesic] wgrad %s B=%d %dx%d Cin=%d -> %dx%d Cout=%d k=%d s=%d taps=%d Q=%lld nsplit=%d chunk=%lld blocks=%lld row=%d\n",
-                d->transposed ? "deconv" : "conv", d->B, d->H, d->W, d->Cin, d->Ho, d->Wo, d->Cout, d->KH, d->stride, a.ntaps, (long long)a.Q, a.nsplit,
-                (long long)a.chunk, (long long)(a.rowk ? 5 * a.co_tiles * a.ci_tiles * a.nsplit : blocks), a.rowk);
-    const bool bias_in_tr = setup_bias_part(d, a, ws);               // always (the partial-only call has no dbias, its finishing call does)
-    float* zero_me = (dbias && !accumulate && !bias_in_tr) ? dbias : nullptr;       // accumulate: the caller's buffer already holds a value
-    bool db_zeroed = false;
-    if (wgrad_tr_path(d, a)) {
-        launch_wgrad_tr(a, blocks, st, zero_me, zero_me ? d->Cout : 0);
-        db_zeroed = true;
-    } else if (d->dtype == HESIC_H16) hipLaunchKernelGGL(wgrad_kernel<h16_t>, dim3((unsigned)blocks), dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL(wgrad_kernel<float>, dim3((unsigned)blocks), dim3(NT), 0, st, a);
+    const WgArgs a = wg_bind(p, x, dy, ws, true);                    // always (the partial-only call has no dbias, its finishing call does)
+    float* zero_me = (dbias && !accumulate && !p.bias_in_gemm) ? dbias : nullptr;       // accumulate: the caller's buffer already holds a value
+    const bool db_zeroed = wg_launch(p, a, st, zero_me, zero_me ? d->Cout : 0);
     if (partial_only) HESIC_LAUNCH_RETURN("conv2d_wgrad_partial");
     if (zero_me && !db_zeroed) zero_async(dbias, d->Cout, st);
     const int T_all = d->KH * d->KW;
     if (a.ntaps < T_all && !accumulate) zero_async(dw, (int64_t)T_all * d->Cout * d->Cin, st);      // dead taps of a masked conv
-    FinishArgs f;
-    int64_t P, rpb;
-    const int n_col = make_finish(d, a, ws, dw, accumulate, dbias != nullptr, f, P, rpb, accumulate);
+    const FinishArgs f = finish_bind(p, ws, dw, accumulate, dbias != nullptr);
+    const dim3 g((unsigned)(f.n_red + (dbias ? p.n_col : 0)));
     if (d->dtype == HESIC_H16)
-        hipLaunchKernelGGL(wgrad_finish_kernel<h16_t>, dim3((unsigned)(f.n_red + n_col)), dim3(256), 0, st, f, (const h16_t*)dy, dbias, P,
-                           d->y_pix_stride, d->y_c_off, rpb);
+        hipLaunchKernelGGL(wgrad_finish_kernel<h16_t>, g, dim3(256), 0, st, f, (const h16_t*)dy, dbias, p.P, d->y_pix_stride, d->y_c_off, p.rpb);
     else
-        hipLaunchKernelGGL(wgrad_finish_kernel<float>, dim3((unsigned)(f.n_red + n_col)), dim3(256), 0, st, f, (const float*)dy, dbias, P,
-                           d->y_pix_stride, d->y_c_off, rpb);
+        hipLaunchKernelGGL(wgrad_finish_kernel<float>, g, dim3(256), 0, st, f, (const float*)dy, dbias, p.P, d->y_pix_stride, d->y_c_off, p.rpb);
     HESIC_LAUNCH_RETURN("conv2d_wgrad_direct");
 }
 
@@ -2566,9 +2465,8 @@ extern "C" int64_t hesic_sconv2d_wgrad_ws_bytes(const hesic_sconv_desc* d) {
     if (Q >= (1ll << 22)) return 0;
     hesic_conv_desc g;
     nw_gemm_desc(Q, g);
-    WgArgs a;
-    fill_args(&g, a);
-    return (Q * 96 * 2 + 255) / 256 * 256 + (int64_t)a.nsplit * 128 * 96 * 4 + (int64_t)a.nsplit * 128 * 4;      // im2col matrix, weight partials, bias partials
+    const WgPlan p = wgrad_plan(&g, 0);
+    return (Q * 96 * 2 + 255) / 256 * 256 + p.part_bytes + (int64_t)p.a.nsplit * 128 * 4;      // im2col matrix, weight partials, bias partials (one tap)
 }
 
 extern "C" int hesic_sconv2d_wgrad(const hesic_sconv_desc* d, const void* x, const void* dy, float* dw, float* dbias, void* ws,
@@ -2583,11 +2481,10 @@ extern "C" int hesic_sconv2d_wgrad(const hesic_sconv_desc* d, const void* x, con
     a.ys_b = d->ys_b; a.ys_c = d->ys_c; a.ys_y = d->ys_y; a.ys_x = d->ys_x;
     hipStream_t st = (hipStream_t)stream;
     const int64_t nw = (int64_t)d->Cout * d->Cin * d->KH * d->KW;
-    constexpr bool legacy = false;
     const bool k5 = d->KH == 5 && d->KW == 5 && d->pad == 2;
     bool conv1 = false;
     const int64_t need = hesic_sconv2d_wgrad_ws_bytes(d);
-    const bool mfma_route = !legacy && need > 0 && ws && ws_bytes >= need && nw_fast_case(d, conv1);
+    const bool mfma_route = need > 0 && ws && ws_bytes >= need && nw_fast_case(d, conv1);
     if (!mfma_route) zero_async(dw, nw, st);          // the routes below accumulate with atomics; the MFMA route's finishing pass writes every element
     if (mfma_route) {
         // MFMA route: im2col of the 3-channel side, then the 1x1 weight-gradient kernel with WIDE as "dY"
@@ -2595,6 +2492,9 @@ extern "C" int hesic_sconv2d_wgrad(const hesic_sconv_desc* d, const void* x, con
         const int QH = conv1 ? d->Ho : d->H, QW = conv1 ? d->Wo : d->W, NH = conv1 ? d->H : d->Ho, NW = conv1 ? d->W : d->Wo;
         h16_t* P = (h16_t*)ws;
         float* part = (float*)((unsigned char*)ws + (Q * 96 * 2 + 255) / 256 * 256);
+        hesic_conv_desc g;
+        nw_gemm_desc(Q, g);
+        const WgPlan gp = wgrad_plan(&g, 0);                         // the one-tap GEMM over Q pixels; its slice count sized the workspace
         bool fused_done = false;
         {
             // round 5: one fused launch (wgrad_nw_fused_kernel) when the narrow image is fp32 and a 64-pixel stage stays inside one row of the
@@ -2605,16 +2505,12 @@ extern "C" int hesic_sconv2d_wgrad(const hesic_sconv_desc* d, const void* x, con
             const int64_t span = ((int64_t)(d->B - 1) * nsb0 + 2 * nsc0 + (int64_t)(NH + 2) * nsy0 + (int64_t)(NW + 140) * nsx0) * 4;
             if ((!e || atoi(e) != 0) && ndt0 == HESIC_F32 && QW % 64 == 0 && Q < (1ll << 23) && nsb0 >= 0 && nsc0 >= 0 && nsy0 >= 0 && nsx0 >= 0 &&
                 span < (1ll << 31)) {
-                hesic_conv_desc g0;
-                nw_gemm_desc(Q, g0);
-                WgArgs a0;
-                fill_args(&g0, a0);                                   // the slice count the workspace was sized for
                 NwArgs n;
                 n.wide = conv1 ? dy : x; n.narrow = (const float*)(conv1 ? x : dy); n.part = part;
                 n.ns_b = nsb0; n.ns_c = nsc0; n.ns_y = nsy0; n.ns_x = nsx0;
                 n.QH = QH; n.QW = QW; n.NH = NH; n.NW = NW; n.Q = Q;
                 const int64_t stages = Q / 64;
-                int64_t ns = a0.nsplit < 256 ? a0.nsplit : 256;
+                int64_t ns = gp.a.nsplit < 256 ? gp.a.nsplit : 256;
                 if (ns > stages) ns = stages;
                 const int64_t per = (stages + ns - 1) / ns;
                 n.chunk = per * 64;
@@ -2637,11 +2533,10 @@ extern "C" int hesic_sconv2d_wgrad(const hesic_sconv_desc* d, const void* x, con
             }
         }
         if (!fused_done) {
-        constexpr bool chunk_form = false;      // A/B switch: the thread-per-chunk kernel of rounds 1-3
         const void* nimg = conv1 ? x : dy;
         const int ndt = conv1 ? d->x_dtype : d->y_dtype;
         const int64_t nsb = conv1 ? d->xs_b : d->ys_b, nsc = conv1 ? d->xs_c : d->ys_c, nsy = conv1 ? d->xs_y : d->ys_y, nsx = conv1 ? d->xs_x : d->ys_x;
-        if (!chunk_form && Q < (1ll << 31)) {
+        if (Q < (1ll << 31)) {
             const FastDiv dqw = make_fastdiv((uint32_t)QW), dqh = make_fastdiv((uint32_t)QH);
             const dim3 grid((unsigned)((Q + 255) / 256));
             if (ndt == HESIC_H16)
@@ -2650,43 +2545,35 @@ extern "C" int hesic_sconv2d_wgrad(const hesic_sconv_desc* d, const void* x, con
                 hipLaunchKernelGGL(im2col_narrow_rows_kernel<float>, grid, dim3(256), 0, st, (const float*)nimg, nsb, nsc, nsy, nsx, P, Q, QH, QW, NH, NW, dqw, dqh);
         } else
             hipLaunchKernelGGL(im2col_narrow_kernel, dim3(grid_for(Q * 12, 256)), dim3(256), 0, st, nimg, ndt, nsb, nsc, nsy, nsx, P, d->B, QH, QW, NH, NW, 3);
-        hesic_conv_desc g;
-        nw_gemm_desc(Q, g);
-        WgArgs a2;
-        fill_args(&g, a2);
-        a2.x = P; a2.dy = conv1 ? dy : x; a2.out = part;
         // conv1: the GEMM's "dY" operand IS dy (128 channels, 134 MB at B=8 512^2) -- its column sums (the bias gradient) come out of the same
-        // launch (WgArgs::bias_part) instead of a second pass over it
-        constexpr bool bias_colsum = false;      // A/B switch
-        float* bpart = part + (int64_t)a2.nsplit * 128 * 96;
-        if (conv1 && dbias && !bias_colsum) { a2.bias_part = bpart; a2.nb_taps = 1; a2.b_tap[0] = 0; }
-        launch_wgrad_tr(a2, (int64_t)a2.ntaps * a2.co_tiles * a2.ci_tiles * a2.nsplit, st);
+        // launch (WgArgs::bias_part, behind the weight partials) instead of a second pass over it
+        const WgArgs a2 = wg_bind(gp, P, conv1 ? dy : x, part, conv1 && dbias);
+        wg_launch(gp, a2, st);
         hipLaunchKernelGGL(nw_reduce_kernel, dim3((128 * 75 + 3) / 4), dim3(256), 0, st, (const float*)part, dw, a2.nsplit, 75);
         if (a2.bias_part) {
-            hipLaunchKernelGGL(nw_bias_reduce_kernel, dim3(1), dim3(1024), 0, st, (const float*)bpart, dbias, a2.nsplit);
+            hipLaunchKernelGGL(nw_bias_reduce_kernel, dim3(1), dim3(1024), 0, st, (const float*)a2.bias_part, dbias, a2.nsplit);
             dbias = nullptr;                          // done: skip the column-sum pass below
         }
         }
-    } else if (!legacy && k5 && d->stride == 2 && !d->transposed && d->Cin == 3 && d->Cout == 128 && d->ys_c == 1 && d->y_dtype == HESIC_H16 &&
+    } else if (k5 && d->stride == 2 && !d->transposed && d->Cin == 3 && d->Cout == 128 && d->ys_c == 1 && d->y_dtype == HESIC_H16 &&
         d->H == 2 * d->Ho && d->W == 2 * d->Wo) {
         // conv1: WIDE = dy (output grid), NARROW = x
         const int64_t tiles = (int64_t)((d->Wo + 15) / 16) * ((d->Ho + 7) / 8) * d->B;
         hipLaunchKernelGGL((sconv_wgrad_nw_kernel<3, h16_t>), dim3((unsigned)(tiles < 1024 ? tiles : 1024)), dim3(256), 0, st, (const h16_t*)dy,
                            d->ys_b, d->ys_y, d->ys_x, x, d->x_dtype, d->xs_b, d->xs_c, d->xs_y, d->xs_x, dw, d->B, d->Ho, d->Wo, d->H, d->W);
-    } else if (!legacy && k5 && d->stride == 2 && d->transposed && d->Cin == 128 && d->Cout == 3 && d->xs_c == 1 && d->x_dtype == HESIC_H16 &&
+    } else if (k5 && d->stride == 2 && d->transposed && d->Cin == 128 && d->Cout == 3 && d->xs_c == 1 && d->x_dtype == HESIC_H16 &&
                d->Ho == 2 * d->H && d->Wo == 2 * d->W) {
         // deconv4: WIDE = x (input grid), NARROW = dy
         const int64_t tiles = (int64_t)((d->W + 15) / 16) * ((d->H + 7) / 8) * d->B;
         hipLaunchKernelGGL((sconv_wgrad_nw_kernel<3, h16_t>), dim3((unsigned)(tiles < 1024 ? tiles : 1024)), dim3(256), 0, st, (const h16_t*)x,
                            d->xs_b, d->xs_y, d->xs_x, dy, d->y_dtype, d->ys_b, d->ys_c, d->ys_y, d->ys_x, dw, d->B, d->H, d->W, d->Ho, d->Wo);
-    } else if (!legacy && k5 && d->stride == 1 && d->Cin == 6 && d->Cout == 3 && d->Ho == d->H && d->Wo == d->W) {
+    } else if (k5 && d->stride == 1 && d->Cin == 6 && d->Cout == 3 && d->Ho == d->H && d->Wo == d->W) {
         const int64_t tiles = (int64_t)((d->W + 63) / 64) * ((d->H + 15) / 16) * d->B;
         const unsigned g = (unsigned)(tiles < NN_BLOCKS ? tiles : NN_BLOCKS);       // persistent blocks
         float* part = (ws && ws_bytes >= (int64_t)NN_BLOCKS * 450 * 4) ? (float*)ws : nullptr;
-        // LDS-DMA staging: fp32 on both sides, non-negative strides, 32-bit byte offsets inside one image (HESIC_NN_DMA=0: register staging, A/B)
-        constexpr bool dma_off = false;
+        // LDS-DMA staging: fp32 on both sides, non-negative strides, 32-bit byte offsets inside one image; otherwise register staging
         auto span = [&](int64_t sc, int64_t sy, int64_t sx, int C_) { return (C_ * sc + (int64_t)(d->H + 4) * sy + (int64_t)(d->W + 4) * sx) * 4; };
-        const bool dma = !dma_off && d->x_dtype == HESIC_F32 && d->y_dtype == HESIC_F32 && d->xs_c >= 0 && d->xs_y >= 0 && d->xs_x >= 0 && d->ys_c >= 0 &&
+        const bool dma = d->x_dtype == HESIC_F32 && d->y_dtype == HESIC_F32 && d->xs_c >= 0 && d->xs_y >= 0 && d->xs_x >= 0 && d->ys_c >= 0 &&
                          d->ys_y >= 0 && d->ys_x >= 0 && span(d->xs_c, d->xs_y, d->xs_x, 6) < (1ll << 31) && span(d->ys_c, d->ys_y, d->ys_x, 3) < (1ll << 31);
         if (!d->transposed) {   // A = dy (co), S = x (ci); dW[co][ci][k]
             if (dma) hipLaunchKernelGGL((sconv_wgrad_nn_kernel<3, 6, true>), dim3(g), dim3(256), 0, st, dy, d->y_dtype, d->ys_b, d->ys_c, d->ys_y, d->ys_x, x,
@@ -2725,12 +2612,12 @@ extern "C" int hesic_sconv2d_wgrad(const hesic_sconv_desc* d, const void* x, con
     HESIC_LAUNCH_RETURN("sconv2d_wgrad");
 }
 
-static int gdn_fast_desc(int64_t P, hesic_conv_desc& d) {
-    // the parameter gradients of the fast path are a 1x1 "conv" weight gradient over P pixels: dY = dn, X = x
+static void gdn_fast_desc(int64_t P, hesic_conv_desc& d) {
+    // the parameter gradients of the 128-channel path as a 1x1 "conv" weight gradient over P pixels (dY = dn, X = x): the three-launch form
+    // that ran them so is gone, its workspace is still one of the size terms hesic_gdn_backward_ws_bytes reports
     memset(&d, 0, sizeof(d));
     d.B = 1; d.H = 1; d.W = (int32_t)P; d.Cin = 128; d.Ho = 1; d.Wo = (int32_t)P; d.Cout = 128; d.KH = d.KW = 1; d.stride = 1;
     d.dtype = HESIC_H16; d.x_pix_stride = 128; d.y_pix_stride = 128;
-    return 0;
 }
 
 extern "C" int64_t hesic_gdn_backward_ws_bytes(int64_t P, int C) {
@@ -2738,9 +2625,7 @@ extern "C" int64_t hesic_gdn_backward_ws_bytes(int64_t P, int C) {
     if (C == 128 && P < (1ll << 22)) {
         hesic_conv_desc d;
         gdn_fast_desc(P, d);
-        WgArgs a;
-        fill_args(&d, a);
-        const int64_t fast = P * 128 * 2 + 256 + (int64_t)a.nsplit * 128 * 128 * 4 + (128 * 128 + 128) * 4;
+        const int64_t fast = P * 128 * 2 + 256 + wgrad_plan(&d, 0).part_bytes + (128 * 128 + 128) * 4;
         if (fast > generic) generic = fast;
         const int64_t tiles = (P + 127) / 128;
         const int64_t fused = ((tiles < 256 ? tiles : 256) + 1) * (128 * 128 + 128) * 4;       // one partial per block + the reduced gradient
@@ -2795,8 +2680,7 @@ __global__ __launch_bounds__(256) void gdn_param_finish_batched_kernel(const Gdn
 }  // namespace
 
 extern "C" int hesic_gdn_backward_partial_ok(int64_t P, int C, int dtype) {
-    constexpr bool legacy = false, split_params = false;
-    return (!legacy && !split_params && C == 128 && dtype == HESIC_H16 && P > 0 && P < (1ll << 22)) ? 1 : 0;
+    return (C == 128 && dtype == HESIC_H16 && P > 0 && P < (1ll << 22)) ? 1 : 0;
 }
 
 // accumulate (hesic_gdn_backward_acc): add into dbeta / dgamma; partial_only (hesic_gdn_backward_partial): stop behind gdn128_bwd_kernel
@@ -2805,70 +2689,29 @@ static int gdn_backward_launch(const void* x, const void* dy, const float* beta,
     HESIC_CHECK_ARG(x && dy && beta && gamma && dx && (partial_only || (dbeta && dgamma)) && ws && P > 0 && C > 0, "gdn_backward: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     const float bound = sqrtf(beta_min + kPedestal);
-    constexpr bool legacy = false;
     HESIC_CHECK_ARG(!partial_only || hesic_gdn_backward_partial_ok(P, C, dtype), "gdn_backward_partial: only the fused 128-channel 16-bit form leaves block partials");
-    if (!legacy && C == 128 && dtype == HESIC_H16 && P < (1ll << 22)) {
-        hesic_conv_desc d;
-        gdn_fast_desc(P, d);
-        WgArgs a;
-        fill_args(&d, a);
-        unsigned char* base = (unsigned char*)ws;
-        h16_t* dn = (h16_t*)base;
-        int64_t off = (P * 128 * 2 + 255) / 256 * 256;
-        void* wws = base + off;
-        const int64_t wws_bytes = (int64_t)a.nsplit * 128 * 128 * 4;
-        off += wws_bytes;
-        float* dgp = (float*)(base + off);
-        float* dbp = dgp + 128 * 128;
+    if (C == 128 && dtype == HESIC_H16 && P < (1ll << 22)) {
         static bool attr = false;
         if (!attr) {
-            (void)hipFuncSetAttribute((const void*)gdn128_bwd_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 512);
-            (void)hipFuncSetAttribute((const void*)gdn128_bwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 512);
-            (void)hipFuncSetAttribute((const void*)gdn128_bwd_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 512);
-            (void)hipFuncSetAttribute((const void*)gdn128_bwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 512);
+            (void)hipFuncSetAttribute((const void*)gdn128_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 512);
+            (void)hipFuncSetAttribute((const void*)gdn128_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 512);
             attr = true;
         }
         const int64_t tiles = (P + 127) / 128;
         const int nb = (int)(tiles < 256 ? tiles : 256);
-        constexpr bool split_params = false;      // A/B switch: the three-launch form of round 2
-        if (!split_params) {
-            // one pass: dx + a (128 x 128 + 128) parameter-gradient partial per block, then the block partials summed in a fixed order
-            constexpr int NP = 128 * 128 + 128;
-            float* part = (float*)base;
-            if (inverse) hipLaunchKernelGGL((gdn128_bwd_kernel<true, true>), dim3((unsigned)nb), dim3(256), 131072 + 512, st, (const h16_t*)x, (const h16_t*)dy, beta, gamma,
-                                            (h16_t*)dx, (h16_t*)nullptr, part, P, bound);
-            else hipLaunchKernelGGL((gdn128_bwd_kernel<true, false>), dim3((unsigned)nb), dim3(256), 131072 + 512, st, (const h16_t*)x, (const h16_t*)dy, beta, gamma,
-                                    (h16_t*)dx, (h16_t*)nullptr, part, P, bound);
-            {
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) { hesic_set_error("gdn_backward: %s", hipGetErrorString(e)); return (int)e; }
-            }
-            if (partial_only) HESIC_LAUNCH_RETURN("gdn_backward_partial");
-            hipLaunchKernelGGL(gdn_param_finish_kernel, dim3((unsigned)(NP / 64)), dim3(256), 0, st, (const float*)part, nb, beta, gamma, dgamma, dbeta, bound, accumulate);
-            HESIC_LAUNCH_RETURN("gdn_backward");
-        }
-        if (inverse) hipLaunchKernelGGL((gdn128_bwd_kernel<false, true>), dim3((unsigned)nb), dim3(256), 131072 + 512, st, (const h16_t*)x,
-                                        (const h16_t*)dy, beta, gamma, (h16_t*)dx, dn, (float*)nullptr, P, bound);
-        else hipLaunchKernelGGL((gdn128_bwd_kernel<false, false>), dim3((unsigned)nb), dim3(256), 131072 + 512, st, (const h16_t*)x,
-                                (const h16_t*)dy, beta, gamma, (h16_t*)dx, dn, (float*)nullptr, P, bound);
+        // one pass: dx + a (128 x 128 + 128) parameter-gradient partial per block, then the block partials summed in a fixed order
+        constexpr int NP = 128 * 128 + 128;
+        float* part = (float*)ws;
+        if (inverse) hipLaunchKernelGGL(gdn128_bwd_kernel<true>, dim3((unsigned)nb), dim3(256), 131072 + 512, st, (const h16_t*)x, (const h16_t*)dy, beta, gamma,
+                                        (h16_t*)dx, (h16_t*)nullptr, part, P, bound);
+        else hipLaunchKernelGGL(gdn128_bwd_kernel<false>, dim3((unsigned)nb), dim3(256), 131072 + 512, st, (const h16_t*)x, (const h16_t*)dy, beta, gamma,
+                                (h16_t*)dx, (h16_t*)nullptr, part, P, bound);
         {
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) { hesic_set_error("gdn_backward: %s", hipGetErrorString(e)); return (int)e; }
         }
-        // dgamma'[i][j] = sum_p dn[p][i] x[p][j]^2 ; dbeta'[i] = sum_p dn[p][i]
-        // (same kernels as hesic_conv2d_wgrad, with the X operand squared on load)
-        a.x = x; a.dy = dn; a.out = (float*)wws; a.in_sq = 1;
-        const int64_t blocks = (int64_t)a.ntaps * a.co_tiles * a.ci_tiles * a.nsplit;
-        constexpr bool wg_legacy = false;
-        if (wg_legacy) hipLaunchKernelGGL(wgrad_kernel<h16_t>, dim3((unsigned)blocks), dim3(NT), 0, st, a);
-        else launch_wgrad_tr(a, blocks, st, dbp, 128);
-        if (wg_legacy) zero_async(dbp, 128, st);
-        const int64_t rpb = P / 256 > 0 ? (P + 255) / 256 : 1;      // <= 256 column-sum blocks: every block ends in C atomics
-        // K-slice reduce (slice-parallel form: this 1-tap problem is cut into up to 256 slices) + column sums of dn, one launch
-        const int n_red = 128 * 128 / 64, n_col = (int)((P + rpb - 1) / rpb);
-        hipLaunchKernelGGL(wgrad_reduce_wide_colsum_kernel<h16_t>, dim3((unsigned)(n_red + n_col)), dim3(256), 0, st, (const float*)wws, dgp, a.nsplit, 1,
-                           (int64_t)128 * 128, a, n_red, (const h16_t*)dn, dbp, P, 128, 128, 0, rpb);
-        hipLaunchKernelGGL(gdn_bwd_chain_kernel, dim3(64), dim3(256), 0, st, beta, gamma, dgp, dbp, dgamma, dbeta, C, bound, accumulate);
+        if (partial_only) HESIC_LAUNCH_RETURN("gdn_backward_partial");
+        hipLaunchKernelGGL(gdn_param_finish_kernel, dim3((unsigned)(NP / 64)), dim3(256), 0, st, (const float*)part, nb, beta, gamma, dgamma, dbeta, bound, accumulate);
         HESIC_LAUNCH_RETURN("gdn_backward");
     }
     float* dn = (float*)ws;
@@ -2876,8 +2719,7 @@ static int gdn_backward_launch(const void* x, const void* dy, const float* beta,
     float* dgp = dx0 + P * C;
     float* dbp = dgp + (int64_t)C * C;
     zero_async(dgp, (int64_t)C * C + C, st);
-    constexpr bool small_split = false;      // A/B switch: the three passes
-    if (C == 3 && !small_split) {
+    if (C == 3) {
         const dim3 g3(grid_for(P, 256 * 2, 1024));      // 128 blocks (the parameter pass's grid: few atomics) left half the CUs idle: 57.9 us
         if (dtype == HESIC_H16)
             hipLaunchKernelGGL((gdn_bwd_small_fused_kernel<3, h16_t>), g3, dim3(256), 0, st, (const h16_t*)x, (const h16_t*)dy, beta, gamma, (h16_t*)dx, dgp, dbp, P, inverse, bound);
@@ -2893,8 +2735,7 @@ static int gdn_backward_launch(const void* x, const void* dy, const float* beta,
     if (gy > P) gy = (int)P;
     const int64_t rpb = (P + gy - 1) / gy;
     gy = (int)((P + rpb - 1) / rpb);
-    if (C == 3) hipLaunchKernelGGL(gdn_bwd_param_small_kernel<3>, dim3(grid_for(P, 256 * 8, 128)), dim3(256), 0, st, x, dn, dgp, dbp, P, dtype);
-    else hipLaunchKernelGGL(gdn_bwd_param_kernel, dim3(gx, gy), dim3(256), 0, st, x, dn, dgp, dbp, P, C, dtype, rpb);
+    hipLaunchKernelGGL(gdn_bwd_param_kernel, dim3(gx, gy), dim3(256), 0, st, x, dn, dgp, dbp, P, C, dtype, rpb);
     hipLaunchKernelGGL(gdn_bwd_chain_kernel, dim3(gx), dim3(256), 0, st, beta, gamma, dgp, dbp, dgamma, dbeta, C, bound, accumulate);
     HESIC_LAUNCH_RETURN("gdn_backward");
 }
@@ -2968,37 +2809,26 @@ extern "C" int hesic_conv2d_wgrad_partial_batched(int n, const hesic_conv_desc* 
                                                   const int64_t* ws_bytes, const int32_t* nsplit, void* stream) {
     HESIC_CHECK_ARG(n >= 0 && (n == 0 || (descs && x && dy && ws && ws_bytes)), "conv2d_wgrad_partial_batched: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    constexpr int ring = WGRAD_RING_DEFAULT;
-    struct Job { WgArgs a; int64_t blocks; };
+    struct Job { WgPlan p; WgArgs a; };
     std::vector<Job> jobs;
     for (int i = 0; i < n; ++i) {
         const hesic_conv_desc* d = descs + i;
         HESIC_CHECK_ARG(x[i] && dy[i] && ws[i], "conv2d_wgrad_partial_batched: job %d: null pointer", i);
-        WgArgs a;
-        bool batched = d->KH * d->KW <= 25 && ring == 0;
-        if (batched) {
-            fill_args(d, a, nsplit ? nsplit[i] : 0);
-            a.ws_layout = direct_ws_layout();
-            batched = wgrad_tr_path(d, a) && !a.rowk;
-        }
-        if (!batched) {
+        const int named = nsplit ? nsplit[i] : 0;
+        const WgPlan p = wgrad_plan(d, named);
+        if (!p.taps_ok || p.route != WG_TR) {
             // another kernel takes this layer: it picks its own K-slice count, which a caller-named count has to agree with
-            if (nsplit && nsplit[i] > 0) {
-                WgArgs a0;
-                fill_args(d, a0);
-                HESIC_CHECK_ARG(a0.nsplit == nsplit[i], "conv2d_wgrad_partial_batched: job %d: %d K slices named, this layer's kernel takes %d", i, nsplit[i], a0.nsplit);
+            if (named > 0 && p.taps_ok) {
+                const int own = wgrad_plan(d, 0).a.nsplit;
+                HESIC_CHECK_ARG(own == named, "conv2d_wgrad_partial_batched: job %d: %d K slices named, this layer's kernel takes %d", i, named, own);
             }
             if (int rc = wgrad_direct_launch(d, x[i], dy[i], nullptr, nullptr, 1, ws[i], ws_bytes[i], true, stream)) return rc;
             continue;
         }
-        const int ce = 8;
-        HESIC_CHECK_ARG(d->Cin % ce == 0 && d->Cout % ce == 0 && d->x_pix_stride % ce == 0 && d->y_pix_stride % ce == 0 && d->x_c_off % ce == 0 &&
-                            d->y_c_off % ce == 0, "conv2d_wgrad_partial_batched: job %d: channels must be multiples of %d", i, ce);
-        const int64_t need = (int64_t)a.nsplit * a.ntaps * d->Cout * d->Cin * 4 + bias_part_bytes(d, a);
+        HESIC_CHECK_ARG(p.chan_ok, "conv2d_wgrad_partial_batched: job %d: channels must be multiples of %d", i, p.ce);
+        const int64_t need = p.part_bytes + p.bias_bytes;
         HESIC_CHECK_ARG(ws_bytes[i] >= need, "conv2d_wgrad_partial_batched: job %d: workspace too small (%lld < %lld)", i, (long long)ws_bytes[i], (long long)need);
-        a.x = x[i]; a.dy = dy[i]; a.out = (float*)ws[i];
-        setup_bias_part(d, a, ws[i]);
-        jobs.push_back(Job{a, (int64_t)a.ntaps * a.co_tiles * a.ci_tiles * a.nsplit});
+        jobs.push_back(Job{p, wg_bind(p, x[i], dy[i], ws[i], true)});
     }
     // longest K slices first: the launch ends on its shortest blocks
     std::stable_sort(jobs.begin(), jobs.end(), [](const Job& p, const Job& q) { return p.a.chunk > q.a.chunk; });
@@ -3006,14 +2836,14 @@ extern "C" int hesic_conv2d_wgrad_partial_batched(int n, const hesic_conv_desc* 
         WgTrBatch B;
         memset(&B, 0, sizeof(B));
         B.n = (int)(jobs.size() - j0 < (size_t)WB_MAX ? jobs.size() - j0 : WB_MAX);
+        if (B.n == 1) { wg_launch(jobs[j0].p, jobs[j0].a, st); continue; }
         for (int j = 0; j < B.n; ++j) {
             const Job& J = jobs[j0 + j];
             B.job[j] = make_tr_args(J.a, nullptr, 0);
-            B.blocks[j] = (int)J.blocks;
-            B.start[j + 1] = B.start[j] + (int)((J.blocks + 7) / 8 * 8);
+            B.blocks[j] = (int)J.p.blocks;
+            B.start[j + 1] = B.start[j] + (int)((J.p.blocks + 7) / 8 * 8);
         }
-        if (B.n == 1) { launch_wgrad_tr(jobs[j0].a, jobs[j0].blocks, st); continue; }
-        hipLaunchKernelGGL((wgrad_tr_batched_kernel<64, 2>), dim3((unsigned)B.start[B.n]), dim3(NT), 2 * 64 * 512, st, B);
+        hipLaunchKernelGGL(wgrad_tr_batched_kernel, dim3((unsigned)B.start[B.n]), dim3(NT), TR_LDS, st, B);
     }
     HESIC_LAUNCH_RETURN("conv2d_wgrad_partial_batched");
 }
@@ -3027,21 +2857,18 @@ extern "C" int hesic_conv2d_wgrad_finish_batched_n(int n, const hesic_conv_desc*
         memset(&fb, 0, sizeof(fb));
         fb.n = n - j0 < FIN_NB ? n - j0 : FIN_NB;
         for (int j = 0; j < fb.n; ++j) {
-            const hesic_conv_desc* d = descs + j0 + j;
-            HESIC_CHECK_ARG(ws[j0 + j] && dy[j0 + j] && dw[j0 + j], "conv2d_wgrad_finish_batched: job %d: null pointer", j0 + j);
-            HESIC_CHECK_ARG(d->KH * d->KW <= 25 && d->dtype == descs[0].dtype, "conv2d_wgrad_finish_batched: job %d: at most 25 taps, one storage type per call", j0 + j);
-            for (int i = 0; i < j0 + j; ++i)
-                HESIC_CHECK_ARG(dw[i] != dw[j0 + j] || i < j0, "conv2d_wgrad_finish_batched: jobs %d and %d add into the same gradient in one launch", i, j0 + j);
-            WgArgs a;
-            fill_args(d, a, nsplit ? nsplit[j0 + j] : 0);
-            a.ws_layout = direct_ws_layout();
-            FinishExtra& e = fb.e[j];
-            const bool bias_in_tr = setup_bias_part(d, a, (void*)ws[j0 + j]);      // the same decision hesic_conv2d_wgrad_partial took
-            const int n_col = make_finish(d, a, ws[j0 + j], dw[j0 + j], accumulate, dbias[j0 + j] != nullptr, fb.f[j], e.P, e.rpb, accumulate);
-            if (a.ntaps < d->KH * d->KW && !accumulate) zero_async(dw[j0 + j], (int64_t)d->KH * d->KW * d->Cout * d->Cin, st);
-            if (dbias[j0 + j] && !accumulate && !bias_in_tr) zero_async(dbias[j0 + j], d->Cout, st);
-            e.dy = dy[j0 + j]; e.db = dbias[j0 + j]; e.y_ps = d->y_pix_stride; e.y_co = d->y_c_off;
-            fb.start[j + 1] = fb.start[j] + fb.f[j].n_red + n_col;
+            const int q = j0 + j;
+            const hesic_conv_desc* d = descs + q;
+            HESIC_CHECK_ARG(ws[q] && dy[q] && dw[q], "conv2d_wgrad_finish_batched: job %d: null pointer", q);
+            HESIC_CHECK_ARG(d->KH * d->KW <= 25 && d->dtype == descs[0].dtype, "conv2d_wgrad_finish_batched: job %d: at most 25 taps, one storage type per call", q);
+            for (int i = 0; i < q; ++i)
+                HESIC_CHECK_ARG(dw[i] != dw[q] || i < j0, "conv2d_wgrad_finish_batched: jobs %d and %d add into the same gradient in one launch", i, q);
+            const WgPlan p = wgrad_plan(d, nsplit ? nsplit[q] : 0);      // the plan of the launch that left the partials: same layout, same bias decision
+            fb.f[j] = finish_bind(p, ws[q], dw[q], accumulate, dbias[q] != nullptr);
+            if (p.a.ntaps < d->KH * d->KW && !accumulate) zero_async(dw[q], (int64_t)d->KH * d->KW * d->Cout * d->Cin, st);
+            if (dbias[q] && !accumulate && !p.bias_in_gemm) zero_async(dbias[q], d->Cout, st);
+            fb.e[j] = FinishExtra{dy[q], dbias[q], p.P, p.rpb, d->y_pix_stride, d->y_c_off};
+            fb.start[j + 1] = fb.start[j] + fb.f[j].n_red + (dbias[q] ? p.n_col : 0);
         }
         if (descs[0].dtype == HESIC_H16) hipLaunchKernelGGL(wgrad_finish_batched_kernel<h16_t>, dim3((unsigned)fb.start[fb.n]), dim3(256), 0, st, fb);
         else hipLaunchKernelGGL(wgrad_finish_batched_kernel<float>, dim3((unsigned)fb.start[fb.n]), dim3(256), 0, st, fb);

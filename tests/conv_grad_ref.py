@@ -217,6 +217,17 @@ DIRECT = {
     "conv1_nw_kernel": (3, 128, 5, 2, 2, 0, (2, 18, 34), {}),                      # hesic_sconv2d_wgrad without a workspace; [dw 0.017 db 0.000]
 }
 CASES = {**WIDE, **IMAGE, **DIRECT}
+# hesic_conv2d_wgrad (the packed-layout entry; weight / bias gradient only), in bf16 and in fp32.  Kept out of CASES: the CPU mutation tests
+# size their one-dropped-product argument for Q <= 4096 (see operands()).
+PACKED = {
+    "packed_c5s2":     (128, 128, 5, 2, 2, 0, (1, 16, 16), {}),                    # Q = 64: one K slice, the plain reduce; [dw 0.000 db 0.000]
+    "packed_c1_wide":  (128, 128, 1, 1, 0, 0, (1, 96, 96), {}),                    # Q = 9216, one tap: >= 32 K slices, the slice-parallel reduce; [dw 0.003 db 0.000]
+    "packed_mask12":   (128, 128, 5, 1, 2, 0, (1, 8, 8), {"mask": "A", "tap_mask": (1 << 12) - 1}),      # 13 dead taps must come back 0; [dw 0.000 db 0.000]
+}
+
+
+def case(tag):
+    return CASES[tag] if tag in CASES else PACKED[tag]
 
 
 def make_mask(kind, wshape):
@@ -230,7 +241,7 @@ def make_mask(kind, wshape):
 
 def storage(tag):
     """(y16, dx16): which of the two map outputs the 16-bit path stores in bf16."""
-    Cin, Cout = CASES[tag][0], CASES[tag][1]
+    Cin, Cout = case(tag)[0], case(tag)[1]
     return (Cout > 8), (Cin > 8)
 
 
@@ -240,7 +251,7 @@ def operands(tag, salt=0):
     [0, 1] would hide sign errors) and exact zeros where |x| < 0.25 (one in eight).  The threshold is also what lets ONE dropped product show
     at the largest pixel count of the table (Q = 4096, conv1_fused): the bar is 8 * sqrt(Q) * 2^-24 * Q * mean|x gy| = mean|x gy| / 8 there,
     and with |x| in [0.25, 2], |gy| in [0, 1] uniform, P(|x gy| < mean / 8) = 0.0615 * ln(8) / 1.75 = 7 %; with |x| down to 0 it is 14 %."""
-    Cin, Cout, k, s, p, tr, (B, H, W), opt = CASES[tag]
+    Cin, Cout, k, s, p, tr, (B, H, W), opt = case(tag)
     name = f"cgp.{tag}.{salt}."
     wshape = (Cin, Cout, k, k) if tr else (Cout, Cin, k, k)
     fan = Cin * k * k / (s * s if tr else 1)
@@ -256,7 +267,7 @@ def operands(tag, salt=0):
 
 
 def reference_of(tag, salt=0, y_saved=None):
-    Cin, Cout, k, s, p, tr, _, opt = CASES[tag]
+    Cin, Cout, k, s, p, tr, _, opt = case(tag)
     o = operands(tag, salt)
     y16, dx16 = storage(tag)
     return reference(o["x"], o["w"], o["b"], o["gy"], stride=s, pad=p, transposed=bool(tr), out_pad=opt.get("out_pad"), mask=o["mask"],

@@ -86,11 +86,11 @@ def test_image_side_conv_gradients(tag):
     _conv_fwd_bwd(tag)
 
 
-def _wgrad_desc(tag):
+def _wgrad_desc(tag, dtype=None):
     from hesic_amd import _lib as L
-    Cin, Cout, k, s, p, tr, (B, H, W), opt = R.CASES[tag]
+    Cin, Cout, k, s, p, tr, (B, H, W), opt = R.case(tag)
     Ho, Wo = R.out_hw(H, W, k, s, p, tr, opt.get("out_pad"))
-    return L.ConvDesc(B, H, W, Cin, Ho, Wo, Cout, k, k, s, p, int(tr), L.BF16, 0, int(opt.get("in_abs", False)), Cin, 0, Cout, 0,
+    return L.ConvDesc(B, H, W, Cin, Ho, Wo, Cout, k, k, s, p, int(tr), L.BF16 if dtype is None else dtype, 0, int(opt.get("in_abs", False)), Cin, 0, Cout, 0,
                       opt.get("tap_mask", 0))
 
 
@@ -174,3 +174,41 @@ def test_direct_narrow_wgrad_without_a_workspace():
     L.call("hesic_sconv2d_wgrad", C.byref(d), L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(db), None, 0, L.stream())
     torch.cuda.synchronize()
     _assert_all(tag, R.cached_reference(tag), {"dw": dw, "db": db})
+
+
+def _packed_wgrad(tag, f32, with_bias):
+    """hesic_conv2d_wgrad + hesic_unpack_conv_wgrad of a PACKED case: (dw in the PyTorch layout, db or None).  Every buffer the calls have to
+    write starts out as 7 (the workspace as NaN)."""
+    from hesic_amd import _lib as L
+    Cin, Cout, k, s, p, tr, _, _ = R.case(tag)
+    o = R.operands(tag)
+    dt = torch.float32 if f32 else BF
+    x, gy = (o[q].to(DEV, dt).contiguous(memory_format=CL) for q in ("x", "gy"))
+    d = _wgrad_desc(tag, L.F32 if f32 else L.BF16)
+    nws = int(L.lib().hesic_conv2d_wgrad_ws_bytes(C.byref(d)))
+    ws = torch.full((max(nws, 16) // 4,), float("nan"), device=DEV)
+    dwp = torch.full((k * k, Cout, Cin), 7.0, device=DEV)
+    dw = torch.full((Cout, Cin, k, k), 7.0, device=DEV)
+    db = torch.full((Cout,), 7.0, device=DEV) if with_bias else None
+    L.call("hesic_conv2d_wgrad", C.byref(d), L.ptr(x), L.ptr(gy), L.ptr(dwp), None if db is None else L.ptr(db), L.ptr(ws), nws, L.stream())
+    L.call("hesic_unpack_conv_wgrad", L.ptr(dwp), None, L.ptr(dw), Cout, Cin, k, k, int(tr), L.stream())
+    torch.cuda.synchronize()
+    return dw, db
+
+
+@pytest.mark.parametrize("with_bias", [True, False], ids=["bias", "nobias"])
+@pytest.mark.parametrize("f32", [False, True], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("tag", list(R.PACKED))
+@_bf16_library
+def test_packed_layout_wgrad(tag, f32, with_bias):
+    """The packed-layout entry point, which no Python wrapper calls: its K-slice reduce (plain for few slices, slice-parallel for the one-tap
+    layer with >= 32 slices, fused with the bias column sums when dbias is given) and the zero fill of a masked conv's dead taps."""
+    from hesic_amd import _lib as L
+    Cin, Cout, k, _, _, _, _, opt = R.case(tag)
+    d = _wgrad_desc(tag, L.F32 if f32 else L.BF16)
+    nsplit = int(L.lib().hesic_conv2d_wgrad_nsplit(C.byref(d), 0))
+    taps = bin(opt["tap_mask"]).count("1") if "tap_mask" in opt else k * k
+    wide_reduce = nsplit >= 32 and taps * Cout * Cin < 262144
+    assert wide_reduce == (tag == "packed_c1_wide"), (nsplit, taps)
+    dw, db = _packed_wgrad(tag, f32, with_bias)
+    _assert_all(f"{tag}_{'fp32' if f32 else 'bf16'}_{'bias' if with_bias else 'nobias'}", R.cached_reference(tag), {"dw": dw, "db": db})
