@@ -26,6 +26,7 @@ TRAIN_CTL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_t
 HOMOGRAPHY_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_train.h")
 HOMOGRAPHY_NET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_net.h")
 HOMOGRAPHY_PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_prep.h")
+PAIR_BATCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_batch.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -313,6 +314,19 @@ _HOMOGRAPHY_PREP_SIGS = {
 }
 PREP_U8, PREP_F32 = 0, 1        # HESIC_PREP_U8 / HESIC_PREP_F32
 
+
+# include/hesic_pair_batch.h: a batch of stereo crops gathered from uint8 images resident on the device, with the re-based homographies, in one
+# launch (functional.pair_batch_gather, pair_cache.DevicePairCache.batch, ``python -m hesic_amd.train_folder``), in both libraries
+class PairItem(C.Structure):
+    """hesic_pair_item (48 bytes)."""
+    _fields_ = [("left", C.c_uint64), ("right", C.c_uint64)] + \
+               [(n, _i32) for n in ("pitch_px", "rows", "x0", "y0", "hx", "hy", "h_index", "reserved")]
+
+
+_PAIR_BATCH_SIGS = {
+    "hesic_pair_batch_gather": ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp], _i32),
+}
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -374,6 +388,13 @@ def declared_homography_prep_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_pair_batch_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_pair_batch.h (used by the pair-batch ABI test)."""
+    with open(PAIR_BATCH_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def _load(h16):
     l = _libs.get(h16)
     if l is None:
@@ -395,7 +416,7 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
         for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
                 + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()) \
-                + list(_HOMOGRAPHY_PREP_SIGS.items()):
+                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -1883,6 +1883,78 @@ def homonet_prepare(x1, x2, xy, pic_size, patch_size, mean, std, out=None):
     return tuple(out)
 
 
+PAIR_ITEM_DTYPE = [("left", "<u8"), ("right", "<u8"), ("pitch_px", "<i4"), ("rows", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("hx", "<i4"),
+                   ("hy", "<i4"), ("h_index", "<i4"), ("reserved", "<i4")]       # hesic_pair_item as a numpy structured dtype (48 bytes)
+
+
+def pair_items(batch):
+    """A zeroed host array of ``batch`` ``hesic_pair_item`` descriptors (numpy structured, fields as in include/hesic_pair_batch.h;
+    ``left`` / ``right`` are device addresses as integers)."""
+    import numpy as np
+    return np.zeros(int(batch), dtype=np.dtype(PAIR_ITEM_DTYPE))
+
+
+def check_pair_items(items, n_table, ph, pw):
+    """The per-item conditions ``hesic_pair_batch_gather`` leaves to its caller, on the host: ValueError names the first item that breaks one."""
+    for b in range(len(items)):
+        it = items[b]
+        if int(it["left"]) == 0 or int(it["right"]) == 0:
+            raise ValueError(f"pair_batch_gather: item {b} has a null view pointer")
+        if int(it["pitch_px"]) < 1 or int(it["rows"]) < 1:
+            raise ValueError(f"pair_batch_gather: item {b} stored image {int(it['rows'])} x {int(it['pitch_px'])}")
+        if not (0 <= int(it["x0"]) and int(it["x0"]) + pw <= int(it["pitch_px"])):
+            raise ValueError(f"pair_batch_gather: item {b} columns [{int(it['x0'])}, {int(it['x0']) + pw}) outside the stored image's "
+                             f"{int(it['pitch_px'])}")
+        if not (0 <= int(it["y0"]) and int(it["y0"]) + ph <= int(it["rows"])):
+            raise ValueError(f"pair_batch_gather: item {b} rows [{int(it['y0'])}, {int(it['y0']) + ph}) outside the stored image's "
+                             f"{int(it['rows'])}")
+        if not -1 <= int(it["h_index"]) < n_table:
+            raise ValueError(f"pair_batch_gather: item {b} h_index {int(it['h_index'])} outside [-1, {n_table})")
+        if int(it["reserved"]) != 0:
+            raise ValueError(f"pair_batch_gather: item {b} reserved field must be 0")
+
+
+def pair_batch_gather(items, h_table, ph, pw, out=None):
+    """``hesic_pair_batch_gather`` (include/hesic_pair_batch.h): ``items`` the HOST description of the batch -- a numpy array of
+    ``PAIR_ITEM_DTYPE`` (``pair_items(B)``) or its bytes as a (B, 48) uint8 CPU tensor --, whose ``left`` / ``right`` are addresses of uint8
+    HWC images on the current device; ``h_table`` a dense fp64 (N, 9) device tensor or ``None``.  Every item is checked here, on the host
+    (the C entry cannot read them); the descriptors are then uploaded and one launch writes ``(x1, x2, h)``: (B,3,ph,pw), (B,3,ph,pw),
+    (B,3,3), fp32.  ``out``: three preallocated dense fp32 tensors of those shapes."""
+    import numpy as np
+    if torch.is_tensor(items):
+        if items.is_cuda or items.dtype != torch.uint8 or items.dim() != 2 or items.shape[1] != 48 or not items.is_contiguous():
+            raise ValueError("pair_batch_gather: items as a tensor must be a contiguous (B, 48) uint8 CPU tensor")
+        items = items.numpy().view(np.dtype(PAIR_ITEM_DTYPE)).reshape(-1)
+    items = np.ascontiguousarray(items)
+    if items.dtype != np.dtype(PAIR_ITEM_DTYPE) or items.ndim != 1:
+        raise ValueError("pair_batch_gather: items must be a 1-d array of PAIR_ITEM_DTYPE")
+    B, ph, pw = len(items), int(ph), int(pw)
+    if B < 1 or ph < 1 or pw < 1:
+        raise ValueError(f"pair_batch_gather: bad shape B={B} ph={ph} pw={pw}")
+    n_table = 0
+    if h_table is not None:
+        L.require_cuda(h_table)
+        if h_table.dtype != torch.float64 or h_table.dim() != 2 or h_table.shape[1] != 9 or not h_table.is_contiguous():
+            raise ValueError(f"pair_batch_gather: h_table must be a dense fp64 (N, 9) tensor, got {h_table.dtype} {tuple(h_table.shape)}")
+        n_table = h_table.shape[0]
+    check_pair_items(items, n_table, ph, pw)
+    if not torch.cuda.is_available():
+        raise RuntimeError("hesic_amd: the HIP path needs a ROCm device (no CPU fallback)")
+    dev = h_table.device if h_table is not None else (out[0].device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+    shapes = [(B, 3, ph, pw), (B, 3, ph, pw), (B, 3, 3)]
+    if out is None:
+        out = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+    else:
+        L.require_cuda(*out)
+        for t, s in zip(out, shapes):
+            if tuple(t.shape) != s or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"pair_batch_gather: out must be dense fp32 tensors of shapes {shapes}")
+    host = torch.from_numpy(items.view(np.uint8).reshape(B, 48)).pin_memory()        # a pinned copy: the caller may reuse ``items`` at once
+    items_dev = host.to(dev, non_blocking=True)
+    L.call("hesic_pair_batch_gather", L.ptr(items_dev), L.ptr(h_table), B, ph, pw, *[L.ptr(t) for t in out], L.stream())
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------ HomographyNet in training mode
 # include/hesic_homography_net.h: the pieces of ywz/mywork/model.py:73-101 that are not convolutions, with their gradients.
 class _MaxPool2Fn(torch.autograd.Function):

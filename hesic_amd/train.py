@@ -593,6 +593,11 @@ class GraphedTrainer(Trainer):
                                "read from device memory by every replay)")
         super().set_lr(lr, aux_lr)
 
+    def static_inputs(self):
+        """The step's static input tensors ``(x1, x2, h_matrix)``, or ``None`` before the first step.  A producer that writes a batch straight
+        into them and passes them to ``step`` saves the staging copies: ``_stage`` finds equal pointers and copies nothing."""
+        return self._in
+
     def _stage(self, x1, x2, h_matrix, noise):
         if self._in is None:
             self._in = (x1.clone(), x2.clone(), h_matrix.clone())
