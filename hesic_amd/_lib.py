@@ -27,6 +27,7 @@ HOMOGRAPHY_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "
 HOMOGRAPHY_NET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_net.h")
 HOMOGRAPHY_PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_prep.h")
 PAIR_BATCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_batch.h")
+PAIR_METRICS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_metrics.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -327,6 +328,14 @@ _PAIR_BATCH_SIGS = {
     "hesic_pair_batch_gather": ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp], _i32),
 }
 
+# include/hesic_pair_metrics.h: bits per likelihood map, squared error and 8-bit squared error per view as one fp64 row PER PAIR of a batch,
+# without atomics (functional.pair_metrics, models.pair_metrics, ``python -m hesic_amd.eval_folder``), in both libraries
+_PAIR_METRICS_SIGS = {
+    "hesic_pair_metrics_ws_bytes": ([_i32, _i32, _P(_i64), _i32, _i32], _i64),
+    "hesic_pair_metrics": ([_i32, _i32, _vp, _P(_i64), _vp, _P(_i32), _P(_i64), _vp, _P(_i32), _P(_i64), _i32, _i32, _i32, _vp, _vp, _i64, _vp], _i32),
+}
+PAIR_METRICS_MAX_LIK = 8        # HESIC_PAIR_METRICS_MAX_LIK
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -395,6 +404,13 @@ def declared_pair_batch_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_pair_metrics_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_pair_metrics.h (used by the pair-metrics ABI test)."""
+    with open(PAIR_METRICS_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def _load(h16):
     l = _libs.get(h16)
     if l is None:
@@ -416,7 +432,7 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
         for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
                 + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()) \
-                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()):
+                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -2797,6 +2797,50 @@ def rd_sums(liks, lik_outs, pairs, sq_outs):
            i32s(*[L.dt(b) for _, b in pairs]), i64s(*sb), i32d(*dims), vps(*[o.data_ptr() for o in sq_outs]), L.stream())
 
 
+def pair_metrics(liks, pairs, out=None, ws=None):
+    """The sums behind bpp / PSNR PER PAIR of a batch (``hesic_pair_metrics``, include/hesic_pair_metrics.h): a ``(B, len(liks) + 4)`` fp64
+    table whose row b holds sum(log2(lik_i)) over image b's slice of every likelihood map, then sse1, sse2 (sum((a - b)^2) of
+    ``pairs = [(x1_hat, x1), (x2_hat, x2)]`` over image b) and sse8_1, sse8_2 (the same on the 8-bit images ``codec.quantise`` writes).
+    Two launches, no atomics, no zero-fill: the table is written, and a pair's row has the same bits in every batch and at every position.
+    ``liks``: fp32 maps with the batch outermost (made contiguous only when neither dense nor channels-last); ``pairs``: (B, C, H, W)
+    tensors of any strides, fp32 or the active 16-bit format.  ``out`` / ``ws``: a preallocated table / workspace (uint8, 8-byte aligned)."""
+    if len(pairs) != 2:
+        raise ValueError("pair_metrics: two image pairs, (x1_hat, x1) and (x2_hat, x2)")
+    L.require_cuda(*liks, *[t for p in pairs for t in p])
+    B, Cc, H, W = pairs[0][0].shape
+    for t in (t for p in pairs for t in p):
+        if tuple(t.shape) != (B, Cc, H, W):
+            raise ValueError(f"pair_metrics: the four images must share one shape, got {tuple(t.shape)} and {(B, Cc, H, W)}")
+    nl = len(liks)
+    if nl > L.PAIR_METRICS_MAX_LIK:
+        raise ValueError(f"pair_metrics: at most {L.PAIR_METRICS_MAX_LIK} likelihood maps, got {nl}")
+    for l in liks:
+        if l.dtype != torch.float32 or l.dim() < 1 or l.shape[0] != B:
+            raise ValueError(f"pair_metrics: likelihood maps are fp32 with the batch of {B} outermost, got {l.dtype} {tuple(l.shape)}")
+    liks = [l if (l.is_contiguous() or (l.dim() == 4 and l.is_contiguous(memory_format=_CL))) else l.contiguous() for l in liks]
+    dev = pairs[0][0].device
+    numel = (C.c_int64 * max(nl, 1))(*[l.numel() for l in liks])
+    need = L.lib().hesic_pair_metrics_ws_bytes(B, nl, numel, H, W)
+    if need < 0:
+        raise RuntimeError(f"hesic_pair_metrics_ws_bytes failed: {L.lib().hesic_last_error().decode()}")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty((B, nl + 4), dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (B, nl + 4) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError(f"pair_metrics: out must be a dense fp64 {(B, nl + 4)} tensor")
+    L.require_cuda(out, ws)
+    vps, i32s, i64s = C.c_void_p * 2, C.c_int32 * 2, C.c_int64 * 8
+    sa, sb = [], []
+    for a, b in pairs:
+        sa += list(a.stride()); sb += list(b.stride())
+    L.call("hesic_pair_metrics", B, nl, (C.c_void_p * max(nl, 1))(*[l.data_ptr() for l in liks]), numel,
+           vps(*[a.data_ptr() for a, _ in pairs]), i32s(*[L.dt(a) for a, _ in pairs]), i64s(*sa),
+           vps(*[b.data_ptr() for _, b in pairs]), i32s(*[L.dt(b) for _, b in pairs]), i64s(*sb), Cc, H, W, L.ptr(out), L.ptr(ws),
+           ws.numel() * ws.element_size(), L.stream())
+    return out
+
+
 class _RdLossFn(torch.autograd.Function):
     """RateDistortionLoss (ywz/mywork/newtrain1.py:37-56) as two kinds of HIP reductions:
     loss = lmbda*255^2*(MSE1+MSE2) + sum_t sum(log lik_t)/(-ln2 * B*H*W).  Returns (loss, bpp, mse)."""

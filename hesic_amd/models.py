@@ -2218,3 +2218,41 @@ def metrics_from(rd, channels=3):
     bpp_loss = sum(bits.values()) / n
     return {"bits": bits, "bpp_loss": bpp_loss, "bpp": bpp_loss / 2, "mse1": mse1, "mse2": mse2, "psnr1": p1,
             "psnr2": p2, "psnr": (p1 + p2) / 2}
+
+
+def pair_metrics(out, x1, x2):
+    """``rate_distortion`` PER PAIR: bits / squared error of every pair of one forward as (B,) fp64 device tensors (``Fn.pair_metrics``:
+    two launches, no atomics, no host sync) -- what the reference gets by evaluating at ``--test-batch-size 1`` (test3real.py:3).
+    Returns dict(bits_<key> for every key of ``out["likelihoods"]``, sse1, sse2, sse8_1, sse8_2, num_pixels): ``sse8`` is the squared
+    error of the 8-bit images a decoder writes (``codec.quantise``), in units of grey levels squared; ``num_pixels`` = H * W of ONE
+    original image.  x1 / x2 are the ORIGINAL images: padded reconstructions are cropped to them (views), as in ``rate_distortion``."""
+    keys = list(out["likelihoods"].keys())
+    h, w = x1.shape[-2:]
+    n = len(keys)
+    t = Fn.pair_metrics([out["likelihoods"][k] for k in keys], [(out["x1_hat"][..., :h, :w], x1), (out["x2_hat"][..., :h, :w], x2)])
+    res = {"bits_" + k: -t[:, i] for i, k in enumerate(keys)}
+    res["sse1"], res["sse2"], res["sse8_1"], res["sse8_2"] = t[:, n], t[:, n + 1], t[:, n + 2], t[:, n + 3]
+    res["num_pixels"] = h * w
+    return res
+
+
+def _psnr_db(mse, peak=1.0):
+    """10 log10(peak^2 / mse) per element; 100 dB where the error is exactly zero (the reference's ``psnr()``, test3real.py:74-79)."""
+    return torch.where(mse == 0, torch.full_like(mse, 100.0), 10.0 * torch.log10(peak * peak / mse))
+
+
+def pair_metrics_from(pm, channels=3):
+    """``metrics_from`` per pair, as (B,) fp64 device tensors under the same names and conventions: bpp_loss (bits of both views / H W), bpp
+    (= bpp_loss / 2), mse1, mse2, psnr1, psnr2, psnr (= (psnr1 + psnr2) / 2); psnr8_1, psnr8_2, psnr8 from ``sse8`` with peak 255, the
+    PSNR of the decoded PNGs; ``bits`` per likelihood key.  A zero squared error gives 100.0 dB."""
+    n = pm["num_pixels"]
+    bits = {k[5:]: v for k, v in pm.items() if k.startswith("bits_")}
+    mse1, mse2 = pm["sse1"] / (n * channels), pm["sse2"] / (n * channels)
+    p1, p2 = _psnr_db(mse1), _psnr_db(mse2)
+    q1, q2 = _psnr_db(pm["sse8_1"] / (n * channels), 255.0), _psnr_db(pm["sse8_2"] / (n * channels), 255.0)
+    total = None
+    for v in bits.values():
+        total = v if total is None else total + v
+    bpp_loss = (total if total is not None else torch.zeros_like(mse1)) / n
+    return {"bits": bits, "bpp_loss": bpp_loss, "bpp": bpp_loss / 2, "mse1": mse1, "mse2": mse2, "psnr1": p1, "psnr2": p2,
+            "psnr": (p1 + p2) / 2, "psnr8_1": q1, "psnr8_2": q2, "psnr8": (q1 + q2) / 2}
