@@ -28,6 +28,7 @@ HOMOGRAPHY_NET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "he
 HOMOGRAPHY_PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_prep.h")
 PAIR_BATCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_batch.h")
 PAIR_METRICS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_metrics.h")
+EN_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_en_train.h")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -336,6 +337,21 @@ _PAIR_METRICS_SIGS = {
 }
 PAIR_METRICS_MAX_LIK = 8        # HESIC_PAIR_METRICS_MAX_LIK
 
+
+# include/hesic_en_train.h: the stage-2 criterion of both views, its gradient as the output layer's 32-channel map, and the data-gradient weights of
+# a flat parameter buffer's convs in one launch (functional.en_criterion, train.EnhancerTrainer, ``python -m hesic_amd.train_stage2``), in both libraries
+class MirrorEntry(C.Structure):
+    """hesic_mirror_entry (32 bytes)."""
+    _fields_ = [("src", _i64), ("dst", _i64), ("cout", _i32), ("cin", _i32), ("cout_pad", _i32), ("reserved", _i32)]
+
+
+_EN_TRAIN_SIGS = {
+    "hesic_en_loss_ws_bytes": ([_i32, _i32, _i32], _i64),
+    "hesic_en_loss": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _i64, _vp], _i32),
+    "hesic_en_loss_grad": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp], _i32),
+    "hesic_c32_mirror_weights": ([_vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp], _i32),
+}
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -411,6 +427,13 @@ def declared_pair_metrics_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_en_train_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_en_train.h (used by the stage-2 training ABI test)."""
+    with open(EN_TRAIN_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def _load(h16):
     l = _libs.get(h16)
     if l is None:
@@ -432,7 +455,7 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
         for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
                 + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()) \
-                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()):
+                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()) + list(_EN_TRAIN_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

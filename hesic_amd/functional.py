@@ -1512,6 +1512,157 @@ def _mirror_t(weight, pad_to=None):
     return wt.contiguous()
 
 
+# ------------------------------------------------------------------------------ mirrored data-gradient weights
+# train.EnhancerTrainer keeps the data-gradient weight of every 3x3 conv of the enhancement net in ONE flat fp32 buffer that a single launch per
+# step refreshes (``c32_mirror_weights``).  The registry follows the gradient slots': a weight is looked up by storage address, and only while the
+# gate is on (inside that trainer's step, after its refresh) does a backward pass take the view; everywhere else ``_mirror_t`` runs as before.
+_mirror_views = {}
+_mirror_active = False
+
+
+def register_mirror_views(pairs):
+    """``pairs``: iterable of (weight parameter, its view of the mirrored flat buffer, shaped like ``_mirror_t(weight, 32)``).  Replaces any view
+    registered for the same storage address; returns the registered addresses (for ``clear_mirror_views``)."""
+    import weakref
+    keys = []
+    for p, view in pairs:
+        _mirror_views[p.data_ptr()] = (weakref.ref(p), view)
+        keys.append(p.data_ptr())
+    return keys
+
+
+def clear_mirror_views(keys=None):
+    if keys is None:
+        _mirror_views.clear()
+    else:
+        for k in keys:
+            _mirror_views.pop(k, None)
+
+
+def mirror_views_active(on):
+    """Gate of the registry; returns the previous state.  The caller has refreshed the flat buffer on this stream before it turns the gate on."""
+    global _mirror_active
+    prev, _mirror_active = _mirror_active, bool(on)
+    return prev
+
+
+def _dgrad_weight(weight, pad_to=32):
+    """The weight of ``weight``'s data-gradient conv: the registered view while the registry is active, ``_mirror_t`` otherwise."""
+    if _mirror_active and _mirror_views:
+        hit = _mirror_views.get(weight.data_ptr())
+        if hit is not None:
+            owner = hit[0]()
+            if owner is None or owner.data_ptr() != weight.data_ptr():      # the parameter is gone (its address may have been reused)
+                _mirror_views.pop(weight.data_ptr(), None)
+            elif hit[1].shape == (weight.shape[1], max(weight.shape[0], pad_to or 0), 3, 3) and hit[1].device == weight.device:
+                return hit[1]
+    return _mirror_t(weight, pad_to)
+
+
+def c32_mirror_weights(src, dst, table, n_layers):
+    """``hesic_c32_mirror_weights``: the data-gradient weights of ``n_layers`` convs of the flat fp32 buffer ``src`` into the flat fp32 buffer
+    ``dst``, one launch; ``table``: a device uint8 tensor holding ``_lib.MirrorEntry`` records."""
+    L.require_cuda(src, dst, table)
+    L.call("hesic_c32_mirror_weights", L.ptr(src), src.numel(), L.ptr(dst), dst.numel(), L.ptr(table), int(n_layers),
+           table.numel() // C.sizeof(L.MirrorEntry), L.stream())
+    return dst
+
+
+def mirror_table(entries, device):
+    """A device table for ``c32_mirror_weights`` from ``(src offset, dst offset, cout, cin, cout_pad)`` tuples (offsets in floats)."""
+    arr = (L.MirrorEntry * len(entries))(*[L.MirrorEntry(int(s), int(d), int(co), int(ci), int(cp), 0) for s, d, co, ci, cp in entries])
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def _check_en_images(who, *ts):
+    for t in ts:
+        if t.dim() != 4 or t.shape[1] != 3 or t.shape != ts[0].shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{who}: four dense fp32 (B,3,H,W) tensors of one shape")
+
+
+def en_loss(a1, b1, a2, b2, lambda_255sq, out=None, ws=None):
+    """``hesic_en_loss``: fp64 ``[sse1, sse2, mse_loss, loss]`` of two (enhanced image, target) pairs, dense fp32 planar (B,3,H,W); two launches,
+    no atomics.  ``out`` (4 fp64) and ``ws`` (uint8, ``hesic_en_loss_ws_bytes``) are allocated when not given."""
+    L.require_cuda(a1, b1, a2, b2, out, ws)
+    _check_en_images("en_loss", a1, b1, a2, b2)
+    B, _, H, W = a1.shape
+    nws = int(L.lib().hesic_en_loss_ws_bytes(B, H, W))
+    if nws < 0:
+        raise RuntimeError(f"hesic_en_loss_ws_bytes failed: {L.lib().hesic_last_error().decode()}")
+    if ws is None:
+        ws = torch.empty(nws, dtype=torch.uint8, device=a1.device)
+    if out is None:
+        out = torch.empty(4, dtype=torch.float64, device=a1.device)
+    L.call("hesic_en_loss", L.ptr(a1), L.ptr(b1), L.ptr(a2), L.ptr(b2), B, H, W, float(lambda_255sq), L.ptr(out), L.ptr(ws), ws.numel(), L.stream())
+    return out
+
+
+def en_loss_grad(a1, b1, a2, b2, lambda_255sq, seed=None, out=None):
+    """``hesic_en_loss_grad``: the gradient of ``en_loss``'s loss w.r.t. ``a1`` and ``a2`` as two (B,32,H,W) NHWC maps in the 16-bit format (channels
+    0..2, the rest zero), one launch; ``seed``: an fp32 device scalar that multiplies the scale, or None; ``out``: the two maps, or None."""
+    L.require_cuda(a1, b1, a2, b2, seed)
+    _check_en_images("en_loss_grad", a1, b1, a2, b2)
+    B, _, H, W = a1.shape
+    g1, g2 = out if out is not None else (_empty_nhwc(B, 32, H, W, _h16(), a1.device), _empty_nhwc(B, 32, H, W, _h16(), a1.device))
+    L.call("hesic_en_loss_grad", L.ptr(a1), L.ptr(b1), L.ptr(a2), L.ptr(b2), B, H, W, float(lambda_255sq), L.ptr(seed), L.ptr(g1), L.ptr(g2),
+           L.stream())
+    return g1, g2
+
+
+def _dense_f32(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+class _EnCriterionFn(torch.autograd.Function):
+    """Both views' 32 -> 3 output convs (+ the images they refine) and the stage-2 criterion as ONE autograd node: forward = two
+    ``hesic_conv3x3_c32_forward`` launches and ``hesic_en_loss``; backward = ``hesic_en_loss_grad`` (the gradient lands in the 32-channel map
+    directly: no fp32 gradient image, no zero image, no pack) and per view the 32-channel data-gradient conv and ``conv3x3_c32_wgrad`` (flat
+    slots honoured).  Outputs: loss, mse_loss (fp64 device scalars), the two enhanced images; only ``loss`` carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, t1, w1, b1, img1, x1, t2, w2, b2, img2, x2, lmbda):
+        t1, t2 = _nhwc(t1), _nhwc(t2)
+        x1, x2 = _dense_f32(x1), _dense_f32(x2)
+        y1 = conv3x3_c32(t1, w1, b1, res1=img1)
+        y2 = conv3x3_c32(t2, w2, b2, res1=img2)
+        ctx.scale = float(lmbda) * 255 ** 2
+        out = en_loss(y1, x1, y2, x2, ctx.scale)
+        ctx.save_for_backward(t1, w1, t2, w2, y1, x1, y2, x2)
+        ctx.biases = (b1, b2)
+        loss, mse = out[3], out[2]
+        ctx.mark_non_differentiable(mse, y1, y2)
+        ctx.set_materialize_grads(False)          # no zero images for the outputs that carry no gradient
+        return loss, mse, y1, y2
+
+    @staticmethod
+    def backward(ctx, g_loss, *unused):
+        t1, w1, t2, w2, y1, x1, y2, x2 = ctx.saved_tensors
+        # as in _RdLossFn: g_loss stays on the device and is applied (inside the kernel) only when SCALED_LOSS is on
+        seed = g_loss.detach().reshape(1).to(torch.float32) if SCALED_LOSS else None
+        g1, g2 = en_loss_grad(y1, x1, y2, x2, ctx.scale, seed)
+        grads = []
+        for i, (t, w, g, bias) in enumerate(((t1, w1, g1, ctx.biases[0]), (t2, w2, g2, ctx.biases[1]))):
+            dt = dw = db = None
+            if ctx.needs_input_grad[5 * i]:
+                dt = conv3x3_c32(g, _dgrad_weight(w, 32), None)
+            if ctx.needs_input_grad[5 * i + 1]:
+                dw, db = conv3x3_c32_wgrad(t, g, w, bias)
+            grads += [dt, dw, db, None, None]
+        return (*grads, None)
+
+
+def en_criterion_ok(t, weight):
+    """The fused stage-2 criterion node applies: a ROCm device, autograd on, the 16-bit training format, a (3,32,3,3) output layer."""
+    return (EN_TRAIN_FAST and torch.is_grad_enabled() and t.is_cuda and t.dim() == 4 and t.shape[1] == 32 and t.dtype == _h16() and _is16()
+            and tuple(weight.shape) == (3, 32, 3, 3) and weight.dtype == torch.float32)
+
+
+def en_criterion(t1, w1, b1, img1, x1, t2, w2, b2, img2, x2, lmbda):
+    """``loss = lmbda * 255^2 * (MSE(y1, x1) + MSE(y2, x2))`` with ``y_v = conv3x3(t_v, w_v) + b_v + img_v`` (newtrain6_real.py:82-88 on
+    ``Enhancement``'s output layer): returns ``(loss, mse_loss, y1, y2)``, fp64 device scalars and the detached fp32 enhanced images."""
+    return _EnCriterionFn.apply(t1, w1, b1, img1.float(), x1, t2, w2, b2, img2.float(), x2, lmbda)
+
+
 class _Conv3x3C32Fn(torch.autograd.Function):
     """act(conv3x3(x) + bias) of the 32-channel enhancement layers under autograd, forward, data gradient AND weight gradient on kernels
     built for the shape: dx = conv3x3(act'(y) * dy, W^T with the taps mirrored) is ``hesic_conv3x3_c32_forward`` on another weight tensor,
@@ -1541,7 +1692,7 @@ class _Conv3x3C32Fn(torch.autograd.Function):
             g = gy
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = conv3x3_c32(g, _mirror_t(weight, 32), None)          # (a narrower conv's extra input channels get zero gradient)
+            dx = conv3x3_c32(g, _dgrad_weight(weight, 32), None)      # (a narrower conv's extra input channels get zero gradient)
         if ctx.needs_input_grad[1]:
             dw, db = conv3x3_c32_wgrad(x, g, weight, ctx.bias)
         return dx, dw, db, None

@@ -1891,7 +1891,8 @@ class Enhancement(nn.Module):
         self.EB1, self.EB2, self.EB3 = Enhancement_Block(), Enhancement_Block(), Enhancement_Block()
         self.conv2 = conv3x3(32, 3)
 
-    def forward(self, x, x_another_warp):
+    def trunk(self, x, x_another_warp):
+        """Everything before the 32 -> 3 output layer: the 32-channel feature map ``conv2`` reads."""
         if (Fn.conv3x3_c32_ok(x.new_empty((1, 32, 1, 1), dtype=Fn._h16()), self.EB1.RB1.conv1.weight) and x.is_cuda
                 and tuple(self.conv1.weight.shape) == (32, 6, 3, 3)):
             # inference: the 6 -> 32 input conv reads the two planar images directly (round 6: one launch instead of pack_images_c32 + the
@@ -1904,8 +1905,14 @@ class Enhancement(nn.Module):
             t = Fn.conv3x3_c32_train(Fn.pack_images_c32(x, x_another_warp), self.conv1.weight, self.conv1.bias)
         else:
             t = _ho.plain(self.conv1(torch.cat((x.float(), x_another_warp.float()), 1)))
-        t = self.EB3(self.EB2(self.EB1(t)))
-        if Fn.conv3x3_c32_ok(t, self.conv2.weight):          # 32 -> 3 output conv + the image it refines, fp32 planar out
+        return self.EB3(self.EB2(self.EB1(t)))
+
+    def forward(self, x, x_another_warp):
+        return self.head(self.trunk(x, x_another_warp), x)
+
+    def head(self, t, x):
+        """The 32 -> 3 output layer on ``trunk``'s map, plus the image ``x`` it refines."""
+        if Fn.conv3x3_c32_ok(t, self.conv2.weight):        # 32 -> 3 output conv + the image it refines, fp32 planar out
             return Fn.conv3x3_c32(t, self.conv2.weight, self.conv2.bias, res1=x)
         if (Fn.EN_TRAIN_FAST and torch.is_grad_enabled() and t.is_cuda and t.dtype == Fn._h16() and t.shape[1] == 32
                 and tuple(self.conv2.weight.shape) == (3, 32, 3, 3)):
@@ -1927,6 +1934,24 @@ class Independent_EN(nn.Module):
         x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
         x2_hat_warp = warp_perspective(x2_hat, h_matrix, size, inverse_map=True)   # warp by inverse(H) (:1290): H is its inverse map
         return {"x1_hat": self.EH1(x1_hat, x2_hat_warp), "x2_hat": self.EH2(x2_hat, x1_hat_warp)}
+
+    def criterion(self, x1_hat, x2_hat, h_matrix, x1, x2, lmbda):
+        """The stage-2 criterion on the reconstructions ``x1_hat, x2_hat`` of a frozen compression model (newtrain6_real.py:82-88):
+        ``{"loss": lmbda * 255^2 * mse_loss, "mse_loss": MSE(x1_hat', x1) + MSE(x2_hat', x2), "x1_hat", "x2_hat"}`` -- device scalars (only
+        ``loss`` carries a gradient) and the enhanced images, detached.  On a ROCm device in the 16-bit training format the two output layers and
+        the loss are ONE autograd node (``functional.en_criterion``); elsewhere (fp32 training, the CPU, ``no_grad``) the same quantities come
+        from ``forward`` and torch's elementwise ops."""
+        size = (x1_hat.shape[-2], x1_hat.shape[-1])
+        x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
+        x2_hat_warp = warp_perspective(x2_hat, h_matrix, size, inverse_map=True)
+        t1, t2 = self.EH1.trunk(x1_hat, x2_hat_warp), self.EH2.trunk(x2_hat, x1_hat_warp)
+        c1, c2 = self.EH1.conv2, self.EH2.conv2
+        if Fn.en_criterion_ok(t1, c1.weight) and Fn.en_criterion_ok(t2, c2.weight) and c1.bias is not None and c2.bias is not None:
+            loss, mse, y1, y2 = Fn.en_criterion(t1, c1.weight, c1.bias, x1_hat, x1, t2, c2.weight, c2.bias, x2_hat, x2, lmbda)
+            return {"loss": loss, "mse_loss": mse, "x1_hat": y1, "x2_hat": y2}
+        y1, y2 = self.EH1.head(t1, x1_hat), self.EH2.head(t2, x2_hat)
+        mse = ((y1.float() - x1) ** 2).mean() + ((y2.float() - x2) ** 2).mean()
+        return {"loss": lmbda * 255 ** 2 * mse, "mse_loss": mse.detach(), "x1_hat": y1.detach(), "x2_hat": y2.detach()}
 
 
 class GMM_together(nn.Module):

@@ -832,3 +832,167 @@ class Stage2Trainer:
                 Fn.set_compute_dtype(keep)
         self.optimizer.step()
         return {"loss": loss.detach(), "mse_loss": mse.detach()}
+
+
+class EnhancerTrainer:
+    """Stage 2 as a first-class path: ``Stage2Trainer``'s loss and ``train_dtype`` handling (the f16-inference / bf16-training switch
+    included) over flat buffers, with ``Trainer``'s step controls.
+
+    The enhancer's parameters live in one ``FlatGroup`` stepped by one ``FlatAdam``; ``clip_max_norm``, ``skip_nonfinite`` and ``live_lr``
+    mean what they mean on ``Trainer`` (the same control block, the same returned ``grad_norm`` / ``clip_coef`` / ``skipped``, ``set_lr``), and
+    with none of them set no control launch is issued.  The data-gradient weights of the enhancer's 40 convs live in one more flat buffer
+    that ONE ``hesic_c32_mirror_weights`` launch per step refreshes (``functional.register_mirror_views``), and the two output layers plus the
+    criterion are one autograd node (``Independent_EN.criterion``).  A step: zero the flat gradient -> mirror launch -> frozen forward
+    (``no_grad``, eval mode) -> ``enhancer.criterion`` -> ``loss.backward()`` with the gradient slots and the mirror registry active and
+    ``SCALED_LOSS`` off -> Adam.  The frozen model's parameters never receive a gradient and its aux loss is not computed (the reference
+    computes it and never steps it, newtrain6_real.py:169-171).  Every launch of the step reduces in a fixed order, so equal inputs and state
+    give equal bits."""
+
+    def __init__(self, model, enhancer, lr=1e-4, lmbda=1e-2, train_dtype=None, clip_max_norm=None, skip_nonfinite=False, live_lr=False):
+        if clip_max_norm is not None:
+            import math
+            ok = isinstance(clip_max_norm, (int, float)) and not isinstance(clip_max_norm, bool)
+            if not ok or not math.isfinite(clip_max_norm) or clip_max_norm <= 0:
+                raise ValueError(f"EnhancerTrainer: clip_max_norm must be a finite positive number (or None: no clipping), got {clip_max_norm!r}")
+            clip_max_norm = float(clip_max_norm)
+        for name, flag in (("skip_nonfinite", skip_nonfinite), ("live_lr", live_lr)):
+            if not isinstance(flag, bool):
+                raise TypeError(f"EnhancerTrainer: {name} must be a bool, got {type(flag).__name__}")
+        if train_dtype is None and Fn.compute_dtype() == torch.float16:
+            train_dtype = torch.bfloat16
+        if train_dtype not in (None, torch.bfloat16, torch.float32):
+            raise ValueError("EnhancerTrainer: train_dtype is None, torch.bfloat16 or torch.float32 (float16 is an inference format)")
+        self.model, self.enhancer, self.lmbda, self.train_dtype = model, enhancer, float(lmbda), train_dtype
+        self.clip_max_norm, self.skip_nonfinite, self.live_lr = clip_max_norm, skip_nonfinite, live_lr
+        self.controls = clip_max_norm is not None or skip_nonfinite or live_lr
+        self.group = FlatGroup(enhancer.parameters())
+        self.on_gpu = self.group.flat_p.is_cuda
+        if not self.on_gpu:
+            raise RuntimeError("EnhancerTrainer: the HIP path needs the enhancer on a ROCm device (no CPU fallback)")
+        ctl = {"max_norm": clip_max_norm, "skip_nonfinite": skip_nonfinite, "also_require": None} if self.controls else None
+        self.optimizer = FlatAdam(self.group, lr=lr, controls=ctl)
+        # the mirror table: every 3x3 conv of up to 32 x 32 channels, its weight's offset in the flat parameters and its slot in flat_m
+        import weakref
+        offset = {id(p): o for p, o in zip(self.group.params, self.group.offsets)}
+        entries, views, off = [], [], 0
+        for p in self.group.params:
+            if p.dim() == 4 and tuple(p.shape[2:]) == (3, 3) and p.shape[0] <= 32 and p.shape[1] <= 32:
+                entries.append((offset[id(p)], off, p.shape[0], p.shape[1], 32))
+                views.append((p, off, p.shape[1] * 32 * 9))
+                off += -(-p.shape[1] * 32 * 9 // FlatGroup.ALIGN) * FlatGroup.ALIGN
+        self.mirror_layers = len(entries)
+        if entries:
+            self.flat_m = torch.zeros(off, dtype=torch.float32, device=self.group.flat_p.device)
+            self.mirror_table = Fn.mirror_table(entries, self.flat_m.device)
+            keys = Fn.register_mirror_views((p, self.flat_m[o:o + n].view(p.shape[1], 32, 3, 3)) for p, o, n in views)
+            weakref.finalize(self, Fn.clear_mirror_views, keys)
+
+    def set_lr(self, lr):
+        """The learning rate of every following step (``param_groups`` and, on the control path, the device control block)."""
+        self.optimizer.param_groups[0]["lr"] = float(lr)
+        self._sync_lr()
+
+    def _sync_lr(self):
+        if self.controls and not torch.cuda.is_current_stream_capturing():
+            self.optimizer.sync_lr()
+
+    def step(self, x1, x2, h_matrix):
+        """One iteration (see the class docstring); returns detached device scalars ``{"loss", "mse_loss"}`` plus ``grad_norm``, ``clip_coef``
+        and ``skipped`` when controls are set."""
+        self._sync_lr()                           # control path: param_groups -> control block (not while capturing)
+        self.model.eval()
+        self.enhancer.train()
+        self.group.zero_grad()
+        if self.mirror_layers:
+            Fn.c32_mirror_weights(self.group.flat_p, self.flat_m, self.mirror_table, self.mirror_layers)
+        with torch.no_grad():
+            out = self.model(x1, x2, h_matrix)
+        keep = Fn.compute_dtype()
+        if self.train_dtype is not None and self.train_dtype != keep:
+            Fn.set_compute_dtype(self.train_dtype)
+        scaled, Fn.SCALED_LOSS = Fn.SCALED_LOSS, False     # backward() starts at the unscaled loss
+        slots = Fn.grad_slots_active(True)
+        mirror = Fn.mirror_views_active(self.mirror_layers > 0)
+        try:
+            with torch.enable_grad():
+                crit = self.enhancer.criterion(out["x1_hat"].float(), out["x2_hat"].float(), h_matrix, x1, x2, self.lmbda)
+                crit["loss"].backward()
+        finally:
+            Fn.mirror_views_active(mirror)
+            Fn.grad_slots_active(slots)
+            Fn.SCALED_LOSS = scaled
+            if Fn.compute_dtype() != keep:
+                Fn.set_compute_dtype(keep)
+        res = {"loss": crit["loss"].detach(), "mse_loss": crit["mse_loss"].detach()}
+        self.optimizer.step()
+        if self.controls:
+            from . import _lib as L
+            own = (lambda t: t) if torch.cuda.is_current_stream_capturing() else torch.clone
+            ctl = self.optimizer.ctl
+            res["grad_norm"], res["clip_coef"], res["skipped"] = own(ctl[L.CTL_GRAD_NORM]), own(ctl[L.CTL_CLIP_COEF]), own(ctl[L.CTL_SKIPPED])
+        return res
+
+
+class GraphedEnhancerTrainer(EnhancerTrainer):
+    """``EnhancerTrainer.step`` recorded once into a HIP graph and replayed, by ``GraphedTrainer``'s protocol: the first ``warmup`` calls run
+    eagerly on a side stream (real steps), the next call captures, every later call copies the inputs into the static buffers (nothing, when the
+    producer wrote into ``static_inputs()``) and launches the graph.  The returned dict holds the graph's static tensors (overwritten by the
+    next call).  Without step controls the captured Adam holds its learning rate by value and ``set_lr`` refuses after the capture; with any of
+    them the rate is read from device memory by every replay.  After a replay the enhancer's parameters get their version counters bumped (what
+    the eager optimiser step does); the global pack-cache epoch is left alone, because the graph reads the frozen model's cached packed weights
+    by address -- and when somebody else moves that epoch (``functional.invalidate_weight_cache``), the next call runs eagerly and the one
+    after it captures again.  Stage 2 has no collectives: one process, one device."""
+
+    def __init__(self, model, enhancer, *args, warmup=3, **kw):
+        super().__init__(model, enhancer, *args, **kw)
+        if int(warmup) < 1:
+            raise ValueError("GraphedEnhancerTrainer: warmup >= 1 (workspaces and the frozen model's packed weights are created by an eager step)")
+        self.warmup, self.calls, self.graph = int(warmup), 0, None
+        self._in = self._out = self._epoch = None
+
+    def set_lr(self, lr):
+        if self.graph is not None and not self.controls:
+            raise RuntimeError("GraphedEnhancerTrainer.set_lr: the captured step holds its learning rate by value in the kernel arguments of its "
+                               "Adam launch, a replay cannot see a new one -- build the trainer with live_lr=True (the rate is then read from "
+                               "device memory by every replay)")
+        super().set_lr(lr)
+
+    def static_inputs(self):
+        """The step's static input tensors ``(x1, x2, h_matrix)``, or ``None`` before the first step (see ``GraphedTrainer.static_inputs``)."""
+        return self._in
+
+    def _stage(self, x1, x2, h_matrix):
+        if self._in is None:
+            self._in = (x1.clone(), x2.clone(), h_matrix.clone())
+        else:
+            for dst, src in zip(self._in, (x1, x2, h_matrix)):
+                if src.data_ptr() != dst.data_ptr():
+                    dst.copy_(src)
+
+    def step(self, x1, x2, h_matrix):
+        self._stage(x1, x2, h_matrix)
+        self._sync_lr()                           # this call's rate, filled in ahead of the capture / the replay
+        if self.graph is not None and Fn._epoch_n != self._epoch:
+            # Somebody started a new pack-cache epoch (``invalidate_weight_cache``) since the capture: the frozen model's next eager forward
+            # replaces -- and frees -- the packed weights this graph reads.  Drop the graph: one eager step re-packs, the next call captures.
+            self.graph, self._out, self.calls = None, None, self.warmup - 1
+        self.calls += 1
+        if self.graph is None and self.calls <= self.warmup:
+            side = torch.cuda.Stream(device=x1.device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                out = super().step(*self._in)
+            torch.cuda.current_stream().wait_stream(side)
+            return out
+        if self.graph is None:
+            self.graph = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize()
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                self._out = super().step(*self._in)
+            self._epoch = Fn._epoch_n
+        self.graph.replay()
+        # A replay runs no Python: the captured Adam moved the parameters without touching their version counters.  Bump them, as the eager
+        # ``FlatAdam.step`` does: every cache keyed on the ENHANCER's parameters misses from here on.  ``GraphedTrainer`` starts a new global
+        # cache epoch instead; here that would also drop the FROZEN model's packed weights, which the graph reads by address (see above).
+        torch.autograd.graph.increment_version(self.group.params)
+        return self._out
