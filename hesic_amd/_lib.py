@@ -26,6 +26,7 @@ TRAIN_CTL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_t
 HOMOGRAPHY_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_train.h")
 HOMOGRAPHY_NET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_net.h")
 HOMOGRAPHY_PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_prep.h")
+HOMONET_ITEMS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homonet_items.h")
 PAIR_BATCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_batch.h")
 PAIR_METRICS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_metrics.h")
 EN_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_en_train.h")
@@ -317,6 +318,20 @@ _HOMOGRAPHY_PREP_SIGS = {
 PREP_U8, PREP_F32 = 0, 1        # HESIC_PREP_U8 / HESIC_PREP_F32
 
 
+# include/hesic_homonet_items.h (included by hesic_homography_prep.h): the same step from stored uint8 images of per-item address and size
+# (functional.homonet_prepare_items, pair_cache.DevicePairCache.homonet_batch, ``python -m hesic_amd.homography_train --cache device|stream``),
+# in both libraries
+class HomonetItem(C.Structure):
+    """hesic_homonet_item (48 bytes)."""
+    _fields_ = [("left", C.c_uint64), ("right", C.c_uint64)] + \
+               [(n, _i32) for n in ("pitch_px", "rows", "x0", "y0", "cw", "ch", "wx", "wy")]
+
+
+_HOMONET_ITEMS_SIGS = {
+    "hesic_homonet_prepare_items": ([_vp, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+}
+
+
 # include/hesic_pair_batch.h: a batch of stereo crops gathered from uint8 images resident on the device, with the re-based homographies, in one
 # launch (functional.pair_batch_gather, pair_cache.DevicePairCache.batch, ``python -m hesic_amd.train_folder``), in both libraries
 class PairItem(C.Structure):
@@ -413,6 +428,13 @@ def declared_homography_prep_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_homonet_items_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_homonet_items.h (used by the item-form input-preparation ABI test)."""
+    with open(HOMONET_ITEMS_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def declared_pair_batch_symbols():
     """Every ``hesic_*`` function declared in include/hesic_pair_batch.h (used by the pair-batch ABI test)."""
     with open(PAIR_BATCH_HEADER_PATH) as f:
@@ -455,7 +477,7 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
         for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
                 + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()) \
-                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()) + list(_EN_TRAIN_SIGS.items()):
+                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_HOMONET_ITEMS_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()) + list(_EN_TRAIN_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -100,7 +100,98 @@ __global__ __launch_bounds__(PREP_THREADS) void homonet_prepare_kernel(const Pre
     if (px < (unsigned)P && py < (unsigned)P) v.patch[((int64_t)b * P + py) * P + px] = g;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ the item form
+// hesic_homonet_prepare_items (include/hesic_homonet_items.h): the same thread map and the same device functions, the sources being stored
+// HWC bytes of per-item geometry.  blockIdx.y = item: the descriptor is block-uniform and read once (scalar loads).  A row's two taps are
+// two neighbouring pixels = six adjacent bytes: they are fetched as one dword and one ushort at byte alignment (gfx950 global loads take
+// any alignment) instead of six strided bytes, so a thread issues 4 loads where the strided kernel issues 12, and one 64-bit address per row.
+// `xs` is the first of the two columns fetched: i0, or i0 - 1 at the crop's last column, where i1 == i0 and both taps are the second
+// pixel -- the six bytes never leave the crop's row.  A crop one pixel wide (block-uniform) is read as its three bytes.
+typedef uint32_t __attribute__((aligned(1))) prep_u32_any;      // a dword / ushort at any byte address
+typedef uint16_t __attribute__((aligned(1))) prep_u16_any;
+
+struct PrepTaps {
+    uint32_t px[2];         // the two adjacent pixels, R G B in bits 0-23 of each (bits 24-31 are not used)
+};
+
+__device__ __forceinline__ PrepTaps prep_load_taps(const uint8_t* p, bool two) {
+    const __attribute__((address_space(1))) uint8_t* g = (const __attribute__((address_space(1))) uint8_t*)p;       // global, not flat, loads
+    PrepTaps t;
+    if (two) {
+        const uint32_t lo = *(const __attribute__((address_space(1))) prep_u32_any*)g;
+        const uint32_t hi = *(const __attribute__((address_space(1))) prep_u16_any*)(g + 4);
+        t.px[0] = lo;
+        t.px[1] = __funnelshift_r(lo, hi, 24);
+    } else {
+        t.px[0] = t.px[1] = (uint32_t)g[0] | ((uint32_t)g[1] << 8) | ((uint32_t)g[2] << 16);       // the one pixel: either tap index reads it
+    }
+    return t;
+}
+
+// channel c of pixel k (0 or 1) of a fetched pair
+__device__ __forceinline__ float prep_tap_level(const PrepTaps& t, int k, int c) {
+    return (float)(((k ? t.px[1] : t.px[0]) >> (8 * c)) & 0xffu);
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void homonet_prepare_items_kernel(const hesic_homonet_item* __restrict__ items, float* __restrict__ grey1,
+                                                                             float* __restrict__ grey2, float* __restrict__ patch1,
+                                                                             float* __restrict__ patch2, float* __restrict__ corners, int S, int P,
+                                                                             float mean, float std) {
+    const int b = blockIdx.y;
+    const hesic_homonet_item it = items[b];
+    const int wx = it.wx, wy = it.wy;
+    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x < 8) {
+        const int k = threadIdx.x >> 1;                 // as in homonet_prepare_kernel
+        const int val = (threadIdx.x & 1) ? wy + (k >= 2 ? P : 0) : wx + ((k == 1 || k == 2) ? P : 0);
+        corners[(int64_t)b * 8 + threadIdx.x] = (float)val;
+    }
+    const int idx = blockIdx.x * PREP_THREADS + threadIdx.x;
+    if (idx >= S * S) return;
+    const int y = idx / S, x = idx - y * S;
+    const float scale_y = __fdiv_rn((float)it.ch, (float)S), scale_x = __fdiv_rn((float)it.cw, (float)S);
+    const PrepAxis ay = prep_axis(y, it.ch, scale_y), ax = prep_axis(x, it.cw, scale_x);
+    const bool two = it.cw >= 2;
+    const int xs = two ? min(ax.i0, it.cw - 2) : 0;
+    const int k0 = ax.i0 - xs, k1 = ax.i1 - xs;         // 0 or 1 each
+    const uint8_t* view = blockIdx.z == 0 ? it.left : it.right;
+    const int64_t col = (int64_t)(it.x0 + xs) * 3;
+    const PrepTaps r0 = prep_load_taps(view + (int64_t)(it.y0 + ay.i0) * it.pitch_px * 3 + col, two);
+    const PrepTaps r1 = prep_load_taps(view + (int64_t)(it.y0 + ay.i1) * it.pitch_px * 3 + col, two);
+    float n[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        n[c] = prep_normalise(prep_resample(prep_tap_level(r0, k0, c), prep_tap_level(r0, k1, c), prep_tap_level(r1, k0, c),
+                                            prep_tap_level(r1, k1, c), ax, ay), mean, std);
+    float g;
+    {
+#pragma clang fp contract(off)
+        g = __fdiv_rn((n[0] + n[1]) + n[2], 3.f);
+    }
+    float* grey = blockIdx.z == 0 ? grey1 : grey2;
+    float* patch = blockIdx.z == 0 ? patch1 : patch2;
+    grey[((int64_t)b * S + y) * S + x] = g;
+    // unsigned compares: inside the window AND inside the patch buffer whatever the descriptor holds
+    const unsigned px = (unsigned)(x - wx), py = (unsigned)(y - wy);
+    if (px < (unsigned)P && py < (unsigned)P) patch[((int64_t)b * P + py) * P + px] = g;
+}
+
 }  // namespace
+
+extern "C" int hesic_homonet_prepare_items(const hesic_homonet_item* items, int B, int S, int P, float mean, float std, float* grey1, float* grey2,
+                                           float* patch1, float* patch2, float* corners, void* stream) {
+    static_assert(sizeof(hesic_homonet_item) == 48, "hesic_homonet_item is 48 bytes");
+    HESIC_CHECK_ARG(items && grey1 && grey2 && patch1 && patch2 && corners, "homonet_prepare_items: null pointer");
+    HESIC_CHECK_ARG(B >= 1 && B <= 65535, "homonet_prepare_items: bad shape B=%d", B);
+    HESIC_CHECK_ARG(S >= 1 && S <= 16384 && P >= 1 && P <= S, "homonet_prepare_items: need 1 <= P <= S <= 16384, got S=%d P=%d", S, P);
+    HESIC_CHECK_ARG(std == std && mean == mean && std != 0.f, "homonet_prepare_items: std must be non-zero, mean and std not NaN");
+    HESIC_CHECK_ARG(((uintptr_t)items & 7) == 0 &&
+                        (((uintptr_t)grey1 | (uintptr_t)grey2 | (uintptr_t)patch1 | (uintptr_t)patch2 | (uintptr_t)corners) & 3) == 0,
+                    "homonet_prepare_items: misaligned pointer");
+    const dim3 grid((unsigned)cdiv64((int64_t)S * S, PREP_THREADS), (unsigned)B, 2);
+    hipLaunchKernelGGL(homonet_prepare_items_kernel, grid, dim3(PREP_THREADS), 0, (hipStream_t)stream, items, grey1, grey2, patch1, patch2, corners, S,
+                       P, mean, std);
+    HESIC_LAUNCH_RETURN("homonet_prepare_items");
+}
 
 extern "C" int hesic_homonet_prepare(const void* x1, const int64_t* xs1, const void* x2, const int64_t* xs2, const int32_t* xy, int B, int H, int W,
                                      int S, int P, float mean, float std, int dtype, float* grey1, float* grey2, float* patch1, float* patch2,

@@ -2034,6 +2034,72 @@ def homonet_prepare(x1, x2, xy, pic_size, patch_size, mean, std, out=None):
     return tuple(out)
 
 
+HOMONET_ITEM_DTYPE = [("left", "<u8"), ("right", "<u8"), ("pitch_px", "<i4"), ("rows", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("cw", "<i4"),
+                      ("ch", "<i4"), ("wx", "<i4"), ("wy", "<i4")]       # hesic_homonet_item as a numpy structured dtype (48 bytes)
+
+
+def homonet_items(batch):
+    """A zeroed host array of ``batch`` ``hesic_homonet_item`` descriptors (numpy structured, fields as in include/hesic_homonet_items.h;
+    ``left`` / ``right`` are device addresses as integers)."""
+    import numpy as np
+    return np.zeros(int(batch), dtype=np.dtype(HOMONET_ITEM_DTYPE))
+
+
+def check_homonet_items(items, S, P):
+    """The per-item conditions ``hesic_homonet_prepare_items`` leaves to its caller, on the host: ValueError names the first item that breaks one."""
+    S, P = int(S), int(P)
+    for b in range(len(items)):
+        it = {k: int(items[b][k]) for k in items.dtype.names}
+        if it["left"] == 0 or it["right"] == 0:
+            raise ValueError(f"homonet_prepare_items: item {b} has a null view pointer")
+        if it["pitch_px"] < 1 or it["rows"] < 1:
+            raise ValueError(f"homonet_prepare_items: item {b} stored image {it['rows']} x {it['pitch_px']}")
+        if it["cw"] < 1 or it["ch"] < 1:
+            raise ValueError(f"homonet_prepare_items: item {b} crop {it['ch']} x {it['cw']} (at least one pixel each way)")
+        if not (0 <= it["x0"] and it["x0"] + it["cw"] <= it["pitch_px"]):
+            raise ValueError(f"homonet_prepare_items: item {b} columns [{it['x0']}, {it['x0'] + it['cw']}) outside the stored image's "
+                             f"{it['pitch_px']}")
+        if not (0 <= it["y0"] and it["y0"] + it["ch"] <= it["rows"]):
+            raise ValueError(f"homonet_prepare_items: item {b} rows [{it['y0']}, {it['y0'] + it['ch']}) outside the stored image's {it['rows']}")
+        if not (0 <= it["wx"] <= S - P and 0 <= it["wy"] <= S - P):
+            raise ValueError(f"homonet_prepare_items: item {b} window origin ({it['wx']}, {it['wy']}) outside [0, {S - P}]")
+
+
+def homonet_prepare_items(items, pic_size, patch_size, mean, std, out=None):
+    """``hesic_homonet_prepare_items`` (include/hesic_homonet_items.h): ``items`` the HOST description of the batch -- a numpy array of
+    ``HOMONET_ITEM_DTYPE`` (``homonet_items(B)``) or its bytes as a (B, 48) uint8 CPU tensor --, whose ``left`` / ``right`` are addresses of
+    uint8 HWC images on the current device.  Every item is checked here, on the host (the C entry cannot read them); the descriptors are
+    then uploaded and one launch writes ``(grey1, grey2, patch1, patch2, corners)``, fp32, the outputs of ``homonet_prepare`` on each
+    item's crop.  ``out``: five preallocated dense fp32 tensors of those shapes."""
+    import numpy as np
+    if torch.is_tensor(items):
+        if items.is_cuda or items.dtype != torch.uint8 or items.dim() != 2 or items.shape[1] != 48 or not items.is_contiguous():
+            raise ValueError("homonet_prepare_items: items as a tensor must be a contiguous (B, 48) uint8 CPU tensor")
+        items = items.numpy().view(np.dtype(HOMONET_ITEM_DTYPE)).reshape(-1)
+    items = np.ascontiguousarray(items)
+    if items.dtype != np.dtype(HOMONET_ITEM_DTYPE) or items.ndim != 1:
+        raise ValueError("homonet_prepare_items: items must be a 1-d array of HOMONET_ITEM_DTYPE")
+    B, S, P = len(items), int(pic_size), int(patch_size)
+    if not (1 <= B <= 65535 and 1 <= P <= S <= 16384):
+        raise ValueError(f"homonet_prepare_items: need 1 <= B <= 65535 and 1 <= P <= S <= 16384, got B={B} S={S} P={P}")
+    check_homonet_items(items, S, P)
+    if not torch.cuda.is_available():
+        raise RuntimeError("hesic_amd: the HIP path needs a ROCm device (no CPU fallback)")
+    dev = out[0].device if out is not None else torch.device("cuda", torch.cuda.current_device())
+    shapes = [(B, 1, S, S), (B, 1, S, S), (B, 1, P, P), (B, 1, P, P), (B, 4, 2)]
+    if out is None:
+        out = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+    else:
+        L.require_cuda(*out)
+        for t, s in zip(out, shapes):
+            if tuple(t.shape) != s or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"homonet_prepare_items: out must be dense fp32 tensors of shapes {shapes}")
+    host = torch.from_numpy(items.view(np.uint8).reshape(B, 48)).pin_memory()        # a pinned copy: the caller may reuse ``items`` at once
+    items_dev = host.to(dev, non_blocking=True)
+    L.call("hesic_homonet_prepare_items", L.ptr(items_dev), B, S, P, float(mean), float(std), *[L.ptr(t) for t in out], L.stream())
+    return tuple(out)
+
+
 PAIR_ITEM_DTYPE = [("left", "<u8"), ("right", "<u8"), ("pitch_px", "<i4"), ("rows", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("hx", "<i4"),
                    ("hy", "<i4"), ("h_index", "<i4"), ("reserved", "<i4")]       # hesic_pair_item as a numpy structured dtype (48 bytes)
 

@@ -6,10 +6,20 @@
     --batch_size 16 --learning_rate 1e-4 --epochs 10 --rho 45 --picsize 256 --patchsize 128      QHtrain's options
     --crop H W            one random crop offset shared by both views (default: the whole image)
     --seed 0  --resume PATH|none  --out DIR  --clip-max-norm X  --skip-nonfinite
+    --cache host|device|stream  --cache-gb G  -n/--num-workers 3  --mix-sizes
 
-The host only reads and crops: a batch is stacked as uint8 and uploaded as bytes, and ``HomographyTrainer.step_pairs`` turns it into the
-net's inputs in one launch (resize, normalise, grey, random window), runs the forward, the photometric loss, the backward and Adam.  Pairs of
-one size share a batch (as in ``codec.encode_folder``).  Per epoch: shuffle and train, then the validation loss -- eval mode under
+``--cache host`` (the default): the host reads, decodes and crops every batch of every epoch on one thread; a batch is stacked as uint8
+and uploaded as bytes, and ``HomographyTrainer.step_pairs`` turns it into the net's inputs in one launch (resize, normalise, grey, random
+window), runs the forward, the photometric loss, the backward and Adam.  Pairs of one size share a batch (as in ``codec.encode_folder``).
+``--cache device``: every pair is decoded ONCE into a uint8 device arena (``pair_cache.DevicePairCache``, one per split, ``-n`` host threads,
+``--cache-gb`` its memory budget) and a batch's inputs come straight from the stored bytes in one launch
+(``DevicePairCache.homonet_batch``, include/hesic_homonet_items.h), followed by ``HomographyTrainer.step`` -- the call ``step_pairs`` ends
+in.  ``--cache stream`` keeps the files on the host (a set that does not fit): per batch ``-n`` threads read and crop, the crops are
+uploaded into a reused slab and the same kernel runs on it.  ``draw_batch`` consumes the random stream exactly as the host route does, and
+the kernel gives the host route's bits, so losses, parameters and checkpoints are the same in all three modes and a run may be resumed under
+another one.  ``--mix-sizes`` (``device`` / ``stream`` only): the net sees every view resized to ``picsize``², so pairs of ALL sizes form one
+pool instead of one group per image size -- fewer, fuller batches on a folder of mixed sizes (and other batches than without the flag).
+Per epoch: shuffle and train, then the validation loss -- eval mode under
 ``no_grad``, the mean of the per-batch losses, added up on the device and read back once --, ``DIR/checkpoint.pth.tar``, and a copy as
 ``DIR/checkpoint_best_loss.pth.tar`` when that loss is the lowest so far (QHtrain.py:121-133).
 
@@ -56,11 +66,12 @@ def _check_crop(pairs, crop):
                 raise ValueError(f"{os.path.basename(lf)}: crop {tuple(crop)} larger than the image ({h}, {w})")
 
 
-def batches(pairs, batch_size, crop, rng, shuffle):
-    """Lists of pairs that share a batch: pairs of one (cropped) size, in ``rng``'s order when ``shuffle``."""
+def batches(pairs, batch_size, crop, rng, shuffle, mix_sizes=False):
+    """Lists of pairs that share a batch: pairs of one (cropped) size -- of any size under ``mix_sizes`` --, in ``rng``'s order when
+    ``shuffle``."""
     groups = {}
     for p in pairs:
-        groups.setdefault(tuple(crop) if crop is not None else (p[2][1], p[2][0]), []).append(p)
+        groups.setdefault(() if mix_sizes else tuple(crop) if crop is not None else (p[2][1], p[2][0]), []).append(p)
     out = []
     for key in sorted(groups):
         items = list(groups[key])
@@ -89,23 +100,64 @@ def load_batch(items, crop, rng, device):
     return x1, x2
 
 
-def train_epoch(trainer, pairs, a, rng, device):
-    """One pass over ``pairs``; returns (mean training loss, steps, seconds).  The losses stay on the device until the end."""
+def draw_batch(items, crop, rng, picsize, patchsize, rho):
+    """``(origins, sizes, windows)`` of one batch for ``DevicePairCache.homonet_batch``: ``origins[i] = (y0, x0)``, ``sizes[i] = (ch, cw)``
+    (``None`` without ``crop``: the whole images), ``windows[i] = (wx, wy)``.  A pure host function that consumes ``rng`` exactly as the host
+    route does: first ``load_batch``'s draws -- per pair ``randint(0, h - ch)`` then ``randint(0, w - cw)``, only with ``crop`` --, then
+    ``homography.window_origins``' for the batch."""
+    from . import homography
+    origins, sizes = [(0, 0)] * len(items), None
+    if crop is not None:
+        ch, cw = crop
+        origins = [(rng.randint(0, h - ch), rng.randint(0, w - cw)) for _, _, (w, h) in items]
+        sizes = [(ch, cw)] * len(items)
+    return origins, sizes, homography.window_origins(len(items), None, picsize, patchsize, rho, rng)
+
+
+def cached_inputs(cache, items, a, rng):
+    """``(grey1, patch1, patch2, corners)`` of the batch ``items`` from the split's ``DevicePairCache``, one launch: what ``step_pairs`` /
+    ``evaluate_pairs`` prepare from ``load_batch``'s upload."""
+    origins, sizes, windows = draw_batch(items, a.crop, rng, a.picsize, a.patchsize, a.rho)
+    grey1, _, patch1, patch2, corners = cache.homonet_batch([cache.index_of[lf] for lf, _, _ in items], origins, sizes, windows, a.picsize,
+                                                            a.patchsize)
+    return grey1, patch1, patch2, corners
+
+
+def train_epoch(trainer, pairs, a, rng, device, cache=None):
+    """One pass over ``pairs`` (from ``cache`` when given, else read on the host); returns (mean training loss, steps, seconds).  The losses
+    stay on the device until the end."""
     total, n, t0 = torch.zeros((), device=device), 0, time.time()
-    for items in batches(pairs, a.batch_size, a.crop, rng, True):
-        x1, x2 = load_batch(items, a.crop, rng, device)
-        total += trainer.step_pairs(x1, x2, None, a.picsize, a.rho, rng)["loss"]
+    for items in batches(pairs, a.batch_size, a.crop, rng, True, cache is not None and a.mix_sizes):
+        if cache is None:
+            x1, x2 = load_batch(items, a.crop, rng, device)
+            total += trainer.step_pairs(x1, x2, None, a.picsize, a.rho, rng)["loss"]
+        else:
+            total += trainer.step(*cached_inputs(cache, items, a, rng))["loss"]
         n += 1
     return float(total) / max(n, 1), n, time.time() - t0
 
 
-def validate(trainer, pairs, a, rng, device):
+def validate(trainer, pairs, a, rng, device, cache=None):
     total, n = torch.zeros((), device=device), 0
-    for items in batches(pairs, a.batch_size, a.crop, rng, False):
-        x1, x2 = load_batch(items, a.crop, rng, device)
-        total += trainer.evaluate_pairs(x1, x2, None, a.picsize, a.rho, rng)
+    for items in batches(pairs, a.batch_size, a.crop, rng, False, cache is not None and a.mix_sizes):
+        if cache is None:
+            x1, x2 = load_batch(items, a.crop, rng, device)
+            total += trainer.evaluate_pairs(x1, x2, None, a.picsize, a.rho, rng)
+        else:
+            total += trainer.evaluate(*cached_inputs(cache, items, a, rng))
         n += 1
     return float(total) / max(n, 1)
+
+
+def build_cache(root, split, pairs, a):
+    """The split's ``DevicePairCache`` in ``--cache``'s mode, with ``index_of``: left file -> pair index (the listing is ``list_pairs``')."""
+    from . import pair_cache
+    budget = None if a.cache_gb is None else int(a.cache_gb * 2 ** 30)
+    cache = pair_cache.DevicePairCache(root, split, mode=a.cache, budget_bytes=budget, workers=a.num_workers)
+    if [f[0] for f in cache.files] != [p[0] for p in pairs]:
+        raise RuntimeError(f"homography_train: {split}: the folder changed while it was listed")
+    cache.index_of = {lf: i for i, (lf, _) in enumerate(cache.files)}
+    return cache
 
 
 def save_checkpoint(trainer, path, loss, epoch, seed):
@@ -131,12 +183,17 @@ def parser():
     p.add_argument("--out", default=".")
     p.add_argument("--clip-max-norm", type=float, default=None)
     p.add_argument("--skip-nonfinite", action="store_true")
+    p.add_argument("--cache", choices=("host", "device", "stream"), default="host",
+                   help="host: read and decode every batch; device: decode once into device memory; stream: read per batch on -n threads")
+    p.add_argument("--cache-gb", type=float, default=None, help="device-memory budget of the decoded pairs (default: half of the free memory)")
+    p.add_argument("-n", "--num-workers", type=int, default=3, help="host threads that decode image files (--cache device|stream)")
+    p.add_argument("--mix-sizes", action="store_true", help="pairs of all sizes share batches (--cache device|stream)")
     return p
 
 
 def main(argv=None, log=print):
     """Returns the epochs' records ({"epoch", "train_loss", "valid_loss", "best", "steps", "seconds_per_step"}, each also logged as one JSON
-    line); 2 without a ROCm device."""
+    line; ``--cache device|stream`` add "cache" and, in the run's first record, "decode_seconds"); 2 without a ROCm device."""
     from . import homography, train
     p = parser()
     a = p.parse_args(argv)
@@ -146,6 +203,10 @@ def main(argv=None, log=print):
         p.error("--patchsize must be a multiple of 8, at most --picsize")
     if a.rho < 0:
         p.error("--rho must not be negative")
+    if a.mix_sizes and a.cache == "host":
+        p.error("--mix-sizes needs --cache device or --cache stream (the host route uploads a batch as one tensor of one size)")
+    if a.num_workers < 1 or (a.cache_gb is not None and a.cache_gb <= 0):
+        p.error("--num-workers and --cache-gb must be positive")
     if not torch.cuda.is_available():
         print("homography_train: needs a ROCm device (the training kernels have no CPU path)", file=sys.stderr)
         return 2
@@ -172,10 +233,14 @@ def main(argv=None, log=print):
             best_loss = min(best_loss, float(torch.load(prev_best, map_location="cpu")["loss"]))
             if prev_best.resolve() != best.resolve() and not best.is_file():
                 shutil.copyfile(prev_best, best)
+    tcache = vcache = None
+    if a.cache != "host" and first_epoch < a.epochs:
+        tcache = build_cache(a.root, "train", train_pairs, a)
+        vcache = tcache if a.valid_split == "train" else build_cache(a.root, a.valid_split, valid_pairs, a)
     history = []
     for epoch in range(first_epoch, a.epochs):
-        train_loss, steps, secs = train_epoch(trainer, train_pairs, a, random.Random(f"{seed}/{epoch}"), device)
-        valid_loss = validate(trainer, valid_pairs, a, random.Random(f"{seed}/valid"), device)
+        train_loss, steps, secs = train_epoch(trainer, train_pairs, a, random.Random(f"{seed}/{epoch}"), device, tcache)
+        valid_loss = validate(trainer, valid_pairs, a, random.Random(f"{seed}/valid"), device, vcache)
         save_checkpoint(trainer, last, valid_loss, epoch, seed)
         is_best = valid_loss < best_loss
         if is_best or not best.is_file():
@@ -183,6 +248,10 @@ def main(argv=None, log=print):
             shutil.copyfile(last, best)
         rec = {"epoch": epoch, "train_loss": train_loss, "valid_loss": valid_loss, "best": bool(is_best), "steps": steps,
                "seconds_per_step": secs / max(steps, 1)}
+        if tcache is not None:
+            rec["cache"] = a.cache
+            if not history:
+                rec["decode_seconds"] = tcache.decode_seconds + (vcache.decode_seconds if vcache is not tcache else 0.0)
         history.append(rec)
         log(json.dumps(rec))
     return history

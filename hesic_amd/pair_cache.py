@@ -5,7 +5,9 @@ the sidecar matrix per item on the host, every epoch.  ``DevicePairCache`` decod
 the bytes as uint8 HWC in one device arena, the sidecar matrices ``ROOT/<split>/H/<stem>.npy|.txt`` as one fp64 (N, 9) device table, and turns
 a list of (pair, crop origin) into ``(x1, x2, h_matrix)`` with one launch (``hesic_pair_batch_gather``, include/hesic_pair_batch.h): the same
 bits ``ImageFolder`` + ``ToTensor`` give.  A set that does not fit the memory budget is served in ``"stream"`` mode instead: per batch the
-host reads and crops the bytes, uploads them into a reused staging slab and runs the same kernel on the slab.
+host reads and crops the bytes, uploads them into a reused staging slab and runs the same kernel on the slab.  ``homonet_batch`` serves
+HomographyNet the same way: its grey frames, windows and corners straight from the stored bytes in one launch
+(``hesic_homonet_prepare_items``, include/hesic_homonet_items.h), any crop per item, pairs of different sizes in one batch.
 
 ``crop_origin`` is the loader's crop rule and ``epoch_plan`` the order and crops of one epoch; both depend on nothing but their arguments.
 """
@@ -186,7 +188,10 @@ class DevicePairCache:
         self.decode_seconds = time.time() - t0
 
     def _stream_slab(self, B, ph, pw):
-        n = 2 * B * ph * pw * 3
+        return self._stream_bytes(2 * B * ph * pw * 3)
+
+    def _stream_bytes(self, n):
+        """The first ``n`` bytes of the reused device slab and of its pinned host twin, both grown when the batch at hand needs more."""
         if self._slab is None or self._slab.numel() < n:
             self._slab = torch.empty(n, dtype=torch.uint8, device=self.device)
             self._slab_host = torch.empty(n, dtype=torch.uint8).pin_memory()
@@ -234,3 +239,51 @@ class DevicePairCache:
                 it["pitch_px"], it["rows"], it["x0"], it["y0"] = pw, ph, 0, 0
         x1, x2, hm = Fn.pair_batch_gather(items, self.h_table, ph, pw, out=out)
         return x1, x2, hm, torch.tensor([self.has_h[i] for i in indices], dtype=torch.bool)
+
+    def homonet_batch(self, indices, origins, sizes, windows, pic_size, patch_size, out=None):
+        """HomographyNet's inputs ``(grey1, grey2, patch1, patch2, corners)`` of the pairs ``indices``, straight from the stored bytes in
+        one launch (``hesic_homonet_prepare_items``, include/hesic_homonet_items.h): pair ``indices[i]`` cropped at ``origins[i]`` =
+        (y0, x0) to ``sizes[i]`` = (ch, cw) -- ``sizes=None``: every whole image, at origin (0, 0) whatever ``origins`` holds --, resized to
+        ``pic_size``², with the ``patch_size``² window at ``windows[i]`` = (wx, wy).  Pairs and crops of different sizes share a batch.
+        ``"stream"`` mode reads and crops on the host, packs the crops back to back into the reused slab and runs the same kernel on it.
+        ``out``: five dense fp32 tensors to write into."""
+        from . import functional as Fn
+        from .compressai.datasets import MEAN, STD
+        indices = [int(i) for i in indices]
+        B = len(indices)
+        if B < 1 or len(windows) != B or (sizes is None and origins is not None and len(origins) != B) or \
+                (sizes is not None and (len(sizes) != B or len(origins) != B)):
+            raise ValueError(f"DevicePairCache.homonet_batch: {B} indices need as many origins, sizes and windows")
+        items = Fn.homonet_items(B)
+        for b, i in enumerate(indices):
+            if not 0 <= i < len(self):
+                raise IndexError(f"DevicePairCache.homonet_batch: pair {i} outside [0, {len(self)})")
+            h, w = self.sizes[i]
+            (y0, x0), (ch, cw) = ((0, 0), (h, w)) if sizes is None else (origins[b], sizes[b])
+            y0, x0, ch, cw = int(y0), int(x0), int(ch), int(cw)
+            if not (ch >= 1 and cw >= 1 and 0 <= x0 and x0 + cw <= w and 0 <= y0 and y0 + ch <= h):
+                raise ValueError(f"DevicePairCache.homonet_batch: crop ({ch}, {cw}) at ({y0}, {x0}) outside pair {i}'s image ({h}, {w})")
+            it = items[b]
+            it["pitch_px"], it["rows"], it["x0"], it["y0"], it["cw"], it["ch"] = w, h, x0, y0, cw, ch
+            it["wx"], it["wy"] = int(windows[b][0]), int(windows[b][1])
+        if self.mode == "device":
+            base = self.arena.data_ptr()
+            for b, i in enumerate(indices):
+                items[b]["left"], items[b]["right"] = base + self.offsets[i][0], base + self.offsets[i][1]
+        else:
+            nbytes = [int(it["ch"]) * int(it["cw"]) * 3 for it in items]
+            slab, host = self._stream_bytes(2 * sum(nbytes))
+            flat = host.numpy()
+            with ThreadPoolExecutor(max_workers=self.workers) as pool:
+                off = 0
+                for b, (a, c) in enumerate(pool.map(self._read, indices)):
+                    it = items[b]
+                    y0, x0, ch, cw, n = int(it["y0"]), int(it["x0"]), int(it["ch"]), int(it["cw"]), nbytes[b]
+                    flat[off:off + n].reshape(ch, cw, 3)[...] = a[y0:y0 + ch, x0:x0 + cw]
+                    flat[off + n:off + 2 * n].reshape(ch, cw, 3)[...] = c[y0:y0 + ch, x0:x0 + cw]
+                    it["left"], it["right"] = slab.data_ptr() + off, slab.data_ptr() + off + n
+                    it["pitch_px"], it["rows"], it["x0"], it["y0"] = cw, ch, 0, 0
+                    off += 2 * n
+            slab.copy_(host, non_blocking=True)
+            self._slab_event.record()
+        return Fn.homonet_prepare_items(items, pic_size, patch_size, float(MEAN), float(STD), out=out)

@@ -5,7 +5,11 @@
  * libhesic_hip_f16.so); an addition to HESIC_ABI_VERSION 2.  hesic_hip.h does not include this header.
  *
  * Conventions as in hesic_hip.h: DEVICE pointers, element strides, `stream` a hipStream_t, asynchronous; return 0 or a hipError_t (> 0) or
- * HESIC_EINVAL (-1), with hesic_last_error() describing the failure.  No atomics, no shared memory: the same inputs give the same bits.   */
+ * HESIC_EINVAL (-1), with hesic_last_error() describing the failure.  No atomics, no shared memory: the same inputs give the same bits.
+ *
+ * The same step for a batch whose views are STORED uint8 images, each at its own address and of its own size (a device-resident folder):
+ * hesic_homonet_prepare_items in hesic_homonet_items.h, included at the end of this header -- one kernel source, the same device functions
+ * per axis, tap and level, the same bits.                                                                                                */
 #ifndef HESIC_HOMOGRAPHY_PREP_H
 #define HESIC_HOMOGRAPHY_PREP_H
 #include <stdint.h>
@@ -39,4 +43,5 @@ int hesic_homonet_prepare(const void* x1, const int64_t* xs1, const void* x2, co
 #ifdef __cplusplus
 }
 #endif
+#include "hesic_homonet_items.h"
 #endif /* HESIC_HOMOGRAPHY_PREP_H */
