@@ -28,6 +28,7 @@ HOMOGRAPHY_NET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "he
 HOMOGRAPHY_PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_prep.h")
 HOMONET_ITEMS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homonet_items.h")
 PAIR_BATCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_batch.h")
+PAIR_AUGMENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_augment.h")
 PAIR_METRICS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_metrics.h")
 EN_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_en_train.h")
 
@@ -344,6 +345,13 @@ _PAIR_BATCH_SIGS = {
     "hesic_pair_batch_gather": ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp], _i32),
 }
 
+# include/hesic_pair_augment.h: the same gather with the descriptor's ``reserved`` word read as flip / swap bits (functional.pair_batch_gather_aug,
+# pair_cache.DevicePairCache.batch(flags=...), ``--augment`` of the folder trainers), in both libraries
+_PAIR_AUGMENT_SIGS = {
+    "hesic_pair_batch_gather_aug": ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp], _i32),
+}
+PAIR_HFLIP, PAIR_VFLIP, PAIR_SWAP = 1, 2, 4         # HESIC_PAIR_HFLIP, HESIC_PAIR_VFLIP, HESIC_PAIR_SWAP
+
 # include/hesic_pair_metrics.h: bits per likelihood map, squared error and 8-bit squared error per view as one fp64 row PER PAIR of a batch,
 # without atomics (functional.pair_metrics, models.pair_metrics, ``python -m hesic_amd.eval_folder``), in both libraries
 _PAIR_METRICS_SIGS = {
@@ -442,6 +450,13 @@ def declared_pair_batch_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_pair_augment_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_pair_augment.h (used by the pair-augmentation ABI test)."""
+    with open(PAIR_AUGMENT_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def declared_pair_metrics_symbols():
     """Every ``hesic_*`` function declared in include/hesic_pair_metrics.h (used by the pair-metrics ABI test)."""
     with open(PAIR_METRICS_HEADER_PATH) as f:
@@ -477,7 +492,7 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
         for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
                 + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()) \
-                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_HOMONET_ITEMS_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()) + list(_EN_TRAIN_SIGS.items()):
+                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_HOMONET_ITEMS_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_AUGMENT_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()) + list(_EN_TRAIN_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -2111,50 +2111,52 @@ def pair_items(batch):
     return np.zeros(int(batch), dtype=np.dtype(PAIR_ITEM_DTYPE))
 
 
-def check_pair_items(items, n_table, ph, pw):
-    """The per-item conditions ``hesic_pair_batch_gather`` leaves to its caller, on the host: ValueError names the first item that breaks one."""
+PAIR_HFLIP, PAIR_VFLIP, PAIR_SWAP = L.PAIR_HFLIP, L.PAIR_VFLIP, L.PAIR_SWAP       # the bits ``hesic_pair_batch_gather_aug`` reads in ``reserved``
+PAIR_FLAG_MASK = PAIR_HFLIP | PAIR_VFLIP | PAIR_SWAP
+
+
+def check_pair_items(items, n_table, ph, pw, flag_mask=0, name="pair_batch_gather"):
+    """The per-item conditions ``hesic_pair_batch_gather`` leaves to its caller, on the host: ValueError names the first item that breaks one.
+    ``flag_mask``: the bits ``reserved`` may hold (none for the plain entry, ``PAIR_FLAG_MASK`` for ``hesic_pair_batch_gather_aug``)."""
     for b in range(len(items)):
         it = items[b]
         if int(it["left"]) == 0 or int(it["right"]) == 0:
-            raise ValueError(f"pair_batch_gather: item {b} has a null view pointer")
+            raise ValueError(f"{name}: item {b} has a null view pointer")
         if int(it["pitch_px"]) < 1 or int(it["rows"]) < 1:
-            raise ValueError(f"pair_batch_gather: item {b} stored image {int(it['rows'])} x {int(it['pitch_px'])}")
+            raise ValueError(f"{name}: item {b} stored image {int(it['rows'])} x {int(it['pitch_px'])}")
         if not (0 <= int(it["x0"]) and int(it["x0"]) + pw <= int(it["pitch_px"])):
-            raise ValueError(f"pair_batch_gather: item {b} columns [{int(it['x0'])}, {int(it['x0']) + pw}) outside the stored image's "
+            raise ValueError(f"{name}: item {b} columns [{int(it['x0'])}, {int(it['x0']) + pw}) outside the stored image's "
                              f"{int(it['pitch_px'])}")
         if not (0 <= int(it["y0"]) and int(it["y0"]) + ph <= int(it["rows"])):
-            raise ValueError(f"pair_batch_gather: item {b} rows [{int(it['y0'])}, {int(it['y0']) + ph}) outside the stored image's "
+            raise ValueError(f"{name}: item {b} rows [{int(it['y0'])}, {int(it['y0']) + ph}) outside the stored image's "
                              f"{int(it['rows'])}")
         if not -1 <= int(it["h_index"]) < n_table:
-            raise ValueError(f"pair_batch_gather: item {b} h_index {int(it['h_index'])} outside [-1, {n_table})")
-        if int(it["reserved"]) != 0:
-            raise ValueError(f"pair_batch_gather: item {b} reserved field must be 0")
+            raise ValueError(f"{name}: item {b} h_index {int(it['h_index'])} outside [-1, {n_table})")
+        if int(it["reserved"]) & ~flag_mask:
+            raise ValueError(f"{name}: item {b} reserved field must be 0" if not flag_mask else
+                             f"{name}: item {b} reserved field {int(it['reserved'])} holds bits other than HFLIP = 1, VFLIP = 2, SWAP = 4")
 
 
-def pair_batch_gather(items, h_table, ph, pw, out=None):
-    """``hesic_pair_batch_gather`` (include/hesic_pair_batch.h): ``items`` the HOST description of the batch -- a numpy array of
-    ``PAIR_ITEM_DTYPE`` (``pair_items(B)``) or its bytes as a (B, 48) uint8 CPU tensor --, whose ``left`` / ``right`` are addresses of uint8
-    HWC images on the current device; ``h_table`` a dense fp64 (N, 9) device tensor or ``None``.  Every item is checked here, on the host
-    (the C entry cannot read them); the descriptors are then uploaded and one launch writes ``(x1, x2, h)``: (B,3,ph,pw), (B,3,ph,pw),
-    (B,3,3), fp32.  ``out``: three preallocated dense fp32 tensors of those shapes."""
+def _pair_batch_gather(name, flag_mask, items, h_table, ph, pw, out):
+    """Both gather entries: the host checks, the upload of the descriptors, one launch of ``hesic_<name>``."""
     import numpy as np
     if torch.is_tensor(items):
         if items.is_cuda or items.dtype != torch.uint8 or items.dim() != 2 or items.shape[1] != 48 or not items.is_contiguous():
-            raise ValueError("pair_batch_gather: items as a tensor must be a contiguous (B, 48) uint8 CPU tensor")
+            raise ValueError(f"{name}: items as a tensor must be a contiguous (B, 48) uint8 CPU tensor")
         items = items.numpy().view(np.dtype(PAIR_ITEM_DTYPE)).reshape(-1)
     items = np.ascontiguousarray(items)
     if items.dtype != np.dtype(PAIR_ITEM_DTYPE) or items.ndim != 1:
-        raise ValueError("pair_batch_gather: items must be a 1-d array of PAIR_ITEM_DTYPE")
+        raise ValueError(f"{name}: items must be a 1-d array of PAIR_ITEM_DTYPE")
     B, ph, pw = len(items), int(ph), int(pw)
     if B < 1 or ph < 1 or pw < 1:
-        raise ValueError(f"pair_batch_gather: bad shape B={B} ph={ph} pw={pw}")
+        raise ValueError(f"{name}: bad shape B={B} ph={ph} pw={pw}")
     n_table = 0
     if h_table is not None:
         L.require_cuda(h_table)
         if h_table.dtype != torch.float64 or h_table.dim() != 2 or h_table.shape[1] != 9 or not h_table.is_contiguous():
-            raise ValueError(f"pair_batch_gather: h_table must be a dense fp64 (N, 9) tensor, got {h_table.dtype} {tuple(h_table.shape)}")
+            raise ValueError(f"{name}: h_table must be a dense fp64 (N, 9) tensor, got {h_table.dtype} {tuple(h_table.shape)}")
         n_table = h_table.shape[0]
-    check_pair_items(items, n_table, ph, pw)
+    check_pair_items(items, n_table, ph, pw, flag_mask, name)
     if not torch.cuda.is_available():
         raise RuntimeError("hesic_amd: the HIP path needs a ROCm device (no CPU fallback)")
     dev = h_table.device if h_table is not None else (out[0].device if out is not None else torch.device("cuda", torch.cuda.current_device()))
@@ -2165,11 +2167,28 @@ def pair_batch_gather(items, h_table, ph, pw, out=None):
         L.require_cuda(*out)
         for t, s in zip(out, shapes):
             if tuple(t.shape) != s or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"pair_batch_gather: out must be dense fp32 tensors of shapes {shapes}")
+                raise ValueError(f"{name}: out must be dense fp32 tensors of shapes {shapes}")
     host = torch.from_numpy(items.view(np.uint8).reshape(B, 48)).pin_memory()        # a pinned copy: the caller may reuse ``items`` at once
     items_dev = host.to(dev, non_blocking=True)
-    L.call("hesic_pair_batch_gather", L.ptr(items_dev), L.ptr(h_table), B, ph, pw, *[L.ptr(t) for t in out], L.stream())
+    L.call("hesic_" + name, L.ptr(items_dev), L.ptr(h_table), B, ph, pw, *[L.ptr(t) for t in out], L.stream())
     return tuple(out)
+
+
+def pair_batch_gather(items, h_table, ph, pw, out=None):
+    """``hesic_pair_batch_gather`` (include/hesic_pair_batch.h): ``items`` the HOST description of the batch -- a numpy array of
+    ``PAIR_ITEM_DTYPE`` (``pair_items(B)``) or its bytes as a (B, 48) uint8 CPU tensor --, whose ``left`` / ``right`` are addresses of uint8
+    HWC images on the current device; ``h_table`` a dense fp64 (N, 9) device tensor or ``None``.  Every item is checked here, on the host
+    (the C entry cannot read them); the descriptors are then uploaded and one launch writes ``(x1, x2, h)``: (B,3,ph,pw), (B,3,ph,pw),
+    (B,3,3), fp32.  ``out``: three preallocated dense fp32 tensors of those shapes."""
+    return _pair_batch_gather("pair_batch_gather", 0, items, h_table, ph, pw, out)
+
+
+def pair_batch_gather_aug(items, h_table, ph, pw, out=None):
+    """``hesic_pair_batch_gather_aug`` (include/hesic_pair_augment.h): ``pair_batch_gather`` -- the same arguments, host checks and outputs --
+    with each item's ``reserved`` read as any combination of ``PAIR_HFLIP`` = 1 (both views mirrored left-right), ``PAIR_VFLIP`` = 2 (top-bottom)
+    and ``PAIR_SWAP`` = 4 (``x1`` from the right view, ``x2`` from the left), the homography following the pixels (``F H F``, the inverse).  Any
+    other bit raises ValueError naming the item, here on the host before any launch: the C entry cannot read the descriptors and ignores it."""
+    return _pair_batch_gather("pair_batch_gather_aug", PAIR_FLAG_MASK, items, h_table, ph, pw, out)
 
 
 # ------------------------------------------------------------------------------ HomographyNet in training mode

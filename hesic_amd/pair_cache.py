@@ -4,8 +4,10 @@ The loader's route (``compressai.datasets.ImageFolder`` behind a ``DataLoader``)
 the sidecar matrix per item on the host, every epoch.  ``DevicePairCache`` decodes every pair of ``ROOT/<split>/{left,right}/`` ONCE, keeps
 the bytes as uint8 HWC in one device arena, the sidecar matrices ``ROOT/<split>/H/<stem>.npy|.txt`` as one fp64 (N, 9) device table, and turns
 a list of (pair, crop origin) into ``(x1, x2, h_matrix)`` with one launch (``hesic_pair_batch_gather``, include/hesic_pair_batch.h): the same
-bits ``ImageFolder`` + ``ToTensor`` give.  A set that does not fit the memory budget is served in ``"stream"`` mode instead: per batch the
-host reads and crops the bytes, uploads them into a reused staging slab and runs the same kernel on the slab.  ``homonet_batch`` serves
+bits ``ImageFolder`` + ``ToTensor`` give.  The same launch flips a crop or exchanges its views, the homography with them, where the plan says
+so (``epoch_plan(..., augment=...)``, ``batch(..., flags=...)``; ``hesic_pair_batch_gather_aug``, include/hesic_pair_augment.h).  A set that
+does not fit the memory budget is served in ``"stream"`` mode instead: per batch the host reads and crops the bytes, uploads them into a
+reused staging slab and runs the same kernel on the slab.  The host ``ImageFolder`` loader does not augment.  ``homonet_batch`` serves
 HomographyNet the same way: its grey frames, windows and corners straight from the stored bytes in one launch
 (``hesic_homonet_prepare_items``, include/hesic_homonet_items.h), any crop per item, pairs of different sizes in one batch.
 
@@ -58,19 +60,40 @@ def crop_origin(rng, Himg, Wimg, ph, pw):
 
 class Plan(list):
     """``[(indices, origins)]`` of one epoch -- ``origins[i] = (y0, x0)`` of pair ``indices[i]`` -- with ``left_out`` (pairs not in ``keep``),
-    ``dropped`` (pairs of a ragged tail batch dropped under ``drop_tail``) and ``rng``, the epoch's random stream after the plan's draws."""
+    ``dropped`` (pairs of a ragged tail batch dropped under ``drop_tail``), ``rng``, the epoch's random stream after the plan's draws, and
+    ``flags``: per batch the items' augmentation bits (``AUGMENT_BITS``), a list parallel to the plan, all zeros when nothing is enabled."""
     left_out = 0
     dropped = 0
     rng = None
+    flags = ()
+
+    def augmented(self):
+        """``{name: items of the plan with that flag set}``, in ``AUGMENT_BITS`` order."""
+        return {name: sum(1 for fl in self.flags for f in fl if f & bit) for name, bit in AUGMENT_BITS.items()}
 
 
-def epoch_plan(n_pairs, sizes, batch_size, ph, pw, seed, epoch, shuffle, drop_tail, keep=None):
+AUGMENT_BITS = {"hflip": 1, "vflip": 2, "swap": 4}      # HESIC_PAIR_HFLIP, HESIC_PAIR_VFLIP, HESIC_PAIR_SWAP (include/hesic_pair_augment.h)
+
+
+def epoch_plan(n_pairs, sizes, batch_size, ph, pw, seed, epoch, shuffle, drop_tail, keep=None, augment=()):
     """The batches of one epoch over pairs ``0 .. n_pairs - 1`` with the image sizes ``sizes`` = [(height, width)].  The random stream is
     ``random.Random(f"{seed}/{epoch}")``; ``epoch=None`` is the validation stream, keyed by the seed alone (every epoch is judged on the
     same crops).  Order of the draws: the shuffle of the kept pairs (when ``shuffle``), then one ``crop_origin`` per pair in batch order.
     ``keep``: the pair indices that take part (default: all; the folder trainer leaves out pairs without a sidecar).  ``drop_tail``
-    drops a last batch of fewer than ``batch_size`` pairs.  The result depends on nothing but the arguments."""
+    drops a last batch of fewer than ``batch_size`` pairs.  The result depends on nothing but the arguments.
+
+    ``augment``: a collection drawn from ``"hflip"``, ``"vflip"``, ``"swap"`` -- the stereo-aware augmentations the gather applies
+    (``DevicePairCache.batch(flags=...)``).  The items' flags come from a SECOND stream, ``random.Random(f"{seed}/{epoch}/augment")``: one
+    ``getrandbits(1)`` per enabled flag per item, in batch order and in the order hflip, vflip, swap; so the shuffle, the crops and ``rng``
+    after the plan are the same with and without augmentation.  Validation (``epoch=None``) is never augmented: the combination is refused."""
     n_pairs, batch_size = int(n_pairs), int(batch_size)
+    augment = [augment] if isinstance(augment, str) else list(augment)
+    unknown = [a for a in augment if a not in AUGMENT_BITS]
+    if unknown:
+        raise ValueError(f"epoch_plan: augment names {unknown[0]!r}; it is drawn from {list(AUGMENT_BITS)}")
+    if augment and epoch is None:
+        raise ValueError("epoch_plan: the validation plan (epoch=None) is never augmented")
+    enabled = [bit for name, bit in AUGMENT_BITS.items() if name in augment]
     if len(sizes) != n_pairs:
         raise ValueError(f"epoch_plan: {len(sizes)} sizes for {n_pairs} pairs")
     if batch_size < 1:
@@ -81,7 +104,9 @@ def epoch_plan(n_pairs, sizes, batch_size, ph, pw, seed, epoch, shuffle, drop_ta
     rng = random.Random(f"{seed}/valid" if epoch is None else f"{seed}/{int(epoch)}")
     if shuffle:
         rng.shuffle(order)
+    arng = random.Random(f"{seed}/{int(epoch)}/augment") if enabled else None
     plan = Plan()
+    plan.flags = []
     plan.left_out = n_pairs - len(order)
     if drop_tail and len(order) % batch_size:
         plan.dropped = len(order) % batch_size
@@ -89,6 +114,7 @@ def epoch_plan(n_pairs, sizes, batch_size, ph, pw, seed, epoch, shuffle, drop_ta
     for c0 in range(0, len(order), batch_size):
         idx = order[c0:c0 + batch_size]
         plan.append((idx, [crop_origin(rng, sizes[i][0], sizes[i][1], ph, pw) for i in idx]))
+        plan.flags.append([sum(bit for bit in enabled if arng.getrandbits(1)) for _ in idx])
     plan.rng = rng
     return plan
 
@@ -200,16 +226,24 @@ class DevicePairCache:
             self._slab_event.synchronize()              # the previous batch's upload has left the pinned buffer
         return self._slab[:n], self._slab_host[:n]
 
-    def batch(self, indices, origins, ph, pw, out=None):
+    def batch(self, indices, origins, ph, pw, out=None, flags=None):
         """``(x1, x2, h, has_h)`` of the pairs ``indices`` cropped at ``origins`` = [(y0, x0)]: fp32 (B,3,ph,pw) twice, the crop-frame
         homographies (B,3,3) -- the identity where a pair has no sidecar -- and a (B,) bool host tensor telling which rows came from a
-        sidecar.  Pairs of different image sizes share a batch.  ``out``: dense fp32 ``(x1, x2, h)`` to write into."""
+        sidecar.  Pairs of different image sizes share a batch.  ``out``: dense fp32 ``(x1, x2, h)`` to write into.
+        ``flags``: per item a combination of ``AUGMENT_BITS`` (``epoch_plan(..., augment=...)``'s ``plan.flags[k]``): the crop is flipped and
+        / or its views exchanged, the homography with them, by the same single launch (``hesic_pair_batch_gather_aug``,
+        include/hesic_pair_augment.h; in ``"stream"`` mode the host uploads the plain crops and the kernel flips them on the slab).  ``None``
+        or all zeros is the plain gather, the same call as without the argument."""
         from . import functional as Fn
         indices, ph, pw = [int(i) for i in indices], int(ph), int(pw)
         B = len(indices)
         if B < 1 or len(origins) != B:
             raise ValueError(f"DevicePairCache.batch: {B} indices and {len(origins)} origins")
+        flags = [0] * B if flags is None else [int(f) for f in flags]
+        if len(flags) != B:
+            raise ValueError(f"DevicePairCache.batch: {B} indices and {len(flags)} flags")
         items = Fn.pair_items(B)
+        items["reserved"] = flags
         for b, (i, (y0, x0)) in enumerate(zip(indices, origins)):
             if not 0 <= i < len(self):
                 raise IndexError(f"DevicePairCache.batch: pair {i} outside [0, {len(self)})")
@@ -237,7 +271,8 @@ class DevicePairCache:
                 it = items[b]
                 it["left"], it["right"] = base + (2 * b) * n, base + (2 * b + 1) * n
                 it["pitch_px"], it["rows"], it["x0"], it["y0"] = pw, ph, 0, 0
-        x1, x2, hm = Fn.pair_batch_gather(items, self.h_table, ph, pw, out=out)
+        gather = Fn.pair_batch_gather_aug if any(flags) else Fn.pair_batch_gather
+        x1, x2, hm = gather(items, self.h_table, ph, pw, out=out)
         return x1, x2, hm, torch.tensor([self.has_h[i] for i in indices], dtype=torch.bool)
 
     def homonet_batch(self, indices, origins, sizes, windows, pic_size, patch_size, out=None):

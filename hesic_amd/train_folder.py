@@ -7,12 +7,20 @@
     --patch-size 256 256  -n/--num-workers 3  --save  --seed S                                                  newtrain1.py's options
     --model hesic|joint  --homography sidecar|net|surf  --homography-checkpoint PATH  --distortion mse|ms-ssim  --clip-max-norm X
     --skip-nonfinite  --graphed  --dtype bf16|f32  --cache device|stream  --cache-gb G  --valid-split test  --resume PATH|none  --out DIR
+    --augment hflip vflip swap   stereo-aware augmentation of the TRAINING batches (default: none)
 
 Every pair is decoded once into device memory (``pair_cache.DevicePairCache``; ``--cache stream`` keeps the files on the host and uploads
 crops per batch) and every batch of every epoch is one gather launch: the shared random crop, ToTensor and the homography of the crop, the
 same bits the reference's ``ImageFolder`` + ``DataLoader`` produce.  The step is ``train.Trainer.step``, or with ``--graphed``
 ``train.GraphedTrainer.step``: the gather then writes straight into the captured step's static inputs, and the ragged last batch of an epoch is
 dropped (and counted), because the captured step has one shape.
+
+``--augment``: each named augmentation is applied to a training item with probability 1/2 -- ``hflip`` / ``vflip`` mirror both views,
+``swap`` exchanges them -- by the gather launch itself (``hesic_pair_batch_gather_aug``, include/hesic_pair_augment.h), which also carries the
+homography along (``F H F`` for a flip, the inverse for a swap); ``net`` and ``surf`` read the augmented pixels.  The flags of epoch ``e`` come
+from a stream of their own, ``random.Random(f"{seed}/{e}/augment")``, so order and crops are those of a run without the option; the
+validation batches are never augmented.  Each epoch's record then holds ``augmented: {"hflip": n, "vflip": n, "swap": n}``, the items that
+got each.  Out of scope: the host ``ImageFolder`` loader and ``homography_train`` (another kernel) do not augment.
 
 ``--homography``: ``sidecar`` is newtrain1.py's ``d[2]`` (pairs without a sidecar are left out of the plan and counted: the reference's loader
 returns a 2-tuple for them and its loop cannot use them); ``net`` is newtrain1_real.py:108-129, a frozen eval-mode HomographyNet on the
@@ -81,6 +89,8 @@ def parser():
     p.add_argument("--dtype", choices=sorted(_DTYPES), default="bf16")
     p.add_argument("--cache", choices=("device", "stream"), default="device")
     p.add_argument("--cache-gb", type=float, default=None, help="device-memory budget of the decoded pairs (default: half of the free memory)")
+    p.add_argument("--augment", nargs="+", choices=("hflip", "vflip", "swap"), default=(), metavar="hflip|vflip|swap",
+                   help="flip both views / exchange them in the training batches, the homography with them (default: none)")
     p.add_argument("--valid-split", default="test")
     p.add_argument("--resume", default="none", metavar="PATH|none")
     p.add_argument("--out", default=".")
@@ -116,8 +126,8 @@ class _Homography:
             self._flags = []
 
 
-def _inputs(cache, indices, origins, ph, pw, homography, rng, out=None):
-    x1, x2, h, _ = cache.batch(indices, origins, ph, pw, out=out)
+def _inputs(cache, indices, origins, ph, pw, homography, rng, out=None, flags=None):
+    x1, x2, h, _ = cache.batch(indices, origins, ph, pw, out=out, flags=flags)
     if homography is not None:
         hm = homography(x1, x2, indices, rng)
         h = h.copy_(hm) if out is not None else hm          # under --graphed the matrix lands in the captured step's static input
@@ -129,11 +139,12 @@ def train_epoch(trainer, cache, plan, ph, pw, homography=None):
     dev = cache.device
     total, n, t0 = torch.zeros(len(TRAIN_KEYS), dtype=torch.float64, device=dev), 0, time.time()
     static = getattr(trainer, "static_inputs", None)
-    for indices, origins in plan:
+    for i, (indices, origins) in enumerate(plan):
+        flags = plan.flags[i] if plan.flags else None       # a plan made by hand carries none
         out = static() if static is not None else None
         if out is not None and out[0].shape[0] != len(indices):
             raise RuntimeError(f"train_folder: a batch of {len(indices)} for a step captured with {out[0].shape[0]}")
-        x1, x2, h = _inputs(cache, indices, origins, ph, pw, homography, plan.rng, out)
+        x1, x2, h = _inputs(cache, indices, origins, ph, pw, homography, plan.rng, out, flags)
         crit = trainer.step(x1, x2, h)
         total += torch.stack([crit[k].reshape(()).double() for k in TRAIN_KEYS])
         n += 1
@@ -257,7 +268,8 @@ def main(argv=None, log=print):
         decode = {"decode_seconds": round(tcache.decode_seconds + (vcache.decode_seconds if vcache is not tcache else 0.0), 3)}
         history = []
         for epoch in range(first_epoch, a.epochs):
-            tplan = pair_cache.epoch_plan(len(tcache), tcache.sizes, a.batch_size, ph, pw, seed, epoch, True, a.graphed, keep=keep_t)
+            tplan = pair_cache.epoch_plan(len(tcache), tcache.sizes, a.batch_size, ph, pw, seed, epoch, True, a.graphed, keep=keep_t,
+                                          augment=a.augment)
             vplan = pair_cache.epoch_plan(len(vcache), vcache.sizes, a.test_batch_size, ph, pw, seed, None, False, False, keep=keep_v)
             tr, steps, secs = train_epoch(trainer, tcache, tplan, ph, pw, homography)
             va = test_epoch(net, vcache, vplan, ph, pw, a.lmbda, a.distortion, homography)
@@ -273,6 +285,8 @@ def main(argv=None, log=print):
                    "train": tr, "valid": va, "train_loss": tr["loss"], "valid_loss": va["loss"],
                    "left_out_no_sidecar": tplan.left_out, "dropped_tail": tplan.dropped,
                    "invalid_homographies": homography.invalid if homography is not None else 0}
+            if a.augment:
+                rec["augmented"] = tplan.augmented()
             if epoch == first_epoch:
                 rec.update(decode)
             history.append(rec)

@@ -6,7 +6,7 @@ from a stereo folder -- ``ywz/mywork/newtrain6_real.py``'s loop on the device, t
 
     -e/--epochs 100  -lr/--learning-rate 1e-4  --lambda 1e-2  --batch-size 16  --test-batch-size 64  --patch-size 256 256  -n/--num-workers 3
     --save  --seed S  --homography sidecar|net|surf  --homography-checkpoint PATH  --clip-max-norm X  --skip-nonfinite  --graphed
-    --dtype bf16|f32  --cache device|stream  --cache-gb G  --valid-split test  --out DIR                          as in ``train_folder``
+    --dtype bf16|f32  --cache device|stream  --cache-gb G  --valid-split test  --out DIR  --augment hflip vflip swap    as in ``train_folder``
     --model hesic|joint  --checkpoint PATH|synthetic   the frozen model (required; ``synthetic``: the deterministic weights)
     --infer-dtype f16|bf16|f32                         the format of the frozen forward (default f16); ``--dtype`` is the enhancer's training format
     --resume PATH|none                                 a ``second_checkpoint*.pth.tar`` of this command
@@ -73,6 +73,8 @@ def parser():
     p.add_argument("--dtype", choices=sorted(_DTYPES), default="bf16", help="the enhancer's training format")
     p.add_argument("--cache", choices=("device", "stream"), default="device")
     p.add_argument("--cache-gb", type=float, default=None, help="device-memory budget of the decoded pairs (default: half of the free memory)")
+    p.add_argument("--augment", nargs="+", choices=("hflip", "vflip", "swap"), default=(), metavar="hflip|vflip|swap",
+                   help="flip both views / exchange them in the training batches, the homography with them (default: none)")
     p.add_argument("--valid-split", default="test")
     p.add_argument("--out", default=".")
     p.add_argument("--model", choices=("hesic", "joint"), default="hesic", help="the frozen model: HSIC (default) or HESIC+ (HSICJoint)")
@@ -86,11 +88,12 @@ def train_epoch(trainer, cache, plan, ph, pw, homography=None):
     """One pass over ``plan``; returns ({key: mean over the steps}, steps, seconds).  The losses stay on the device until the end."""
     total, n, t0 = torch.zeros(len(TRAIN_KEYS), dtype=torch.float64, device=cache.device), 0, time.time()
     static = getattr(trainer, "static_inputs", None)
-    for indices, origins in plan:
+    for i, (indices, origins) in enumerate(plan):
+        flags = plan.flags[i] if plan.flags else None       # a plan made by hand carries none
         out = static() if static is not None else None
         if out is not None and out[0].shape[0] != len(indices):
             raise RuntimeError(f"train_stage2: a batch of {len(indices)} for a step captured with {out[0].shape[0]}")
-        x1, x2, h = _inputs(cache, indices, origins, ph, pw, homography, plan.rng, out)
+        x1, x2, h = _inputs(cache, indices, origins, ph, pw, homography, plan.rng, out, flags)
         crit = trainer.step(x1, x2, h)
         total += torch.stack([crit[k].reshape(()).double() for k in TRAIN_KEYS])
         n += 1
@@ -215,7 +218,8 @@ def main(argv=None, log=print):
         decode = {"decode_seconds": round(tcache.decode_seconds + (vcache.decode_seconds if vcache is not tcache else 0.0), 3)}
         history = []
         for epoch in range(first_epoch, a.epochs):
-            tplan = pair_cache.epoch_plan(len(tcache), tcache.sizes, a.batch_size, ph, pw, seed, epoch, True, a.graphed, keep=keep_t)
+            tplan = pair_cache.epoch_plan(len(tcache), tcache.sizes, a.batch_size, ph, pw, seed, epoch, True, a.graphed, keep=keep_t,
+                                          augment=a.augment)
             vplan = pair_cache.epoch_plan(len(vcache), vcache.sizes, a.test_batch_size, ph, pw, seed, None, False, False, keep=keep_v)
             tr, steps, secs = train_epoch(trainer, tcache, tplan, ph, pw, homography)
             va = test_epoch(net, enhancer, vcache, vplan, ph, pw, a.lmbda, homography)
@@ -231,6 +235,8 @@ def main(argv=None, log=print):
                    "train": tr, "valid": va, "train_loss": tr["loss"], "valid_loss": va["loss"],
                    "left_out_no_sidecar": tplan.left_out, "dropped_tail": tplan.dropped,
                    "invalid_homographies": homography.invalid if homography is not None else 0}
+            if a.augment:
+                rec["augmented"] = tplan.augmented()
             if epoch == first_epoch:
                 rec.update(decode)
             history.append(rec)

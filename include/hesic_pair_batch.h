@@ -19,7 +19,7 @@ typedef struct {
     int32_t x0, y0;         /* crop origin inside the STORED image */
     int32_t hx, hy;         /* crop origin in the FULL image: the translation H is re-based by */
     int32_t h_index;        /* row of h_table, or -1: no matrix for this item */
-    int32_t reserved;       /* 0 */
+    int32_t reserved;       /* 0 (hesic_pair_augment.h's entry reads its flip / swap bits here) */
 } hesic_pair_item;          /* 48 bytes */
 
 /* items: B descriptors in DEVICE memory (8-byte aligned).  The stored image and the full image differ when the caller uploads only the crop
