@@ -166,16 +166,6 @@ def clear_grad_slots(keys=None):
 
 
 _slots_active = False
-_wgrad_stream = None
-
-
-def set_wgrad_stream(stream):
-    """Stream for the weight-gradient launches of the flat-slot path (``_wide_conv_grads``); None = the current stream.  The caller
-    joins it back (``current_stream().wait_stream(stream)``) before anything reads the flat gradient buffer."""
-    global _wgrad_stream
-    prev, _wgrad_stream = _wgrad_stream, stream
-    return prev
-
 
 
 # Deferred finishing passes of the wide weight gradients (see _wide_conv_grads): a list while train.Trainer.step collects them
@@ -609,23 +599,8 @@ def _wide_conv_grads(x, weight, gy, cfg, dims, has_bias, need_dx, need_dw, bias=
         nws = L.lib().hesic_conv2d_wgrad_ws_bytes(C.byref(d))
         ws_, bs_ = _slot_for(weight), (_slot_for(bias) if has_bias else None)
         if ws_ is not None and weight.dtype == torch.float32 and (not has_bias or bs_ is not None) and (mask is None or tap_mask):
-            # flat gradient buffer: the finishing kernel adds dW (PyTorch layout) and dbias into the slots.  Nothing downstream in
-            # the backward pass reads a weight gradient, so with a weight-gradient stream set (train.Trainer) the two launches go
-            # there: the chain of data gradients -- the critical path of the step -- does not wait for them, and they fill the gaps
-            # between its launches.  ONE such stream: the two gradients of a twice-used weight (encoder1) add into their slot in order.
-            side = _wgrad_stream if x.is_cuda else None
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream())
-                x.record_stream(side)
-                gy.record_stream(side)
-                with torch.cuda.stream(side):
-                    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
-                    L.call("hesic_conv2d_wgrad_direct", C.byref(d), L.ptr(x), L.ptr(gy), L.ptr(ws_.grad), L.ptr(bs_.grad if has_bias else None), 1,
-                           L.ptr(ws), nws, L.stream())
-                    _slot_done(ws_)
-                    if has_bias:
-                        _slot_done(bs_)
-                return dx, None, None
+            # flat gradient buffer: the finishing kernel adds dW (PyTorch layout) and dbias into the slots, on the stream of the backward
+            # pass: the two gradients of a twice-used weight (encoder1) add into their slot in order
             nsp = 0
             if _finish_queue is not None and WGRAD_PARTIAL_BATCH:
                 # the shared-grid route: its own (smaller) K-slice count, named to both batched calls; the workspace is sized for it

@@ -45,6 +45,8 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from .folder_loop import resume_position
+
 
 def list_pairs(root, split):
     """[(left path, right path, (width, height))] of ROOT/<split>, in sorted order."""
@@ -222,17 +224,11 @@ def main(argv=None, log=print):
     out = Path(a.out)
     out.mkdir(parents=True, exist_ok=True)
     last, best = out / "checkpoint.pth.tar", out / "checkpoint_best_loss.pth.tar"
-    first_epoch, best_loss = 0, float("inf")
     if resume is not None:
         trainer.load_state_dict({"state_dict": homography.net_state_dict(resume["state_dict"]), "optimizer": resume["optimizer"],
                                  "dropout": resume["dropout"]})
         trainer.set_lr(a.learning_rate)
-        first_epoch, best_loss = int(resume["epoch"]) + 1, float(resume["loss"])
-        prev_best = Path(a.resume).with_name(best.name)
-        if prev_best.is_file():
-            best_loss = min(best_loss, float(torch.load(prev_best, map_location="cpu")["loss"]))
-            if prev_best.resolve() != best.resolve() and not best.is_file():
-                shutil.copyfile(prev_best, best)
+    first_epoch, best_loss = resume_position(resume, a.resume, best, True)      # this command always saves
     tcache = vcache = None
     if a.cache != "host" and first_epoch < a.epochs:
         tcache = build_cache(a.root, "train", train_pairs, a)

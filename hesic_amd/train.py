@@ -239,7 +239,7 @@ class FlatReducer:
         up = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(process_group) if up else 1
         self.buckets, self._work, self._expected, self._events = [], [], None, [0] * len(group.params)
-        self.compute_stream = self.side_stream = None
+        self.compute_stream = None
         # ``force``: issue the collectives even in a 1-rank group (a 1-GPU box can then exercise RCCL bring-up and the capture
         # of the all-reduces into the step's HIP graph)
         self.active = self.world > 1 or (force and up)
@@ -312,12 +312,10 @@ class FlatReducer:
         op = dist.ReduceOp.AVG if self.avg_op else dist.ReduceOp.SUM
         buf = self.group.flat_g[b["lo"]:b["hi"]]
         if buf.is_cuda:
-            # a bucket's gradients are written on the compute stream AND (weight gradients, train.Trainer) on ``side_stream``: the
-            # stream the collective is issued from waits for both
+            # a bucket's gradients are written on the compute stream: the stream the collective is issued from waits for it
             cur = torch.cuda.current_stream()
-            for st in (self.compute_stream, self.side_stream):
-                if st is not None and st != cur:
-                    cur.wait_stream(st)
+            if self.compute_stream is not None and self.compute_stream != cur:
+                cur.wait_stream(self.compute_stream)
         if self.timing and self.avg_op and buf.is_cuda:
             if self._comm is None:
                 self._comm = torch.cuda.Stream(device=buf.device)
@@ -376,7 +374,28 @@ class FlatReducer:
             self._expected = [e if e > 0 else -1 for e in self._events]
 
 
-WGRAD_STREAM = False      # module switch (off): weight gradients on a stream of their own -- measured 12.34 vs 12.28 ms at B=8 512^2: the step is not gap-bound
+def _step_controls(cls, clip_max_norm, skip_nonfinite, live_lr):
+    """The step controls of the trainer class named ``cls``, checked and normalised: ``(clip_max_norm as a float or None, skip_nonfinite,
+    live_lr)``.  Called first in a constructor: a bad argument is refused before any device or dtype check."""
+    if clip_max_norm is not None:
+        import math
+        ok = isinstance(clip_max_norm, (int, float)) and not isinstance(clip_max_norm, bool)
+        if not ok or not math.isfinite(clip_max_norm) or clip_max_norm <= 0:
+            raise ValueError(f"{cls}: clip_max_norm must be a finite positive number (or None: no clipping), got {clip_max_norm!r}")
+        clip_max_norm = float(clip_max_norm)
+    for name, flag in (("skip_nonfinite", skip_nonfinite), ("live_lr", live_lr)):
+        if not isinstance(flag, bool):
+            raise TypeError(f"{cls}: {name} must be a bool, got {type(flag).__name__}")
+    return clip_max_norm, skip_nonfinite, live_lr
+
+
+def _control_readout(optimizer, skipped_from=None):
+    """``{"grad_norm", "clip_coef", "skipped"}`` of ``optimizer``'s control block: views while a graph is captured (every replay refreshes them),
+    copies otherwise.  ``skipped_from``: the optimiser whose block holds the count (default: ``optimizer`` itself)."""
+    from . import _lib as L
+    own = (lambda t: t) if torch.cuda.is_current_stream_capturing() else torch.clone
+    ctl, counts = optimizer.ctl, (optimizer if skipped_from is None else skipped_from).ctl
+    return {"grad_norm": own(ctl[L.CTL_GRAD_NORM]), "clip_coef": own(ctl[L.CTL_CLIP_COEF]), "skipped": own(counts[L.CTL_SKIPPED])}
 
 
 class Trainer:
@@ -405,15 +424,7 @@ class Trainer:
                  distortion="mse", clip_max_norm=None, skip_nonfinite=False, live_lr=False):
         if distortion not in Fn.DISTORTIONS:
             raise ValueError(f"Trainer: distortion must be one of {Fn.DISTORTIONS}, got {distortion!r}")
-        if clip_max_norm is not None:
-            import math
-            ok = isinstance(clip_max_norm, (int, float)) and not isinstance(clip_max_norm, bool)
-            if not ok or not math.isfinite(clip_max_norm) or clip_max_norm <= 0:
-                raise ValueError(f"Trainer: clip_max_norm must be a finite positive number (or None: no clipping), got {clip_max_norm!r}")
-            clip_max_norm = float(clip_max_norm)
-        for name, flag in (("skip_nonfinite", skip_nonfinite), ("live_lr", live_lr)):
-            if not isinstance(flag, bool):
-                raise TypeError(f"Trainer: {name} must be a bool, got {type(flag).__name__}")
+        clip_max_norm, skip_nonfinite, live_lr = _step_controls("Trainer", clip_max_norm, skip_nonfinite, live_lr)
         self.clip_max_norm, self.skip_nonfinite, self.live_lr = clip_max_norm, skip_nonfinite, live_lr
         self.controls = clip_max_norm is not None or skip_nonfinite or live_lr
         # "ms-ssim": loss = lmbda * ((1 - MS-SSIM(x1_hat, x1)) + (1 - MS-SSIM(x2_hat, x2))) + bpp (functional.rd_loss); lmbda has no 255^2
@@ -496,15 +507,7 @@ class Trainer:
         prev = Fn.train_pack_cache(True)          # packed conv weights persist across the step, one batched repack below
         scaled, Fn.SCALED_LOSS = Fn.SCALED_LOSS, False     # backward() starts at the unscaled loss: no g_loss multiplies
         slots = Fn.grad_slots_active(True)        # gradient kernels add straight into the flat buffer (cleared above) for THIS step only
-        wst = None
-        if self.on_gpu and WGRAD_STREAM:
-            if getattr(self, "_wstream", None) is None:
-                self._wstream = torch.cuda.Stream(device=self.main_group.flat_p.device)
-            wst = self._wstream
-            wst.wait_stream(torch.cuda.current_stream())       # behind zero_grad
-            self.main_reducer.side_stream = wst
-        wprev = Fn.set_wgrad_stream(wst)
-        defer = Fn.defer_wgrad_finish(self.on_gpu and wst is None)     # finishing passes of the weight gradients: batches of 8 layers per launch
+        defer = Fn.defer_wgrad_finish(self.on_gpu)     # finishing passes of the weight gradients: batches of 8 layers per launch
         try:
             crit = self._forward_loss(x1, x2, h_matrix, noise)
             crit["loss"].backward()
@@ -513,9 +516,6 @@ class Trainer:
             Fn.train_pack_cache(prev)
             Fn.SCALED_LOSS = scaled
             Fn.grad_slots_active(slots)
-            Fn.set_wgrad_stream(wprev)
-            if wst is not None:
-                torch.cuda.current_stream().wait_stream(wst)    # every weight gradient is in the flat buffer from here on
         self.main_reducer.finish()
         if self.controls and not self.on_gpu:
             self._host_step(aux=False)
@@ -539,19 +539,79 @@ class Trainer:
         crit = {k: v.detach() for k, v in crit.items()}
         crit["aux_loss"] = aux.detach()
         if self.controls and self.on_gpu:
-            from . import _lib as L
-            # views of the control blocks while a graph is captured (every replay refreshes them), copies otherwise; the count is the aux
-            # block's: it includes the steps the main group withheld
-            own = (lambda t: t) if torch.cuda.is_current_stream_capturing() else torch.clone
-            crit["grad_norm"], crit["clip_coef"] = own(self.optimizer.ctl[L.CTL_GRAD_NORM]), own(self.optimizer.ctl[L.CTL_CLIP_COEF])
-            crit["skipped"] = own(self.aux_optimizer.ctl[L.CTL_SKIPPED])
+            crit.update(_control_readout(self.optimizer, self.aux_optimizer))    # the aux block's count includes the steps the main group withheld
         elif self.controls:
             st = self._host_stats
             crit["grad_norm"], crit["clip_coef"], crit["skipped"] = st["grad_norm"], st["clip_coef"], torch.tensor(float(st["skipped"]))
         return crit
 
 
-class GraphedTrainer(Trainer):
+class _GraphedStep:
+    """A step recorded once into a HIP graph and replayed: the base of ``GraphedTrainer`` and ``GraphedEnhancerTrainer``, listed BEFORE the
+    eager trainer whose ``step`` and ``set_lr`` it wraps (``super()`` here is that trainer).
+
+    The first ``warmup`` calls run eagerly on a side stream (real steps), the next call captures, every later call is a copy of the inputs into
+    the static buffers -- nothing, when the producer wrote into ``static_inputs()`` -- plus one graph launch.  A subclass's ``step`` stages,
+    syncs the learning rate, may drop a stale graph, and ends in ``_run``; ``_captured`` and ``_replayed`` are its hooks.  Without step
+    controls the captured Adam holds its learning rate by value and ``set_lr`` refuses after the capture."""
+
+    _ADAM = "Adam launch"       # how ``set_lr``'s refusal names the captured optimiser work
+
+    def _init_graph(self, warmup, why):
+        if int(warmup) < 1:
+            raise ValueError(f"{type(self).__name__}: warmup >= 1 ({why})")
+        self.warmup, self.calls, self.graph = int(warmup), 0, None
+        self._in = self._out = None
+
+    def set_lr(self, *rates, **kw):
+        if self.graph is not None and not self.controls:
+            raise RuntimeError(f"{type(self).__name__}.set_lr: the captured step holds its learning rate by value in the kernel arguments of "
+                               f"its {self._ADAM}, a replay cannot see a new one -- build the trainer with live_lr=True (the rate is then "
+                               "read from device memory by every replay)")
+        super().set_lr(*rates, **kw)
+
+    def static_inputs(self):
+        """The step's static input tensors ``(x1, x2, h_matrix)``, or ``None`` before the first step.  A producer that writes a batch straight
+        into them and passes them to ``step`` saves the staging copies: ``_stage`` finds equal pointers and copies nothing."""
+        return self._in
+
+    def _stage(self, *inputs):
+        if self._in is None:
+            self._in = tuple(t.clone() for t in inputs)
+        else:
+            for dst, src in zip(self._in, inputs):
+                if src.data_ptr() != dst.data_ptr():
+                    dst.copy_(src)
+
+    def _captured(self):
+        pass
+
+    def _run(self, **kw):
+        """Count the call, then the eager step on the static inputs -- on a side stream (warm-up) or under capture -- or a replay."""
+        self.calls += 1
+        if self.graph is None and self.calls <= self.warmup:
+            side = torch.cuda.Stream(device=self._in[0].device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                out = super().step(*self._in, **kw)
+            torch.cuda.current_stream().wait_stream(side)
+            return out
+        if self.graph is None:
+            self.graph = torch.cuda.CUDAGraph()
+            # The process group's watchdog thread polls the events of the warm-up steps' collectives; under the default ("global")
+            # capture mode such a query from ANOTHER thread while this one captures is an error that takes the process down
+            # ("operation not permitted when stream is capturing", seen with one RCCL rank).  Drain first, and confine the capture
+            # rules to this thread.
+            torch.cuda.synchronize()
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                self._out = super().step(*self._in, **kw)
+            self._captured()
+        self.graph.replay()
+        self._replayed()            # a replay runs no Python: the captured Adam moved the parameters without touching their version counters
+        return self._out
+
+
+class GraphedTrainer(_GraphedStep, Trainer):
     """``Trainer.step`` recorded once into a HIP graph and replayed -- with a process group up, one graph per rank with the
     bucketed RCCL all-reduces inside it (collectives are stream work like any kernel; their forked comm-stream nodes keep the
     overlap with the backward pass in the graph).
@@ -570,15 +630,14 @@ class GraphedTrainer(Trainer):
     one that asks for nothing else) the rate lives in the control block: ``set_lr`` and writes to ``param_groups`` are picked up before
     every replay by a device fill outside the graph."""
 
+    _ADAM = "Adam launches"
+
     def __init__(self, model, *args, warmup=3, **kw):
         super().__init__(model, *args, **kw)
         if not self.on_gpu:
             raise RuntimeError("GraphedTrainer needs the model on a ROCm device")
-        if int(warmup) < 1:
-            raise ValueError("GraphedTrainer: warmup >= 1 (the packed-weight registry and the reducer's write counts are created by an "
-                             "eager step)")
-        self.warmup, self.calls, self.graph = int(warmup), 0, None
-        self._in = self._noise = self._out = None
+        self._init_graph(warmup, "the packed-weight registry and the reducer's write counts are created by an eager step")
+        self._noise = None
         # only RCCL's collectives are stream work; gloo stages through the host (synchronises) and cannot be captured
         self.capturable = not (self.main_reducer.active and not self.main_reducer.avg_op)
         if not self.capturable:
@@ -586,31 +645,21 @@ class GraphedTrainer(Trainer):
             warnings.warn("GraphedTrainer: the process group's backend is not nccl/RCCL -- its collectives cannot be captured into a HIP "
                           "graph, steps run eagerly")
 
-    def set_lr(self, lr, aux_lr=None):
-        if self.graph is not None and not self.controls:
-            raise RuntimeError("GraphedTrainer.set_lr: the captured step holds its learning rate by value in the kernel arguments of its "
-                               "Adam launches, a replay cannot see a new one -- build the trainer with live_lr=True (the rate is then "
-                               "read from device memory by every replay)")
-        super().set_lr(lr, aux_lr)
-
-    def static_inputs(self):
-        """The step's static input tensors ``(x1, x2, h_matrix)``, or ``None`` before the first step.  A producer that writes a batch straight
-        into them and passes them to ``step`` saves the staging copies: ``_stage`` finds equal pointers and copies nothing."""
-        return self._in
-
     def _stage(self, x1, x2, h_matrix, noise):
-        if self._in is None:
-            self._in = (x1.clone(), x2.clone(), h_matrix.clone())
+        first = self._in is None
+        super()._stage(x1, x2, h_matrix)
+        if first:
             self._noise = None if noise is None else {k: v.clone() for k, v in noise.items()}
-        else:
-            for dst, src in zip(self._in, (x1, x2, h_matrix)):
-                if src.data_ptr() != dst.data_ptr():
-                    dst.copy_(src)
-            if self._noise is not None:
-                if noise is None:
-                    raise RuntimeError("GraphedTrainer: the step was captured with explicit noise tensors")
-                for k, dst in self._noise.items():
-                    dst.copy_(noise[k])
+        elif self._noise is not None:
+            if noise is None:
+                raise RuntimeError("GraphedTrainer: the step was captured with explicit noise tensors")
+            for k, dst in self._noise.items():
+                dst.copy_(noise[k])
+
+    def _replayed(self):
+        # every cache keyed on the parameters' version counters (bottleneck tables, packed GDN parameters, inference weight packs) must
+        # start a new epoch
+        Fn.invalidate_weight_cache()
 
     def step(self, x1, x2, h_matrix, noise=None):
         if not self.capturable:
@@ -618,28 +667,7 @@ class GraphedTrainer(Trainer):
         self._check_inputs(x1, x2)
         self._stage(x1, x2, h_matrix, noise)
         self._sync_lr()                           # control path: this call's rate, filled in ahead of the capture / the replay
-        self.calls += 1
-        if self.graph is None and self.calls <= self.warmup:
-            side = torch.cuda.Stream(device=x1.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                out = super().step(*self._in, noise=self._noise)
-            torch.cuda.current_stream().wait_stream(side)
-            return out
-        if self.graph is None:
-            self.graph = torch.cuda.CUDAGraph()
-            # The process group's watchdog thread polls the events of the warm-up steps' collectives; under the default ("global")
-            # capture mode such a query from ANOTHER thread while this one captures is an error that takes the process down
-            # ("operation not permitted when stream is capturing", seen with one RCCL rank).  Drain first, and confine the capture
-            # rules to this thread.
-            torch.cuda.synchronize()
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self._out = super().step(*self._in, noise=self._noise)
-        self.graph.replay()
-        # a replay runs no Python: the captured Adam kernels moved the parameters without touching their version counters, so
-        # every cache keyed on them (bottleneck tables, packed GDN parameters, inference weight packs) must start a new epoch
-        Fn.invalidate_weight_cache()
-        return self._out
+        return self._run(noise=self._noise)
 
 
 class HomographyTrainer:
@@ -657,15 +685,7 @@ class HomographyTrainer:
     mask forever.  ``step`` raises while a stream is capturing."""
 
     def __init__(self, net, lr=1e-4, seed=0, clip_max_norm=None, skip_nonfinite=False, live_lr=False):
-        if clip_max_norm is not None:
-            import math
-            ok = isinstance(clip_max_norm, (int, float)) and not isinstance(clip_max_norm, bool)
-            if not ok or not math.isfinite(clip_max_norm) or clip_max_norm <= 0:
-                raise ValueError(f"HomographyTrainer: clip_max_norm must be a finite positive number (or None: no clipping), got {clip_max_norm!r}")
-            clip_max_norm = float(clip_max_norm)
-        for name, flag in (("skip_nonfinite", skip_nonfinite), ("live_lr", live_lr)):
-            if not isinstance(flag, bool):
-                raise TypeError(f"HomographyTrainer: {name} must be a bool, got {type(flag).__name__}")
+        clip_max_norm, skip_nonfinite, live_lr = _step_controls("HomographyTrainer", clip_max_norm, skip_nonfinite, live_lr)
         if getattr(net, "dtype", torch.float32) != torch.float32:
             raise NotImplementedError("HomographyTrainer: the net must store fp32 maps (Net(dtype=torch.float32))")
         self.net = net
@@ -684,7 +704,6 @@ class HomographyTrainer:
 
     def step(self, img_a, patch_a, patch_b, corners):
         """zero the flat gradient -> train-mode forward -> photometric loss -> backward -> one Adam launch.  Returns device scalars."""
-        from . import _lib as L
         from . import homography
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("HomographyTrainer.step is eager: the dropout step counter is passed to the kernels by value, a captured "
@@ -711,8 +730,7 @@ class HomographyTrainer:
             Fn.set_compute_dtype(prev_dtype)
         out = {"loss": loss.detach()}
         if self.controls:
-            ctl = self.optimizer.ctl
-            out["grad_norm"], out["clip_coef"], out["skipped"] = ctl[L.CTL_GRAD_NORM].clone(), ctl[L.CTL_CLIP_COEF].clone(), ctl[L.CTL_SKIPPED].clone()
+            out.update(_control_readout(self.optimizer))         # copies: this step never runs under capture
         return out
 
     @torch.no_grad()
@@ -849,15 +867,7 @@ class EnhancerTrainer:
     give equal bits."""
 
     def __init__(self, model, enhancer, lr=1e-4, lmbda=1e-2, train_dtype=None, clip_max_norm=None, skip_nonfinite=False, live_lr=False):
-        if clip_max_norm is not None:
-            import math
-            ok = isinstance(clip_max_norm, (int, float)) and not isinstance(clip_max_norm, bool)
-            if not ok or not math.isfinite(clip_max_norm) or clip_max_norm <= 0:
-                raise ValueError(f"EnhancerTrainer: clip_max_norm must be a finite positive number (or None: no clipping), got {clip_max_norm!r}")
-            clip_max_norm = float(clip_max_norm)
-        for name, flag in (("skip_nonfinite", skip_nonfinite), ("live_lr", live_lr)):
-            if not isinstance(flag, bool):
-                raise TypeError(f"EnhancerTrainer: {name} must be a bool, got {type(flag).__name__}")
+        clip_max_norm, skip_nonfinite, live_lr = _step_controls("EnhancerTrainer", clip_max_norm, skip_nonfinite, live_lr)
         if train_dtype is None and Fn.compute_dtype() == torch.float16:
             train_dtype = torch.bfloat16
         if train_dtype not in (None, torch.bfloat16, torch.float32):
@@ -926,15 +936,12 @@ class EnhancerTrainer:
         res = {"loss": crit["loss"].detach(), "mse_loss": crit["mse_loss"].detach()}
         self.optimizer.step()
         if self.controls:
-            from . import _lib as L
-            own = (lambda t: t) if torch.cuda.is_current_stream_capturing() else torch.clone
-            ctl = self.optimizer.ctl
-            res["grad_norm"], res["clip_coef"], res["skipped"] = own(ctl[L.CTL_GRAD_NORM]), own(ctl[L.CTL_CLIP_COEF]), own(ctl[L.CTL_SKIPPED])
+            res.update(_control_readout(self.optimizer))
         return res
 
 
-class GraphedEnhancerTrainer(EnhancerTrainer):
-    """``EnhancerTrainer.step`` recorded once into a HIP graph and replayed, by ``GraphedTrainer``'s protocol: the first ``warmup`` calls run
+class GraphedEnhancerTrainer(_GraphedStep, EnhancerTrainer):
+    """``EnhancerTrainer.step`` recorded once into a HIP graph and replayed, by ``GraphedTrainer``'s protocol (``_GraphedStep``): the first ``warmup`` calls run
     eagerly on a side stream (real steps), the next call captures, every later call copies the inputs into the static buffers (nothing, when the
     producer wrote into ``static_inputs()``) and launches the graph.  The returned dict holds the graph's static tensors (overwritten by the
     next call).  Without step controls the captured Adam holds its learning rate by value and ``set_lr`` refuses after the capture; with any of
@@ -945,29 +952,17 @@ class GraphedEnhancerTrainer(EnhancerTrainer):
 
     def __init__(self, model, enhancer, *args, warmup=3, **kw):
         super().__init__(model, enhancer, *args, **kw)
-        if int(warmup) < 1:
-            raise ValueError("GraphedEnhancerTrainer: warmup >= 1 (workspaces and the frozen model's packed weights are created by an eager step)")
-        self.warmup, self.calls, self.graph = int(warmup), 0, None
-        self._in = self._out = self._epoch = None
+        self._init_graph(warmup, "workspaces and the frozen model's packed weights are created by an eager step")
+        self._epoch = None
 
-    def set_lr(self, lr):
-        if self.graph is not None and not self.controls:
-            raise RuntimeError("GraphedEnhancerTrainer.set_lr: the captured step holds its learning rate by value in the kernel arguments of its "
-                               "Adam launch, a replay cannot see a new one -- build the trainer with live_lr=True (the rate is then read from "
-                               "device memory by every replay)")
-        super().set_lr(lr)
+    def _captured(self):
+        self._epoch = Fn._epoch_n
 
-    def static_inputs(self):
-        """The step's static input tensors ``(x1, x2, h_matrix)``, or ``None`` before the first step (see ``GraphedTrainer.static_inputs``)."""
-        return self._in
-
-    def _stage(self, x1, x2, h_matrix):
-        if self._in is None:
-            self._in = (x1.clone(), x2.clone(), h_matrix.clone())
-        else:
-            for dst, src in zip(self._in, (x1, x2, h_matrix)):
-                if src.data_ptr() != dst.data_ptr():
-                    dst.copy_(src)
+    def _replayed(self):
+        # Bump the version counters, as the eager ``FlatAdam.step`` does: every cache keyed on the ENHANCER's parameters misses from here on.
+        # ``GraphedTrainer`` starts a new global cache epoch instead; here that would also drop the FROZEN model's packed weights, which the
+        # graph reads by address (see above).
+        torch.autograd.graph.increment_version(self.group.params)
 
     def step(self, x1, x2, h_matrix):
         self._stage(x1, x2, h_matrix)
@@ -976,23 +971,4 @@ class GraphedEnhancerTrainer(EnhancerTrainer):
             # Somebody started a new pack-cache epoch (``invalidate_weight_cache``) since the capture: the frozen model's next eager forward
             # replaces -- and frees -- the packed weights this graph reads.  Drop the graph: one eager step re-packs, the next call captures.
             self.graph, self._out, self.calls = None, None, self.warmup - 1
-        self.calls += 1
-        if self.graph is None and self.calls <= self.warmup:
-            side = torch.cuda.Stream(device=x1.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                out = super().step(*self._in)
-            torch.cuda.current_stream().wait_stream(side)
-            return out
-        if self.graph is None:
-            self.graph = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self._out = super().step(*self._in)
-            self._epoch = Fn._epoch_n
-        self.graph.replay()
-        # A replay runs no Python: the captured Adam moved the parameters without touching their version counters.  Bump them, as the eager
-        # ``FlatAdam.step`` does: every cache keyed on the ENHANCER's parameters misses from here on.  ``GraphedTrainer`` starts a new global
-        # cache epoch instead; here that would also drop the FROZEN model's packed weights, which the graph reads by address (see above).
-        torch.autograd.graph.increment_version(self.group.params)
-        return self._out
+        return self._run()
