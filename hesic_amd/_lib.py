@@ -27,6 +27,7 @@ HOMOGRAPHY_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "
 HOMOGRAPHY_NET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_net.h")
 HOMOGRAPHY_PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_prep.h")
 HOMONET_ITEMS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homonet_items.h")
+HOMONET_SYNTH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homonet_synth.h")
 PAIR_BATCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_batch.h")
 PAIR_AUGMENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_augment.h")
 PAIR_METRICS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_metrics.h")
@@ -333,6 +334,19 @@ _HOMONET_ITEMS_SIGS = {
 }
 
 
+# include/hesic_homonet_synth.h: synthetic-warp pairs with their label from one stored view (functional.homonet_synth,
+# pair_cache.DevicePairCache.homonet_synth_batch, ``python -m hesic_amd.homography_train --supervision synthetic``, ``python -m
+# hesic_amd.homography_eval``), in both libraries
+class HomonetSynthItem(C.Structure):
+    """hesic_homonet_synth_item (72 bytes)."""
+    _fields_ = [("view", C.c_uint64)] + [(n, _i32) for n in ("pitch_px", "rows", "x0", "y0", "cw", "ch", "wx", "wy")] + [("delta", _i32 * 8)]
+
+
+_HOMONET_SYNTH_SIGS = {
+    "hesic_homonet_synth_items": ([_vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+}
+
+
 # include/hesic_pair_batch.h: a batch of stereo crops gathered from uint8 images resident on the device, with the re-based homographies, in one
 # launch (functional.pair_batch_gather, pair_cache.DevicePairCache.batch, ``python -m hesic_amd.train_folder``), in both libraries
 class PairItem(C.Structure):
@@ -443,6 +457,13 @@ def declared_homonet_items_symbols():
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_homonet_synth_symbols():
+    """Every ``hesic_*`` function declared in include/hesic_homonet_synth.h (used by the synthetic-warp ABI test)."""
+    with open(HOMONET_SYNTH_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+
+
 def declared_pair_batch_symbols():
     """Every ``hesic_*`` function declared in include/hesic_pair_batch.h (used by the pair-batch ABI test)."""
     with open(PAIR_BATCH_HEADER_PATH) as f:
@@ -492,7 +513,7 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
         for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
                 + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()) \
-                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_HOMONET_ITEMS_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_AUGMENT_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()) + list(_EN_TRAIN_SIGS.items()):
+                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_HOMONET_ITEMS_SIGS.items()) + list(_HOMONET_SYNTH_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_AUGMENT_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()) + list(_EN_TRAIN_SIGS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -7,11 +7,10 @@
 // a wave's reads cover 64 k consecutive columns per row and channel, every fetched line is used (by this wave or the next row's).  No LDS,
 // no atomics; memory- and latency-bound (12 gathered loads, ~9 IEEE divisions, 4 B + the window's share stored per thread).
 #include "common.h"
+#include "homonet_prep_dev.h"
 #include "../../include/hesic_homography_prep.h"
 
 namespace {
-
-constexpr int PREP_THREADS = 256;
 
 struct PrepView {
     const void* x;
@@ -19,47 +18,6 @@ struct PrepView {
     float* grey;
     float* patch;
 };
-
-struct PrepAxis {
-    int i0, i1;
-    float l0, l1;
-};
-
-// every product, sum and difference below is an fp32 operation of its own: a fused multiply-add would move values that sit at k + 0.5
-// before the rounding to a level, and the host path (and the numpy restatement the tests hold this to) does not fuse
-__device__ __forceinline__ PrepAxis prep_axis(int d, int n, float scale) {
-#pragma clang fp contract(off)
-    float s = scale * ((float)d + 0.5f) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    PrepAxis a;
-    a.i0 = min((int)s, n - 1);
-    a.i1 = min(a.i0 + 1, n - 1);
-    a.l1 = s - (float)a.i0;
-    a.l0 = 1.f - a.l1;
-    return a;
-}
-
-template <bool F32> __device__ __forceinline__ float prep_level(const void* x, int64_t off) {
-    if (F32) {
-#pragma clang fp contract(off)
-        const float q = rintf(255.f * ((const float*)x)[off]);
-        return fminf(fmaxf(q, 0.f), 255.f);
-    }
-    return (float)((const uint8_t*)x)[off];
-}
-
-__device__ __forceinline__ float prep_resample(float a, float b, float c, float d, const PrepAxis& ax, const PrepAxis& ay) {
-#pragma clang fp contract(off)
-    const float top = ax.l0 * a + ax.l1 * b;
-    const float bot = ax.l0 * c + ax.l1 * d;
-    const float v = ay.l0 * top + ay.l1 * bot;
-    return fminf(fmaxf(rintf(v), 0.f), 255.f);          // rintf: ties to even
-}
-
-__device__ __forceinline__ float prep_normalise(float r, float mean, float std) {
-#pragma clang fp contract(off)
-    return __fdiv_rn(__fdiv_rn(r, 255.f) - mean, std);
-}
 
 template <bool F32>
 __global__ __launch_bounds__(PREP_THREADS) void homonet_prepare_kernel(const PrepView v1, const PrepView v2, const int32_t* __restrict__ xy,
@@ -101,38 +59,8 @@ __global__ __launch_bounds__(PREP_THREADS) void homonet_prepare_kernel(const Pre
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the item form
-// hesic_homonet_prepare_items (include/hesic_homonet_items.h): the same thread map and the same device functions, the sources being stored
-// HWC bytes of per-item geometry.  blockIdx.y = item: the descriptor is block-uniform and read once (scalar loads).  A row's two taps are
-// two neighbouring pixels = six adjacent bytes: they are fetched as one dword and one ushort at byte alignment (gfx950 global loads take
-// any alignment) instead of six strided bytes, so a thread issues 4 loads where the strided kernel issues 12, and one 64-bit address per row.
-// `xs` is the first of the two columns fetched: i0, or i0 - 1 at the crop's last column, where i1 == i0 and both taps are the second
-// pixel -- the six bytes never leave the crop's row.  A crop one pixel wide (block-uniform) is read as its three bytes.
-typedef uint32_t __attribute__((aligned(1))) prep_u32_any;      // a dword / ushort at any byte address
-typedef uint16_t __attribute__((aligned(1))) prep_u16_any;
-
-struct PrepTaps {
-    uint32_t px[2];         // the two adjacent pixels, R G B in bits 0-23 of each (bits 24-31 are not used)
-};
-
-__device__ __forceinline__ PrepTaps prep_load_taps(const uint8_t* p, bool two) {
-    const __attribute__((address_space(1))) uint8_t* g = (const __attribute__((address_space(1))) uint8_t*)p;       // global, not flat, loads
-    PrepTaps t;
-    if (two) {
-        const uint32_t lo = *(const __attribute__((address_space(1))) prep_u32_any*)g;
-        const uint32_t hi = *(const __attribute__((address_space(1))) prep_u16_any*)(g + 4);
-        t.px[0] = lo;
-        t.px[1] = __funnelshift_r(lo, hi, 24);
-    } else {
-        t.px[0] = t.px[1] = (uint32_t)g[0] | ((uint32_t)g[1] << 8) | ((uint32_t)g[2] << 16);       // the one pixel: either tap index reads it
-    }
-    return t;
-}
-
-// channel c of pixel k (0 or 1) of a fetched pair
-__device__ __forceinline__ float prep_tap_level(const PrepTaps& t, int k, int c) {
-    return (float)(((k ? t.px[1] : t.px[0]) >> (8 * c)) & 0xffu);
-}
-
+// hesic_homonet_prepare_items (include/hesic_homonet_items.h): the same thread map and the same device functions (homonet_prep_dev.h), the
+// sources being stored HWC bytes of per-item geometry.  blockIdx.y = item: the descriptor is block-uniform and read once (scalar loads).
 __global__ __launch_bounds__(PREP_THREADS) void homonet_prepare_items_kernel(const hesic_homonet_item* __restrict__ items, float* __restrict__ grey1,
                                                                              float* __restrict__ grey2, float* __restrict__ patch1,
                                                                              float* __restrict__ patch2, float* __restrict__ corners, int S, int P,
@@ -140,33 +68,12 @@ __global__ __launch_bounds__(PREP_THREADS) void homonet_prepare_items_kernel(con
     const int b = blockIdx.y;
     const hesic_homonet_item it = items[b];
     const int wx = it.wx, wy = it.wy;
-    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x < 8) {
-        const int k = threadIdx.x >> 1;                 // as in homonet_prepare_kernel
-        const int val = (threadIdx.x & 1) ? wy + (k >= 2 ? P : 0) : wx + ((k == 1 || k == 2) ? P : 0);
-        corners[(int64_t)b * 8 + threadIdx.x] = (float)val;
-    }
+    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x < 8) corners[(int64_t)b * 8 + threadIdx.x] = prep_corner_word(threadIdx.x, wx, wy, P);
     const int idx = blockIdx.x * PREP_THREADS + threadIdx.x;
     if (idx >= S * S) return;
     const int y = idx / S, x = idx - y * S;
-    const float scale_y = __fdiv_rn((float)it.ch, (float)S), scale_x = __fdiv_rn((float)it.cw, (float)S);
-    const PrepAxis ay = prep_axis(y, it.ch, scale_y), ax = prep_axis(x, it.cw, scale_x);
-    const bool two = it.cw >= 2;
-    const int xs = two ? min(ax.i0, it.cw - 2) : 0;
-    const int k0 = ax.i0 - xs, k1 = ax.i1 - xs;         // 0 or 1 each
-    const uint8_t* view = blockIdx.z == 0 ? it.left : it.right;
-    const int64_t col = (int64_t)(it.x0 + xs) * 3;
-    const PrepTaps r0 = prep_load_taps(view + (int64_t)(it.y0 + ay.i0) * it.pitch_px * 3 + col, two);
-    const PrepTaps r1 = prep_load_taps(view + (int64_t)(it.y0 + ay.i1) * it.pitch_px * 3 + col, two);
-    float n[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-        n[c] = prep_normalise(prep_resample(prep_tap_level(r0, k0, c), prep_tap_level(r0, k1, c), prep_tap_level(r1, k0, c),
-                                            prep_tap_level(r1, k1, c), ax, ay), mean, std);
-    float g;
-    {
-#pragma clang fp contract(off)
-        g = __fdiv_rn((n[0] + n[1]) + n[2], 3.f);
-    }
+    const PrepCrop crop{blockIdx.z == 0 ? it.left : it.right, it.pitch_px, it.x0, it.y0, it.cw, it.ch};
+    const float g = prep_item_grey(crop, S, x, y, mean, std);
     float* grey = blockIdx.z == 0 ? grey1 : grey2;
     float* patch = blockIdx.z == 0 ? patch1 : patch2;
     grey[((int64_t)b * S + y) * S + x] = g;

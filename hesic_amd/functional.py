@@ -2020,6 +2020,20 @@ def homonet_items(batch):
     return np.zeros(int(batch), dtype=np.dtype(HOMONET_ITEM_DTYPE))
 
 
+def _check_homonet_geometry(name, b, it, S, P):
+    """The stored-image, crop and window conditions of item ``b`` that the item entries share (``it``: its integer fields)."""
+    if it["pitch_px"] < 1 or it["rows"] < 1:
+        raise ValueError(f"{name}: item {b} stored image {it['rows']} x {it['pitch_px']}")
+    if it["cw"] < 1 or it["ch"] < 1:
+        raise ValueError(f"{name}: item {b} crop {it['ch']} x {it['cw']} (at least one pixel each way)")
+    if not (0 <= it["x0"] and it["x0"] + it["cw"] <= it["pitch_px"]):
+        raise ValueError(f"{name}: item {b} columns [{it['x0']}, {it['x0'] + it['cw']}) outside the stored image's {it['pitch_px']}")
+    if not (0 <= it["y0"] and it["y0"] + it["ch"] <= it["rows"]):
+        raise ValueError(f"{name}: item {b} rows [{it['y0']}, {it['y0'] + it['ch']}) outside the stored image's {it['rows']}")
+    if not (0 <= it["wx"] <= S - P and 0 <= it["wy"] <= S - P):
+        raise ValueError(f"{name}: item {b} window origin ({it['wx']}, {it['wy']}) outside [0, {S - P}]")
+
+
 def check_homonet_items(items, S, P):
     """The per-item conditions ``hesic_homonet_prepare_items`` leaves to its caller, on the host: ValueError names the first item that breaks one."""
     S, P = int(S), int(P)
@@ -2027,17 +2041,7 @@ def check_homonet_items(items, S, P):
         it = {k: int(items[b][k]) for k in items.dtype.names}
         if it["left"] == 0 or it["right"] == 0:
             raise ValueError(f"homonet_prepare_items: item {b} has a null view pointer")
-        if it["pitch_px"] < 1 or it["rows"] < 1:
-            raise ValueError(f"homonet_prepare_items: item {b} stored image {it['rows']} x {it['pitch_px']}")
-        if it["cw"] < 1 or it["ch"] < 1:
-            raise ValueError(f"homonet_prepare_items: item {b} crop {it['ch']} x {it['cw']} (at least one pixel each way)")
-        if not (0 <= it["x0"] and it["x0"] + it["cw"] <= it["pitch_px"]):
-            raise ValueError(f"homonet_prepare_items: item {b} columns [{it['x0']}, {it['x0'] + it['cw']}) outside the stored image's "
-                             f"{it['pitch_px']}")
-        if not (0 <= it["y0"] and it["y0"] + it["ch"] <= it["rows"]):
-            raise ValueError(f"homonet_prepare_items: item {b} rows [{it['y0']}, {it['y0'] + it['ch']}) outside the stored image's {it['rows']}")
-        if not (0 <= it["wx"] <= S - P and 0 <= it["wy"] <= S - P):
-            raise ValueError(f"homonet_prepare_items: item {b} window origin ({it['wx']}, {it['wy']}) outside [0, {S - P}]")
+        _check_homonet_geometry("homonet_prepare_items", b, it, S, P)
 
 
 def homonet_prepare_items(items, pic_size, patch_size, mean, std, out=None):
@@ -2072,6 +2076,80 @@ def homonet_prepare_items(items, pic_size, patch_size, mean, std, out=None):
     host = torch.from_numpy(items.view(np.uint8).reshape(B, 48)).pin_memory()        # a pinned copy: the caller may reuse ``items`` at once
     items_dev = host.to(dev, non_blocking=True)
     L.call("hesic_homonet_prepare_items", L.ptr(items_dev), B, S, P, float(mean), float(std), *[L.ptr(t) for t in out], L.stream())
+    return tuple(out)
+
+
+HOMONET_SYNTH_ITEM_DTYPE = [("view", "<u8"), ("pitch_px", "<i4"), ("rows", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("cw", "<i4"), ("ch", "<i4"),
+                            ("wx", "<i4"), ("wy", "<i4"), ("delta", "<i4", (8,))]    # hesic_homonet_synth_item as a numpy structured dtype (72 bytes)
+
+
+def homonet_synth_items(batch):
+    """A zeroed host array of ``batch`` ``hesic_homonet_synth_item`` descriptors (numpy structured, fields as in
+    include/hesic_homonet_synth.h; ``view`` is a device address as an integer)."""
+    import numpy as np
+    return np.zeros(int(batch), dtype=np.dtype(HOMONET_SYNTH_ITEM_DTYPE))
+
+
+def perturbed_quad_is_convex(wx, wy, P, delta):
+    """Whether the window's corners [[wx, wy], [wx+P, wy], [wx+P, wy+P], [wx, wy+P]] moved by the eight integers ``delta`` (x, y per corner)
+    form a STRICTLY convex quadrilateral: the four cross products of consecutive edges are non-zero and of one sign.  Exact (Python ints)."""
+    wx, wy, P = int(wx), int(wy), int(P)
+    d = [int(v) for v in delta]
+    q = [(wx + d[0], wy + d[1]), (wx + P + d[2], wy + d[3]), (wx + P + d[4], wy + P + d[5]), (wx + d[6], wy + P + d[7])]
+    cross = []
+    for k in range(4):
+        (ax, ay), (bx, by), (cx, cy) = q[k], q[(k + 1) % 4], q[(k + 2) % 4]
+        cross.append((bx - ax) * (cy - by) - (by - ay) * (cx - bx))
+    return all(c > 0 for c in cross) or all(c < 0 for c in cross)
+
+
+def check_homonet_synth_items(items, S, P):
+    """The per-item conditions ``hesic_homonet_synth_items`` leaves to its caller, on the host: those of ``check_homonet_items`` for the one
+    view, and the strict convexity of the perturbed quadrilateral.  ValueError names the first item that breaks one."""
+    S, P = int(S), int(P)
+    for b in range(len(items)):
+        it = {k: int(items[b][k]) for k in items.dtype.names if k != "delta"}
+        if it["view"] == 0:
+            raise ValueError(f"homonet_synth: item {b} has a null view pointer")
+        _check_homonet_geometry("homonet_synth", b, it, S, P)
+        delta = [int(v) for v in items[b]["delta"]]
+        if not perturbed_quad_is_convex(it["wx"], it["wy"], P, delta):
+            raise ValueError(f"homonet_synth: item {b} corners + delta {delta} is not a strictly convex quadrilateral")
+
+
+def homonet_synth(items, pic_size, patch_size, mean, std, align_corners, out=None):
+    """``hesic_homonet_synth_items`` (include/hesic_homonet_synth.h): ``items`` the HOST description of the batch -- a numpy array of
+    ``HOMONET_SYNTH_ITEM_DTYPE`` (``homonet_synth_items(B)``) or its bytes as a (B, 72) uint8 CPU tensor --, whose ``view`` is the address
+    of a uint8 HWC image on the current device.  Every item is checked here, on the host; the descriptors are then uploaded and the entry
+    writes ``(grey_a, patch_a, corners, delta, h, grey_b, patch_b)``: fp32 but for ``h`` (B, 9) fp64.  ``out``: seven preallocated dense
+    tensors of those shapes and types."""
+    import numpy as np
+    if torch.is_tensor(items):
+        if items.is_cuda or items.dtype != torch.uint8 or items.dim() != 2 or items.shape[1] != 72 or not items.is_contiguous():
+            raise ValueError("homonet_synth: items as a tensor must be a contiguous (B, 72) uint8 CPU tensor")
+        items = items.numpy().view(np.dtype(HOMONET_SYNTH_ITEM_DTYPE)).reshape(-1)
+    items = np.ascontiguousarray(items)
+    if items.dtype != np.dtype(HOMONET_SYNTH_ITEM_DTYPE) or items.ndim != 1:
+        raise ValueError("homonet_synth: items must be a 1-d array of HOMONET_SYNTH_ITEM_DTYPE")
+    B, S, P = len(items), int(pic_size), int(patch_size)
+    if not (1 <= B <= 65535 and 1 <= P <= S <= 16384):
+        raise ValueError(f"homonet_synth: need 1 <= B <= 65535 and 1 <= P <= S <= 16384, got B={B} S={S} P={P}")
+    check_homonet_synth_items(items, S, P)
+    if not torch.cuda.is_available():
+        raise RuntimeError("hesic_amd: the HIP path needs a ROCm device (no CPU fallback)")
+    dev = out[0].device if out is not None else torch.device("cuda", torch.cuda.current_device())
+    shapes = [(B, 1, S, S), (B, 1, P, P), (B, 4, 2), (B, 4, 2), (B, 9), (B, 1, S, S), (B, 1, P, P)]
+    dtypes = [torch.float32] * 4 + [torch.float64] + [torch.float32] * 2
+    if out is None:
+        out = [torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes)]
+    else:
+        L.require_cuda(*out)
+        if len(out) != 7 or any(tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, s, d in zip(out, shapes, dtypes)):
+            raise ValueError(f"homonet_synth: out must be dense fp32 tensors (h: fp64) of shapes {shapes}")
+    host = torch.from_numpy(items.view(np.uint8).reshape(B, 72)).pin_memory()        # a pinned copy: the caller may reuse ``items`` at once
+    items_dev = host.to(dev, non_blocking=True)
+    L.call("hesic_homonet_synth_items", L.ptr(items_dev), B, S, P, float(mean), float(std), int(bool(align_corners)),
+           *[L.ptr(t) for t in out], L.stream())
     return tuple(out)
 
 

@@ -40,8 +40,8 @@ from . import functional as Fn
 from . import geometry
 from .compressai.models.utils import HipConv2d
 
-__all__ = ["Net", "Block", "Flatten", "max_pool2", "get_perspective_transform", "h_matrix_from_delta", "h_matrix", "photometric_loss",
-           "window_origins", "prepare_inputs", "h_matrix_from_pair", "load_checkpoint", "checkpoint_state_dict", "net_state_dict"]
+__all__ = ["Net", "Block", "Flatten", "max_pool2", "get_perspective_transform", "h_matrix_from_delta", "h_matrix", "photometric_loss", "corner_error",
+           "window_origins", "draw_deltas", "prepare_inputs", "h_matrix_from_pair", "load_checkpoint", "checkpoint_state_dict", "net_state_dict"]
 
 
 def max_pool2(x):
@@ -202,6 +202,12 @@ def photometric_loss(delta, img_a, patch_b, corners):
     return Fn.photometric_loss(delta.float(), img_a, patch_b, corners.float(), geometry.DEFAULT_ALIGN_CORNERS)
 
 
+def corner_error(delta_hat, delta):
+    """Mean corner error per pair: the mean over the four corners of ``||delta_hat_k - delta_k||_2``, in pixels of the frame the deltas are
+    measured in.  (B,4,2) twice -> (B,) fp32.  ``delta_hat = 0`` gives the error of predicting the identity, the figure to beat."""
+    return (delta_hat.float() - delta.float()).square().sum(-1).sqrt().mean(-1)
+
+
 def h_matrix(net, homo_img1, homo_img2, homo_corners, img_h, img_w, pic_size=256):
     """The h_matrix of a stereo pair as the `_real` scripts derive it (newtrain1_real.py:108-123)."""
     with torch.no_grad():
@@ -250,6 +256,39 @@ def window_origins(batch, xy=None, pic_size=256, patch_size=128, rho=45, rng=Non
         if not (0 <= x <= S - P and 0 <= y <= S - P):
             raise ValueError(f"prepare_inputs: window origin ({x}, {y}) outside [0, {S - P}] (pic_size {S}, patch_size {P})")
         out.append((int(x), int(y)))
+    return out
+
+
+def draw_deltas(batch, windows, patch_size, rho, rng):
+    """The corner offsets of ``batch`` synthetic warps (include/hesic_homonet_synth.h) as a list of eight integers per item, the label of
+    supervised training: per item eight ``rng.randrange(-rho, rho)`` in the order corner 0 x, corner 0 y, ... corner 3 y -- the range of the
+    reference's ``randint_like(corners, -rho, rho)`` (udh/udh/dataset.py) --, drawn again, all eight, while the window's corners moved by
+    them are not a strictly convex quadrilateral (``functional.perturbed_quad_is_convex``).  ``windows``: the items' window origins
+    ``(wx, wy)``, or their (B,4,2) corners, whose first corner is the origin.  ``rho = 0`` gives zeros without a draw.  A pure host function
+    that consumes only ``rng`` (a ``random.Random``)."""
+    B, P, rho = int(batch), int(patch_size), int(rho)
+    if rho < 0:
+        raise ValueError(f"draw_deltas: rho must not be negative, got {rho}")
+    if torch.is_tensor(windows):
+        windows = windows.detach().cpu().tolist()
+    origins = []
+    for w in windows:
+        x, y = w[0] if hasattr(w[0], "__len__") else w
+        if int(x) != x or int(y) != y:
+            raise TypeError(f"draw_deltas: window origins must hold integers, got ({x!r}, {y!r})")
+        origins.append((int(x), int(y)))
+    if len(origins) != B:
+        raise ValueError(f"draw_deltas: {B} items need as many windows, got {len(origins)}")
+    out = []
+    for wx, wy in origins:
+        if rho == 0:
+            out.append([0] * 8)
+            continue
+        while True:
+            d = [rng.randrange(-rho, rho) for _ in range(8)]
+            if Fn.perturbed_quad_is_convex(wx, wy, P, d):
+                break
+        out.append(d)
     return out
 
 

@@ -7,6 +7,7 @@
     --crop H W            one random crop offset shared by both views (default: the whole image)
     --seed 0  --resume PATH|none  --out DIR  --clip-max-norm X  --skip-nonfinite
     --cache host|device|stream  --cache-gb G  -n/--num-workers 3  --mix-sizes
+    --supervision photometric|synthetic
 
 ``--cache host`` (the default): the host reads, decodes and crops every batch of every epoch on one thread; a batch is stacked as uint8
 and uploaded as bytes, and ``HomographyTrainer.step_pairs`` turns it into the net's inputs in one launch (resize, normalise, grey, random
@@ -25,6 +26,20 @@ Per epoch: shuffle and train, then the validation loss -- eval mode under
 
 A checkpoint holds ``{"state_dict", "loss", "optimizer", "dropout", "epoch", "seed"}``; the ``state_dict`` keys carry the reference's
 ``model.`` prefix, so the `_real` scripts load the file as they load ``homo_best.pth.tar`` (``homography.load_checkpoint`` reads both forms).
+
+``--supervision synthetic`` (``--cache device|stream`` only) trains on pairs with a KNOWN answer instead: every batch is a fresh random
+perspective warp of the LEFT views -- ``homography.draw_deltas`` moves each window corner by up to ``rho`` pixels,
+``DevicePairCache.homonet_synth_batch`` (include/hesic_homonet_synth.h) makes the frame, its warp and both windows from the stored bytes --
+and ``HomographyTrainer.step_supervised`` minimises the MSE between the net's deltas and the drawn ones: the finish of the reference's
+``SyntheticDataset`` (udh/udh/dataset.py), and the augmentation a homography net wants.  The deltas come from a stream of their own,
+``random.Random(f"{seed}/{epoch}/synth")`` (validation: ``f"{seed}/valid/synth"``), so the order, crops and windows of an epoch are those of
+a photometric run with the same seed.  The records then carry ``"supervision"``, ``"valid_loss"`` -- the supervised MSE on synthetic
+validation pairs, which the best checkpoint follows --, ``"valid_corner_error"`` (the mean over the pairs of the mean corner error, in
+pixels of the ``picsize`` frame), ``"identity_corner_error"`` (the same for a net that answers zero: the figure to beat) and
+``"valid_photometric"``, the photometric validation loss on the REAL right views, which shows whether the pre-training transfers; the
+checkpoints gain ``"supervision"``.  ``--resume`` across supervisions is allowed -- synthetic pre-training, then photometric fine-tuning, is
+the intended use --; the two losses are not comparable, so the lowest validation loss so far then starts again at +inf and the first
+epoch's checkpoint becomes the best one.
 
 Determinism: the shuffle, the crop offsets and the windows of epoch ``e`` come from a ``random.Random`` keyed by ``(seed, e)``, the validation
 draws from one keyed by the seed alone (every epoch is judged on the same windows).  ``--epochs`` is the TOTAL number of epochs, as in QHtrain:
@@ -125,12 +140,25 @@ def cached_inputs(cache, items, a, rng):
     return grey1, patch1, patch2, corners
 
 
-def train_epoch(trainer, pairs, a, rng, device, cache=None):
+def synthetic_inputs(cache, items, a, rng, srng):
+    """``(patch_a, patch_b, delta)`` of a synthetic-warp batch on the left views of ``items``: ``draw_batch`` on ``rng`` as ``cached_inputs``
+    does, the corner offsets from ``srng``, one call of ``DevicePairCache.homonet_synth_batch``."""
+    from . import homography
+    origins, sizes, windows = draw_batch(items, a.crop, rng, a.picsize, a.patchsize, a.rho)
+    deltas = homography.draw_deltas(len(items), windows, a.patchsize, a.rho, srng)
+    _, patch_a, _, delta, _, _, patch_b = cache.homonet_synth_batch([cache.index_of[lf] for lf, _, _ in items], origins, sizes, windows, deltas,
+                                                                    a.picsize, a.patchsize)
+    return patch_a, patch_b, delta
+
+
+def train_epoch(trainer, pairs, a, rng, device, cache=None, srng=None):
     """One pass over ``pairs`` (from ``cache`` when given, else read on the host); returns (mean training loss, steps, seconds).  The losses
-    stay on the device until the end."""
+    stay on the device until the end.  ``srng``: the deltas' stream under ``--supervision synthetic``, which makes every step a supervised one."""
     total, n, t0 = torch.zeros((), device=device), 0, time.time()
     for items in batches(pairs, a.batch_size, a.crop, rng, True, cache is not None and a.mix_sizes):
-        if cache is None:
+        if srng is not None:
+            total += trainer.step_supervised(*synthetic_inputs(cache, items, a, rng, srng))["loss"]
+        elif cache is None:
             x1, x2 = load_batch(items, a.crop, rng, device)
             total += trainer.step_pairs(x1, x2, None, a.picsize, a.rho, rng)["loss"]
         else:
@@ -151,6 +179,22 @@ def validate(trainer, pairs, a, rng, device, cache=None):
     return float(total) / max(n, 1)
 
 
+def validate_synthetic(trainer, pairs, a, rng, srng, device, cache):
+    """``(supervised MSE, mean corner error, identity corner error)`` on synthetic warps of the validation pairs' left views: the mean of the
+    per-batch losses and the means over the PAIRS of the two corner errors, added up on the device and read back once."""
+    from . import homography
+    total, nb, n = torch.zeros(3, dtype=torch.float64, device=device), 0, 0
+    for items in batches(pairs, a.batch_size, a.crop, rng, False, a.mix_sizes):
+        patch_a, patch_b, delta = synthetic_inputs(cache, items, a, rng, srng)
+        loss, err = trainer.evaluate_supervised(patch_a, patch_b, delta)
+        ident = homography.corner_error(torch.zeros_like(delta), delta)
+        total += torch.stack([loss.double(), err.double().sum(), ident.double().sum()])
+        nb += 1
+        n += len(items)
+    loss, err, ident = total.tolist()
+    return loss / max(nb, 1), err / max(n, 1), ident / max(n, 1)
+
+
 def build_cache(root, split, pairs, a):
     """The split's ``DevicePairCache`` in ``--cache``'s mode, with ``index_of``: left file -> pair index (the listing is ``list_pairs``')."""
     from . import pair_cache
@@ -162,11 +206,14 @@ def build_cache(root, split, pairs, a):
     return cache
 
 
-def save_checkpoint(trainer, path, loss, epoch, seed):
+def save_checkpoint(trainer, path, loss, epoch, seed, supervision="photometric"):
     from . import homography
     sd = trainer.state_dict()
-    torch.save({"state_dict": homography.checkpoint_state_dict(trainer.net), "loss": float(loss), "optimizer": sd["optimizer"],
-                "dropout": tuple(sd["dropout"]), "epoch": int(epoch), "seed": int(seed)}, path)
+    ckpt = {"state_dict": homography.checkpoint_state_dict(trainer.net), "loss": float(loss), "optimizer": sd["optimizer"],
+            "dropout": tuple(sd["dropout"]), "epoch": int(epoch), "seed": int(seed)}
+    if supervision != "photometric":              # a photometric checkpoint is the file it always was
+        ckpt["supervision"] = supervision
+    torch.save(ckpt, path)
 
 
 def parser():
@@ -190,12 +237,16 @@ def parser():
     p.add_argument("--cache-gb", type=float, default=None, help="device-memory budget of the decoded pairs (default: half of the free memory)")
     p.add_argument("-n", "--num-workers", type=int, default=3, help="host threads that decode image files (--cache device|stream)")
     p.add_argument("--mix-sizes", action="store_true", help="pairs of all sizes share batches (--cache device|stream)")
+    p.add_argument("--supervision", choices=("photometric", "synthetic"), default="photometric",
+                   help="photometric: the loss on the real pairs; synthetic: known random warps of the left views, MSE on the corner deltas "
+                        "(--cache device|stream)")
     return p
 
 
 def main(argv=None, log=print):
     """Returns the epochs' records ({"epoch", "train_loss", "valid_loss", "best", "steps", "seconds_per_step"}, each also logged as one JSON
-    line; ``--cache device|stream`` add "cache" and, in the run's first record, "decode_seconds"); 2 without a ROCm device."""
+    line; ``--cache device|stream`` add "cache" and, in the run's first record, "decode_seconds"; ``--supervision synthetic`` adds
+    "supervision", "valid_corner_error", "identity_corner_error" and "valid_photometric"); 2 without a ROCm device."""
     from . import homography, train
     p = parser()
     a = p.parse_args(argv)
@@ -207,6 +258,8 @@ def main(argv=None, log=print):
         p.error("--rho must not be negative")
     if a.mix_sizes and a.cache == "host":
         p.error("--mix-sizes needs --cache device or --cache stream (the host route uploads a batch as one tensor of one size)")
+    if a.supervision == "synthetic" and a.cache == "host":
+        p.error("--supervision synthetic needs --cache device or --cache stream (the warps are made from the stored bytes on the device)")
     if a.num_workers < 1 or (a.cache_gb is not None and a.cache_gb <= 0):
         p.error("--num-workers and --cache-gb must be positive")
     if not torch.cuda.is_available():
@@ -229,21 +282,32 @@ def main(argv=None, log=print):
                                  "dropout": resume["dropout"]})
         trainer.set_lr(a.learning_rate)
     first_epoch, best_loss = resume_position(resume, a.resume, best, True)      # this command always saves
+    if resume is not None and resume.get("supervision", "photometric") != a.supervision:
+        best_loss = float("inf")                    # the other supervision's loss is not comparable: the first epoch's checkpoint is the best
     tcache = vcache = None
     if a.cache != "host" and first_epoch < a.epochs:
         tcache = build_cache(a.root, "train", train_pairs, a)
         vcache = tcache if a.valid_split == "train" else build_cache(a.root, a.valid_split, valid_pairs, a)
-    history = []
+    history, synthetic = [], a.supervision == "synthetic"
     for epoch in range(first_epoch, a.epochs):
-        train_loss, steps, secs = train_epoch(trainer, train_pairs, a, random.Random(f"{seed}/{epoch}"), device, tcache)
-        valid_loss = validate(trainer, valid_pairs, a, random.Random(f"{seed}/valid"), device, vcache)
-        save_checkpoint(trainer, last, valid_loss, epoch, seed)
+        train_loss, steps, secs = train_epoch(trainer, train_pairs, a, random.Random(f"{seed}/{epoch}"), device, tcache,
+                                              random.Random(f"{seed}/{epoch}/synth") if synthetic else None)
+        if synthetic:
+            valid_loss, corner_err, identity_err = validate_synthetic(trainer, valid_pairs, a, random.Random(f"{seed}/valid"),
+                                                                      random.Random(f"{seed}/valid/synth"), device, vcache)
+            valid_photometric = validate(trainer, valid_pairs, a, random.Random(f"{seed}/valid"), device, vcache)
+        else:
+            valid_loss = validate(trainer, valid_pairs, a, random.Random(f"{seed}/valid"), device, vcache)
+        save_checkpoint(trainer, last, valid_loss, epoch, seed, a.supervision)
         is_best = valid_loss < best_loss
         if is_best or not best.is_file():
             best_loss = min(best_loss, valid_loss)
             shutil.copyfile(last, best)
         rec = {"epoch": epoch, "train_loss": train_loss, "valid_loss": valid_loss, "best": bool(is_best), "steps": steps,
                "seconds_per_step": secs / max(steps, 1)}
+        if synthetic:
+            rec.update({"supervision": a.supervision, "valid_corner_error": corner_err, "identity_corner_error": identity_err,
+                        "valid_photometric": valid_photometric})
         if tcache is not None:
             rec["cache"] = a.cache
             if not history:

@@ -275,6 +275,25 @@ class DevicePairCache:
         x1, x2, hm = gather(items, self.h_table, ph, pw, out=out)
         return x1, x2, hm, torch.tensor([self.has_h[i] for i in indices], dtype=torch.bool)
 
+    def _homonet_geometry(self, name, indices, origins, sizes, windows):
+        """``[(pair, y0, x0, ch, cw, wx, wy)]`` of a HomographyNet batch, checked against the listing (``name``: the calling method)."""
+        indices = [int(i) for i in indices]
+        B = len(indices)
+        if B < 1 or len(windows) != B or (sizes is None and origins is not None and len(origins) != B) or \
+                (sizes is not None and (len(sizes) != B or len(origins) != B)):
+            raise ValueError(f"DevicePairCache.{name}: {B} indices need as many origins, sizes and windows")
+        geo = []
+        for b, i in enumerate(indices):
+            if not 0 <= i < len(self):
+                raise IndexError(f"DevicePairCache.{name}: pair {i} outside [0, {len(self)})")
+            h, w = self.sizes[i]
+            (y0, x0), (ch, cw) = ((0, 0), (h, w)) if sizes is None else (origins[b], sizes[b])
+            y0, x0, ch, cw = int(y0), int(x0), int(ch), int(cw)
+            if not (ch >= 1 and cw >= 1 and 0 <= x0 and x0 + cw <= w and 0 <= y0 and y0 + ch <= h):
+                raise ValueError(f"DevicePairCache.{name}: crop ({ch}, {cw}) at ({y0}, {x0}) outside pair {i}'s image ({h}, {w})")
+            geo.append((i, y0, x0, ch, cw, int(windows[b][0]), int(windows[b][1])))
+        return geo
+
     def homonet_batch(self, indices, origins, sizes, windows, pic_size, patch_size, out=None):
         """HomographyNet's inputs ``(grey1, grey2, patch1, patch2, corners)`` of the pairs ``indices``, straight from the stored bytes in
         one launch (``hesic_homonet_prepare_items``, include/hesic_homonet_items.h): pair ``indices[i]`` cropped at ``origins[i]`` =
@@ -284,41 +303,60 @@ class DevicePairCache:
         ``out``: five dense fp32 tensors to write into."""
         from . import functional as Fn
         from .compressai.datasets import MEAN, STD
-        indices = [int(i) for i in indices]
-        B = len(indices)
-        if B < 1 or len(windows) != B or (sizes is None and origins is not None and len(origins) != B) or \
-                (sizes is not None and (len(sizes) != B or len(origins) != B)):
-            raise ValueError(f"DevicePairCache.homonet_batch: {B} indices need as many origins, sizes and windows")
-        items = Fn.homonet_items(B)
-        for b, i in enumerate(indices):
-            if not 0 <= i < len(self):
-                raise IndexError(f"DevicePairCache.homonet_batch: pair {i} outside [0, {len(self)})")
+        geo = self._homonet_geometry("homonet_batch", indices, origins, sizes, windows)
+        items = Fn.homonet_items(len(geo))
+        for it, (i, y0, x0, ch, cw, wx, wy) in zip(items, geo):
             h, w = self.sizes[i]
-            (y0, x0), (ch, cw) = ((0, 0), (h, w)) if sizes is None else (origins[b], sizes[b])
-            y0, x0, ch, cw = int(y0), int(x0), int(ch), int(cw)
-            if not (ch >= 1 and cw >= 1 and 0 <= x0 and x0 + cw <= w and 0 <= y0 and y0 + ch <= h):
-                raise ValueError(f"DevicePairCache.homonet_batch: crop ({ch}, {cw}) at ({y0}, {x0}) outside pair {i}'s image ({h}, {w})")
-            it = items[b]
-            it["pitch_px"], it["rows"], it["x0"], it["y0"], it["cw"], it["ch"] = w, h, x0, y0, cw, ch
-            it["wx"], it["wy"] = int(windows[b][0]), int(windows[b][1])
+            it["pitch_px"], it["rows"], it["x0"], it["y0"], it["cw"], it["ch"], it["wx"], it["wy"] = w, h, x0, y0, cw, ch, wx, wy
         if self.mode == "device":
             base = self.arena.data_ptr()
-            for b, i in enumerate(indices):
-                items[b]["left"], items[b]["right"] = base + self.offsets[i][0], base + self.offsets[i][1]
+            for it, g in zip(items, geo):
+                it["left"], it["right"] = base + self.offsets[g[0]][0], base + self.offsets[g[0]][1]
         else:
-            nbytes = [int(it["ch"]) * int(it["cw"]) * 3 for it in items]
-            slab, host = self._stream_bytes(2 * sum(nbytes))
-            flat = host.numpy()
-            with ThreadPoolExecutor(max_workers=self.workers) as pool:
-                off = 0
-                for b, (a, c) in enumerate(pool.map(self._read, indices)):
-                    it = items[b]
-                    y0, x0, ch, cw, n = int(it["y0"]), int(it["x0"]), int(it["ch"]), int(it["cw"]), nbytes[b]
-                    flat[off:off + n].reshape(ch, cw, 3)[...] = a[y0:y0 + ch, x0:x0 + cw]
-                    flat[off + n:off + 2 * n].reshape(ch, cw, 3)[...] = c[y0:y0 + ch, x0:x0 + cw]
-                    it["left"], it["right"] = slab.data_ptr() + off, slab.data_ptr() + off + n
-                    it["pitch_px"], it["rows"], it["x0"], it["y0"] = cw, ch, 0, 0
-                    off += 2 * n
-            slab.copy_(host, non_blocking=True)
-            self._slab_event.record()
+            self._stream_crops(items, geo, (0, 1), ("left", "right"))
         return Fn.homonet_prepare_items(items, pic_size, patch_size, float(MEAN), float(STD), out=out)
+
+    def _stream_crops(self, items, geo, views, fields):
+        """``"stream"`` mode: read the batch's pairs on the host, pack the crops of ``views`` (0: left, 1: right) back to back into the reused
+        slab, start the upload, put each crop's address into the descriptor field of ``fields`` that goes with its view, and re-base the
+        descriptors' geometry onto the packed crops."""
+        nbytes = [ch * cw * 3 for _, _, _, ch, cw, _, _ in geo]
+        slab, host = self._stream_bytes(len(fields) * sum(nbytes))
+        flat = host.numpy()
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            off = 0
+            for it, (_, y0, x0, ch, cw, _, _), n, pair in zip(items, geo, nbytes, pool.map(self._read, [g[0] for g in geo])):
+                for f, v in zip(fields, views):
+                    flat[off:off + n].reshape(ch, cw, 3)[...] = pair[v][y0:y0 + ch, x0:x0 + cw]
+                    it[f] = slab.data_ptr() + off
+                    off += n
+                it["pitch_px"], it["rows"], it["x0"], it["y0"] = cw, ch, 0, 0
+        slab.copy_(host, non_blocking=True)
+        self._slab_event.record()
+
+    def homonet_synth_batch(self, indices, origins, sizes, windows, deltas, pic_size, patch_size, view="left", out=None):
+        """Synthetic-warp pairs ``(grey_a, patch_a, corners, delta, h, grey_b, patch_b)`` from ONE view of the pairs ``indices``, straight from
+        the stored bytes (``hesic_homonet_synth_items``, include/hesic_homonet_synth.h): crops, sizes and windows as in ``homonet_batch``,
+        ``deltas[i]`` the eight integer corner offsets of item i (``homography.draw_deltas``), ``view`` = ``"left"`` or ``"right"``; the
+        sampling convention is ``geometry.DEFAULT_ALIGN_CORNERS``, what ``homography.photometric_loss`` samples in.  ``"stream"`` mode reads
+        on the host and uploads only that view's crops.  ``out``: seven dense tensors to write into."""
+        from . import functional as Fn
+        from . import geometry
+        from .compressai.datasets import MEAN, STD
+        if view not in ("left", "right"):
+            raise ValueError(f'DevicePairCache.homonet_synth_batch: view is "left" or "right", got {view!r}')
+        geo = self._homonet_geometry("homonet_synth_batch", indices, origins, sizes, windows)
+        if len(deltas) != len(geo) or any(len(d) != 8 for d in deltas):
+            raise ValueError(f"DevicePairCache.homonet_synth_batch: {len(geo)} indices need as many deltas of eight integers")
+        items = Fn.homonet_synth_items(len(geo))
+        for it, (i, y0, x0, ch, cw, wx, wy), d in zip(items, geo, deltas):
+            h, w = self.sizes[i]
+            it["pitch_px"], it["rows"], it["x0"], it["y0"], it["cw"], it["ch"], it["wx"], it["wy"] = w, h, x0, y0, cw, ch, wx, wy
+            it["delta"] = [int(v) for v in d]
+        if self.mode == "device":
+            base = self.arena.data_ptr()
+            for it, g in zip(items, geo):
+                it["view"] = base + self.offsets[g[0]][view == "right"]
+        else:
+            self._stream_crops(items, geo, (int(view == "right"),), ("view",))
+        return Fn.homonet_synth(items, pic_size, patch_size, float(MEAN), float(STD), geometry.DEFAULT_ALIGN_CORNERS, out=out)

@@ -702,11 +702,10 @@ class HomographyTrainer:
         self.optimizer.param_groups[0]["lr"] = float(lr)
         self.optimizer.sync_lr()
 
-    def step(self, img_a, patch_a, patch_b, corners):
-        """zero the flat gradient -> train-mode forward -> photometric loss -> backward -> one Adam launch.  Returns device scalars."""
-        from . import homography
+    def _train_step(self, name, patch_a, patch_b, criterion):
+        """zero the flat gradient -> train-mode forward -> ``criterion(delta)`` -> backward -> one Adam launch.  Returns device scalars."""
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("HomographyTrainer.step is eager: the dropout step counter is passed to the kernels by value, a captured "
+            raise RuntimeError(f"HomographyTrainer.{name} is eager: the dropout step counter is passed to the kernels by value, a captured "
                                "graph would replay one mask forever")
         self.optimizer.sync_lr()
         self.net.train()
@@ -718,8 +717,7 @@ class HomographyTrainer:
             slots = Fn.grad_slots_active(True)        # gradient kernels write straight into the flat buffer (cleared above)
             try:
                 with torch.enable_grad():
-                    delta = self.net(patch_a, patch_b)
-                    loss = homography.photometric_loss(delta, img_a, patch_b, corners)
+                    loss = criterion(self.net(patch_a, patch_b))
                 loss.backward()
             finally:
                 Fn.grad_slots_active(slots)
@@ -733,18 +731,41 @@ class HomographyTrainer:
             out.update(_control_readout(self.optimizer))         # copies: this step never runs under capture
         return out
 
-    @torch.no_grad()
-    def evaluate(self, img_a, patch_a, patch_b, corners):
-        """The photometric loss of the net in eval mode (no dropout, no graph); the module's mode is left as it was."""
-        from . import homography
+    def _eval_delta(self, patch_a, patch_b):
+        """The net's deltas in eval mode (no dropout, no graph) with fp32 maps; the module's mode is left as it was."""
         was, prev_dtype = self.net.training, Fn.compute_dtype()
         self.net.eval()
         Fn.set_compute_dtype(torch.float32)
         try:
-            return homography.photometric_loss(self.net(patch_a, patch_b), img_a, patch_b, corners)
+            return self.net(patch_a, patch_b)
         finally:
             Fn.set_compute_dtype(prev_dtype)
             self.net.train(was)
+
+    def step(self, img_a, patch_a, patch_b, corners):
+        """zero the flat gradient -> train-mode forward -> photometric loss -> backward -> one Adam launch.  Returns device scalars."""
+        from . import homography
+        return self._train_step("step", patch_a, patch_b, lambda delta: homography.photometric_loss(delta, img_a, patch_b, corners))
+
+    @torch.no_grad()
+    def evaluate(self, img_a, patch_a, patch_b, corners):
+        """The photometric loss of the net in eval mode (no dropout, no graph); the module's mode is left as it was."""
+        from . import homography
+        return homography.photometric_loss(self._eval_delta(patch_a, patch_b), img_a, patch_b, corners)
+
+    def step_supervised(self, patch_a, patch_b, delta):
+        """``step`` with a known label (a synthetic warp, ``DevicePairCache.homonet_synth_batch``): ``loss = mse_loss(net(patch_a, patch_b),
+        delta)``, the mean over the 8 B numbers -- in torch, there is no hot path in it --, then the same backward, Adam launch, controls,
+        eager-only rule and return dict."""
+        return self._train_step("step_supervised", patch_a, patch_b, lambda out: torch.nn.functional.mse_loss(out, delta))
+
+    @torch.no_grad()
+    def evaluate_supervised(self, patch_a, patch_b, delta):
+        """``(loss, corner_error)`` of the net in eval mode against the label: the supervised MSE (a 0-d device tensor) and, per pair, the
+        mean corner error in pixels of the frame (``homography.corner_error``, a (B,) fp32 device tensor)."""
+        from . import homography
+        out = self._eval_delta(patch_a, patch_b)
+        return torch.nn.functional.mse_loss(out, delta), homography.corner_error(out, delta)
 
     def _prepare_pairs(self, x1, x2, xy, pic_size, rho, rng):
         from . import homography
