@@ -18,20 +18,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhesic_hip.so")
 LIB_PATH_F16 = os.path.join(_HERE, "libhesic_hip_f16.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_hip.h")
-STEREO_H_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_stereo_h.h")
-CODEC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_codec.h")
-MSSSIM_LOSS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_msssim_loss.h")
-TRAIN_CTL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_train_ctl.h")
-HOMOGRAPHY_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_train.h")
-HOMOGRAPHY_NET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_net.h")
-HOMOGRAPHY_PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homography_prep.h")
-HOMONET_ITEMS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homonet_items.h")
-HOMONET_SYNTH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_homonet_synth.h")
-PAIR_BATCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_batch.h")
-PAIR_AUGMENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_augment.h")
-PAIR_METRICS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_pair_metrics.h")
-EN_TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hesic_en_train.h")
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 F32, H16 = 0, 1
 ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
@@ -394,100 +381,34 @@ _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
 
 
-def declared_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_hip.h (used by the ABI test)."""
-    with open(HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+# every public header under include/ -> the signatures of the entry points its own text declares, in binding order.  A new header gets its
+# dict above and one line here; tests/test_abi.py holds the table to the directory, to the headers' text and to both libraries' exports
+HEADERS = {
+    "hesic_hip.h": _SIGS,
+    "hesic_stereo_h.h": _STEREO_H_SIGS,
+    "hesic_codec.h": _CODEC_SIGS,
+    "hesic_msssim_loss.h": _MSSSIM_LOSS_SIGS,
+    "hesic_train_ctl.h": _TRAIN_CTL_SIGS,
+    "hesic_homography_train.h": _HOMOGRAPHY_TRAIN_SIGS,
+    "hesic_homography_net.h": _HOMOGRAPHY_NET_SIGS,
+    "hesic_homography_prep.h": _HOMOGRAPHY_PREP_SIGS,
+    "hesic_homonet_items.h": _HOMONET_ITEMS_SIGS,
+    "hesic_homonet_synth.h": _HOMONET_SYNTH_SIGS,
+    "hesic_pair_batch.h": _PAIR_BATCH_SIGS,
+    "hesic_pair_augment.h": _PAIR_AUGMENT_SIGS,
+    "hesic_pair_metrics.h": _PAIR_METRICS_SIGS,
+    "hesic_en_train.h": _EN_TRAIN_SIGS,
+}
 
 
-def declared_stereo_h_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_stereo_h.h (used by the stereo-homography ABI test)."""
-    with open(STEREO_H_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
+def header_path(name):
+    """The path of the public header ``name`` (a key of ``HEADERS``) under include/."""
+    return os.path.join(_INCLUDE, name)
 
 
-def declared_codec_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_codec.h (used by the device-codec ABI test)."""
-    with open(CODEC_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_msssim_loss_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_msssim_loss.h (used by the MS-SSIM loss ABI test)."""
-    with open(MSSSIM_LOSS_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_train_ctl_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_train_ctl.h (used by the step-controls ABI test)."""
-    with open(TRAIN_CTL_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_homography_train_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_homography_train.h (used by the homography-training ABI test)."""
-    with open(HOMOGRAPHY_TRAIN_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_homography_net_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_homography_net.h (used by the HomographyNet-training ABI test)."""
-    with open(HOMOGRAPHY_NET_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_homography_prep_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_homography_prep.h (used by the HomographyNet input-preparation ABI test)."""
-    with open(HOMOGRAPHY_PREP_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_homonet_items_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_homonet_items.h (used by the item-form input-preparation ABI test)."""
-    with open(HOMONET_ITEMS_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_homonet_synth_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_homonet_synth.h (used by the synthetic-warp ABI test)."""
-    with open(HOMONET_SYNTH_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_pair_batch_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_pair_batch.h (used by the pair-batch ABI test)."""
-    with open(PAIR_BATCH_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_pair_augment_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_pair_augment.h (used by the pair-augmentation ABI test)."""
-    with open(PAIR_AUGMENT_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_pair_metrics_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_pair_metrics.h (used by the pair-metrics ABI test)."""
-    with open(PAIR_METRICS_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
-
-
-def declared_en_train_symbols():
-    """Every ``hesic_*`` function declared in include/hesic_en_train.h (used by the stage-2 training ABI test)."""
-    with open(EN_TRAIN_HEADER_PATH) as f:
+def declared_symbols(header="hesic_hip.h"):
+    """Every ``hesic_*`` function declared in the text of include/``header`` itself, not of the headers it includes (used by the ABI tests)."""
+    with open(header_path(header)) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(hesic_[a-z0-9_]+)\s*\(", text)))
 
@@ -511,14 +432,14 @@ def _load(h16):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} exports no hesic_abi_version -- not this package's library; {rebuild}") from None
         if ver != ABI_VERSION:
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} ABI version mismatch (library {ver}, package {ABI_VERSION}): {rebuild}")
-        for name, (args, res) in list(_SIGS.items()) + list(_STEREO_H_SIGS.items()) + list(_CODEC_SIGS.items()) + list(_MSSSIM_LOSS_SIGS.items()) \
-                + list(_TRAIN_CTL_SIGS.items()) + list(_HOMOGRAPHY_TRAIN_SIGS.items()) + list(_HOMOGRAPHY_NET_SIGS.items()) \
-                + list(_HOMOGRAPHY_PREP_SIGS.items()) + list(_HOMONET_ITEMS_SIGS.items()) + list(_HOMONET_SYNTH_SIGS.items()) + list(_PAIR_BATCH_SIGS.items()) + list(_PAIR_AUGMENT_SIGS.items()) + list(_PAIR_METRICS_SIGS.items()) + list(_EN_TRAIN_SIGS.items()):
-            try:
-                fn = getattr(l, name)
-            except AttributeError:
-                raise RuntimeError(f"hesic_amd: {os.path.basename(path)} lacks the entry point {name} although it reports ABI {ver}: {rebuild}") from None
-            fn.argtypes, fn.restype = args, res
+        for sigs in HEADERS.values():
+            for name, (args, res) in sigs.items():
+                try:
+                    fn = getattr(l, name)
+                except AttributeError:
+                    raise RuntimeError(f"hesic_amd: {os.path.basename(path)} lacks the entry point {name} although it reports ABI {ver}: "
+                                       f"{rebuild}") from None
+                fn.argtypes, fn.restype = args, res
         if l.hesic_h16_format() != (1 if h16 == torch.float16 else 0):
             raise RuntimeError(f"hesic_amd: {os.path.basename(path)} was built for the other 16-bit format")
         _libs[h16] = l

@@ -1981,6 +1981,70 @@ def h_from_delta(corners, delta, ratio_a, ratio_b, subtract_origin):
     return _apply(_HFromDeltaFn, corners, delta, float(ratio_a), float(ratio_b), int(subtract_origin))
 
 
+# The host path the descriptor-batch entries share (homonet_prepare_items, homonet_synth, both pair gathers): the items as a structured array,
+# the per-item checks, a device, the outputs, the upload; each wrapper below is these plus its own launch line.
+def _items_array(name, dtype_name, dtype, items):
+    """``items`` -- a 1-d structured array of ``dtype`` (the list called ``dtype_name``) or its bytes as a (B, itemsize) uint8 CPU tensor --
+    as the contiguous structured array."""
+    import numpy as np
+    dtype = np.dtype(dtype)
+    if torch.is_tensor(items):
+        if items.is_cuda or items.dtype != torch.uint8 or items.dim() != 2 or items.shape[1] != dtype.itemsize or not items.is_contiguous():
+            raise ValueError(f"{name}: items as a tensor must be a contiguous (B, {dtype.itemsize}) uint8 CPU tensor")
+        items = items.numpy().view(dtype).reshape(-1)
+    items = np.ascontiguousarray(items)
+    if items.dtype != dtype or items.ndim != 1:
+        raise ValueError(f"{name}: items must be a 1-d array of {dtype_name}")
+    return items
+
+
+def _item_fields(items):
+    """Every item's fields as a dict of Python integers (a sub-array field such as ``delta`` stays an array): one conversion for the whole
+    array, a third of the time of a read per field."""
+    return [dict(zip(items.dtype.names, row)) for row in items.tolist()]
+
+
+def _check_stored_crop(name, b, it, cw, ch):
+    """The stored-image, crop, column and row conditions of item ``b`` (``it``: its integer fields; ``cw``, ``ch``: the crop read from it)."""
+    if it["pitch_px"] < 1 or it["rows"] < 1:
+        raise ValueError(f"{name}: item {b} stored image {it['rows']} x {it['pitch_px']}")
+    if cw < 1 or ch < 1:
+        raise ValueError(f"{name}: item {b} crop {ch} x {cw} (at least one pixel each way)")
+    if not (0 <= it["x0"] and it["x0"] + cw <= it["pitch_px"]):
+        raise ValueError(f"{name}: item {b} columns [{it['x0']}, {it['x0'] + cw}) outside the stored image's {it['pitch_px']}")
+    if not (0 <= it["y0"] and it["y0"] + ch <= it["rows"]):
+        raise ValueError(f"{name}: item {b} rows [{it['y0']}, {it['y0'] + ch}) outside the stored image's {it['rows']}")
+
+
+def _launch_device(*given):
+    """The device a descriptor batch goes to: that of the first tensor of ``given`` that is not ``None``, else the current one.  Called after
+    the host checks and before anything is allocated."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("hesic_amd: the HIP path needs a ROCm device (no CPU fallback)")
+    for t in given:
+        if t is not None:
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _outputs(name, out, shapes, device, dtypes=None, what="fp32 tensors"):
+    """``out`` validated against ``shapes`` / ``dtypes`` (default: all fp32), or dense tensors of them allocated on ``device``."""
+    dtypes = dtypes or [torch.float32] * len(shapes)
+    if out is None:
+        return [torch.empty(s, dtype=d, device=device) for s, d in zip(shapes, dtypes)]
+    L.require_cuda(*out)
+    if len(out) != len(shapes) or any(tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, s, d in zip(out, shapes, dtypes)):
+        raise ValueError(f"{name}: out must be dense {what} of shapes {shapes}")
+    return out
+
+
+def _upload_items(items, device):
+    """The descriptors' bytes on ``device``, through a pinned copy: the caller may reuse ``items`` at once."""
+    import numpy as np
+    host = torch.from_numpy(items.view(np.uint8).reshape(len(items), items.dtype.itemsize)).pin_memory()
+    return host.to(device, non_blocking=True)
+
+
 def homonet_prepare(x1, x2, xy, pic_size, patch_size, mean, std, out=None):
     """``hesic_homonet_prepare`` (include/hesic_homography_prep.h): ``x1``, ``x2`` (B,3,H,W) uint8 or float32 in [0, 1] with any non-negative
     strides, ``xy`` (B,2) int32 window origins on the device (the CALLER checks 0 <= x, y <= pic_size - patch_size) ->
@@ -1996,14 +2060,7 @@ def homonet_prepare(x1, x2, xy, pic_size, patch_size, mean, std, out=None):
     S, P = int(pic_size), int(patch_size)
     if xy.dtype != torch.int32 or tuple(xy.shape) != (B, 2) or not xy.is_contiguous():
         raise ValueError(f"homonet_prepare: xy must be a contiguous int32 (B,2) tensor, got {xy.dtype} {tuple(xy.shape)}")
-    shapes = [(B, 1, S, S), (B, 1, S, S), (B, 1, P, P), (B, 1, P, P), (B, 4, 2)]
-    if out is None:
-        out = [torch.empty(s, dtype=torch.float32, device=x1.device) for s in shapes]
-    else:
-        L.require_cuda(*out)
-        for t, s in zip(out, shapes):
-            if tuple(t.shape) != s or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"homonet_prepare: out must be dense fp32 tensors of shapes {shapes}")
+    out = _outputs("homonet_prepare", out, [(B, 1, S, S), (B, 1, S, S), (B, 1, P, P), (B, 1, P, P), (B, 4, 2)], x1.device)
     L.call("hesic_homonet_prepare", L.ptr(x1), (C.c_int64 * 4)(*x1.stride()), L.ptr(x2), (C.c_int64 * 4)(*x2.stride()), L.ptr(xy), B, H, W, S, P,
            float(mean), float(std), L.PREP_F32 if x1.dtype == torch.float32 else L.PREP_U8, *[L.ptr(t) for t in out], L.stream())
     return tuple(out)
@@ -2022,14 +2079,7 @@ def homonet_items(batch):
 
 def _check_homonet_geometry(name, b, it, S, P):
     """The stored-image, crop and window conditions of item ``b`` that the item entries share (``it``: its integer fields)."""
-    if it["pitch_px"] < 1 or it["rows"] < 1:
-        raise ValueError(f"{name}: item {b} stored image {it['rows']} x {it['pitch_px']}")
-    if it["cw"] < 1 or it["ch"] < 1:
-        raise ValueError(f"{name}: item {b} crop {it['ch']} x {it['cw']} (at least one pixel each way)")
-    if not (0 <= it["x0"] and it["x0"] + it["cw"] <= it["pitch_px"]):
-        raise ValueError(f"{name}: item {b} columns [{it['x0']}, {it['x0'] + it['cw']}) outside the stored image's {it['pitch_px']}")
-    if not (0 <= it["y0"] and it["y0"] + it["ch"] <= it["rows"]):
-        raise ValueError(f"{name}: item {b} rows [{it['y0']}, {it['y0'] + it['ch']}) outside the stored image's {it['rows']}")
+    _check_stored_crop(name, b, it, it["cw"], it["ch"])
     if not (0 <= it["wx"] <= S - P and 0 <= it["wy"] <= S - P):
         raise ValueError(f"{name}: item {b} window origin ({it['wx']}, {it['wy']}) outside [0, {S - P}]")
 
@@ -2037,8 +2087,7 @@ def _check_homonet_geometry(name, b, it, S, P):
 def check_homonet_items(items, S, P):
     """The per-item conditions ``hesic_homonet_prepare_items`` leaves to its caller, on the host: ValueError names the first item that breaks one."""
     S, P = int(S), int(P)
-    for b in range(len(items)):
-        it = {k: int(items[b][k]) for k in items.dtype.names}
+    for b, it in enumerate(_item_fields(items)):
         if it["left"] == 0 or it["right"] == 0:
             raise ValueError(f"homonet_prepare_items: item {b} has a null view pointer")
         _check_homonet_geometry("homonet_prepare_items", b, it, S, P)
@@ -2050,31 +2099,14 @@ def homonet_prepare_items(items, pic_size, patch_size, mean, std, out=None):
     uint8 HWC images on the current device.  Every item is checked here, on the host (the C entry cannot read them); the descriptors are
     then uploaded and one launch writes ``(grey1, grey2, patch1, patch2, corners)``, fp32, the outputs of ``homonet_prepare`` on each
     item's crop.  ``out``: five preallocated dense fp32 tensors of those shapes."""
-    import numpy as np
-    if torch.is_tensor(items):
-        if items.is_cuda or items.dtype != torch.uint8 or items.dim() != 2 or items.shape[1] != 48 or not items.is_contiguous():
-            raise ValueError("homonet_prepare_items: items as a tensor must be a contiguous (B, 48) uint8 CPU tensor")
-        items = items.numpy().view(np.dtype(HOMONET_ITEM_DTYPE)).reshape(-1)
-    items = np.ascontiguousarray(items)
-    if items.dtype != np.dtype(HOMONET_ITEM_DTYPE) or items.ndim != 1:
-        raise ValueError("homonet_prepare_items: items must be a 1-d array of HOMONET_ITEM_DTYPE")
+    items = _items_array("homonet_prepare_items", "HOMONET_ITEM_DTYPE", HOMONET_ITEM_DTYPE, items)
     B, S, P = len(items), int(pic_size), int(patch_size)
     if not (1 <= B <= 65535 and 1 <= P <= S <= 16384):
         raise ValueError(f"homonet_prepare_items: need 1 <= B <= 65535 and 1 <= P <= S <= 16384, got B={B} S={S} P={P}")
     check_homonet_items(items, S, P)
-    if not torch.cuda.is_available():
-        raise RuntimeError("hesic_amd: the HIP path needs a ROCm device (no CPU fallback)")
-    dev = out[0].device if out is not None else torch.device("cuda", torch.cuda.current_device())
-    shapes = [(B, 1, S, S), (B, 1, S, S), (B, 1, P, P), (B, 1, P, P), (B, 4, 2)]
-    if out is None:
-        out = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
-    else:
-        L.require_cuda(*out)
-        for t, s in zip(out, shapes):
-            if tuple(t.shape) != s or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"homonet_prepare_items: out must be dense fp32 tensors of shapes {shapes}")
-    host = torch.from_numpy(items.view(np.uint8).reshape(B, 48)).pin_memory()        # a pinned copy: the caller may reuse ``items`` at once
-    items_dev = host.to(dev, non_blocking=True)
+    dev = _launch_device(*(out or ())[:1])
+    out = _outputs("homonet_prepare_items", out, [(B, 1, S, S), (B, 1, S, S), (B, 1, P, P), (B, 1, P, P), (B, 4, 2)], dev)
+    items_dev = _upload_items(items, dev)
     L.call("hesic_homonet_prepare_items", L.ptr(items_dev), B, S, P, float(mean), float(std), *[L.ptr(t) for t in out], L.stream())
     return tuple(out)
 
@@ -2107,12 +2139,11 @@ def check_homonet_synth_items(items, S, P):
     """The per-item conditions ``hesic_homonet_synth_items`` leaves to its caller, on the host: those of ``check_homonet_items`` for the one
     view, and the strict convexity of the perturbed quadrilateral.  ValueError names the first item that breaks one."""
     S, P = int(S), int(P)
-    for b in range(len(items)):
-        it = {k: int(items[b][k]) for k in items.dtype.names if k != "delta"}
+    for b, it in enumerate(_item_fields(items)):
         if it["view"] == 0:
             raise ValueError(f"homonet_synth: item {b} has a null view pointer")
         _check_homonet_geometry("homonet_synth", b, it, S, P)
-        delta = [int(v) for v in items[b]["delta"]]
+        delta = [int(v) for v in it["delta"]]
         if not perturbed_quad_is_convex(it["wx"], it["wy"], P, delta):
             raise ValueError(f"homonet_synth: item {b} corners + delta {delta} is not a strictly convex quadrilateral")
 
@@ -2123,31 +2154,15 @@ def homonet_synth(items, pic_size, patch_size, mean, std, align_corners, out=Non
     of a uint8 HWC image on the current device.  Every item is checked here, on the host; the descriptors are then uploaded and the entry
     writes ``(grey_a, patch_a, corners, delta, h, grey_b, patch_b)``: fp32 but for ``h`` (B, 9) fp64.  ``out``: seven preallocated dense
     tensors of those shapes and types."""
-    import numpy as np
-    if torch.is_tensor(items):
-        if items.is_cuda or items.dtype != torch.uint8 or items.dim() != 2 or items.shape[1] != 72 or not items.is_contiguous():
-            raise ValueError("homonet_synth: items as a tensor must be a contiguous (B, 72) uint8 CPU tensor")
-        items = items.numpy().view(np.dtype(HOMONET_SYNTH_ITEM_DTYPE)).reshape(-1)
-    items = np.ascontiguousarray(items)
-    if items.dtype != np.dtype(HOMONET_SYNTH_ITEM_DTYPE) or items.ndim != 1:
-        raise ValueError("homonet_synth: items must be a 1-d array of HOMONET_SYNTH_ITEM_DTYPE")
+    items = _items_array("homonet_synth", "HOMONET_SYNTH_ITEM_DTYPE", HOMONET_SYNTH_ITEM_DTYPE, items)
     B, S, P = len(items), int(pic_size), int(patch_size)
     if not (1 <= B <= 65535 and 1 <= P <= S <= 16384):
         raise ValueError(f"homonet_synth: need 1 <= B <= 65535 and 1 <= P <= S <= 16384, got B={B} S={S} P={P}")
     check_homonet_synth_items(items, S, P)
-    if not torch.cuda.is_available():
-        raise RuntimeError("hesic_amd: the HIP path needs a ROCm device (no CPU fallback)")
-    dev = out[0].device if out is not None else torch.device("cuda", torch.cuda.current_device())
-    shapes = [(B, 1, S, S), (B, 1, P, P), (B, 4, 2), (B, 4, 2), (B, 9), (B, 1, S, S), (B, 1, P, P)]
-    dtypes = [torch.float32] * 4 + [torch.float64] + [torch.float32] * 2
-    if out is None:
-        out = [torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes)]
-    else:
-        L.require_cuda(*out)
-        if len(out) != 7 or any(tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, s, d in zip(out, shapes, dtypes)):
-            raise ValueError(f"homonet_synth: out must be dense fp32 tensors (h: fp64) of shapes {shapes}")
-    host = torch.from_numpy(items.view(np.uint8).reshape(B, 72)).pin_memory()        # a pinned copy: the caller may reuse ``items`` at once
-    items_dev = host.to(dev, non_blocking=True)
+    dev = _launch_device(*(out or ())[:1])
+    out = _outputs("homonet_synth", out, [(B, 1, S, S), (B, 1, P, P), (B, 4, 2), (B, 4, 2), (B, 9), (B, 1, S, S), (B, 1, P, P)], dev,
+                   [torch.float32] * 4 + [torch.float64] + [torch.float32] * 2, "fp32 tensors (h: fp64)")
+    items_dev = _upload_items(items, dev)
     L.call("hesic_homonet_synth_items", L.ptr(items_dev), B, S, P, float(mean), float(std), int(bool(align_corners)),
            *[L.ptr(t) for t in out], L.stream())
     return tuple(out)
@@ -2171,35 +2186,20 @@ PAIR_FLAG_MASK = PAIR_HFLIP | PAIR_VFLIP | PAIR_SWAP
 def check_pair_items(items, n_table, ph, pw, flag_mask=0, name="pair_batch_gather"):
     """The per-item conditions ``hesic_pair_batch_gather`` leaves to its caller, on the host: ValueError names the first item that breaks one.
     ``flag_mask``: the bits ``reserved`` may hold (none for the plain entry, ``PAIR_FLAG_MASK`` for ``hesic_pair_batch_gather_aug``)."""
-    for b in range(len(items)):
-        it = items[b]
-        if int(it["left"]) == 0 or int(it["right"]) == 0:
+    for b, it in enumerate(_item_fields(items)):
+        if it["left"] == 0 or it["right"] == 0:
             raise ValueError(f"{name}: item {b} has a null view pointer")
-        if int(it["pitch_px"]) < 1 or int(it["rows"]) < 1:
-            raise ValueError(f"{name}: item {b} stored image {int(it['rows'])} x {int(it['pitch_px'])}")
-        if not (0 <= int(it["x0"]) and int(it["x0"]) + pw <= int(it["pitch_px"])):
-            raise ValueError(f"{name}: item {b} columns [{int(it['x0'])}, {int(it['x0']) + pw}) outside the stored image's "
-                             f"{int(it['pitch_px'])}")
-        if not (0 <= int(it["y0"]) and int(it["y0"]) + ph <= int(it["rows"])):
-            raise ValueError(f"{name}: item {b} rows [{int(it['y0'])}, {int(it['y0']) + ph}) outside the stored image's "
-                             f"{int(it['rows'])}")
-        if not -1 <= int(it["h_index"]) < n_table:
-            raise ValueError(f"{name}: item {b} h_index {int(it['h_index'])} outside [-1, {n_table})")
-        if int(it["reserved"]) & ~flag_mask:
+        _check_stored_crop(name, b, it, pw, ph)
+        if not -1 <= it["h_index"] < n_table:
+            raise ValueError(f"{name}: item {b} h_index {it['h_index']} outside [-1, {n_table})")
+        if it["reserved"] & ~flag_mask:
             raise ValueError(f"{name}: item {b} reserved field must be 0" if not flag_mask else
-                             f"{name}: item {b} reserved field {int(it['reserved'])} holds bits other than HFLIP = 1, VFLIP = 2, SWAP = 4")
+                             f"{name}: item {b} reserved field {it['reserved']} holds bits other than HFLIP = 1, VFLIP = 2, SWAP = 4")
 
 
 def _pair_batch_gather(name, flag_mask, items, h_table, ph, pw, out):
     """Both gather entries: the host checks, the upload of the descriptors, one launch of ``hesic_<name>``."""
-    import numpy as np
-    if torch.is_tensor(items):
-        if items.is_cuda or items.dtype != torch.uint8 or items.dim() != 2 or items.shape[1] != 48 or not items.is_contiguous():
-            raise ValueError(f"{name}: items as a tensor must be a contiguous (B, 48) uint8 CPU tensor")
-        items = items.numpy().view(np.dtype(PAIR_ITEM_DTYPE)).reshape(-1)
-    items = np.ascontiguousarray(items)
-    if items.dtype != np.dtype(PAIR_ITEM_DTYPE) or items.ndim != 1:
-        raise ValueError(f"{name}: items must be a 1-d array of PAIR_ITEM_DTYPE")
+    items = _items_array(name, "PAIR_ITEM_DTYPE", PAIR_ITEM_DTYPE, items)
     B, ph, pw = len(items), int(ph), int(pw)
     if B < 1 or ph < 1 or pw < 1:
         raise ValueError(f"{name}: bad shape B={B} ph={ph} pw={pw}")
@@ -2210,19 +2210,9 @@ def _pair_batch_gather(name, flag_mask, items, h_table, ph, pw, out):
             raise ValueError(f"{name}: h_table must be a dense fp64 (N, 9) tensor, got {h_table.dtype} {tuple(h_table.shape)}")
         n_table = h_table.shape[0]
     check_pair_items(items, n_table, ph, pw, flag_mask, name)
-    if not torch.cuda.is_available():
-        raise RuntimeError("hesic_amd: the HIP path needs a ROCm device (no CPU fallback)")
-    dev = h_table.device if h_table is not None else (out[0].device if out is not None else torch.device("cuda", torch.cuda.current_device()))
-    shapes = [(B, 3, ph, pw), (B, 3, ph, pw), (B, 3, 3)]
-    if out is None:
-        out = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
-    else:
-        L.require_cuda(*out)
-        for t, s in zip(out, shapes):
-            if tuple(t.shape) != s or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{name}: out must be dense fp32 tensors of shapes {shapes}")
-    host = torch.from_numpy(items.view(np.uint8).reshape(B, 48)).pin_memory()        # a pinned copy: the caller may reuse ``items`` at once
-    items_dev = host.to(dev, non_blocking=True)
+    dev = _launch_device(h_table, *(out or ())[:1])
+    out = _outputs(name, out, [(B, 3, ph, pw), (B, 3, ph, pw), (B, 3, 3)], dev)
+    items_dev = _upload_items(items, dev)
     L.call("hesic_" + name, L.ptr(items_dev), L.ptr(h_table), B, ph, pw, *[L.ptr(t) for t in out], L.stream())
     return tuple(out)
 

@@ -213,9 +213,6 @@ class DevicePairCache:
         torch.cuda.synchronize(self.device)
         self.decode_seconds = time.time() - t0
 
-    def _stream_slab(self, B, ph, pw):
-        return self._stream_bytes(2 * B * ph * pw * 3)
-
     def _stream_bytes(self, n):
         """The first ``n`` bytes of the reused device slab and of its pinned host twin, both grown when the batch at hand needs more."""
         if self._slab is None or self._slab.numel() < n:
@@ -242,46 +239,19 @@ class DevicePairCache:
         flags = [0] * B if flags is None else [int(f) for f in flags]
         if len(flags) != B:
             raise ValueError(f"DevicePairCache.batch: {B} indices and {len(flags)} flags")
+        geo = self._crops("batch", indices, origins, [(ph, pw)] * B, sized=False)      # a patch of no pixels: the gather's "bad shape"
         items = Fn.pair_items(B)
         items["reserved"] = flags
-        for b, (i, (y0, x0)) in enumerate(zip(indices, origins)):
-            if not 0 <= i < len(self):
-                raise IndexError(f"DevicePairCache.batch: pair {i} outside [0, {len(self)})")
-            h, w = self.sizes[i]
-            if not (0 <= x0 and x0 + pw <= w and 0 <= y0 and y0 + ph <= h):
-                raise ValueError(f"DevicePairCache.batch: crop ({ph}, {pw}) at ({y0}, {x0}) outside pair {i}'s image ({h}, {w})")
-            items[b]["hx"], items[b]["hy"], items[b]["h_index"] = x0, y0, self.h_index[i]
-        if self.mode == "device":
-            base = self.arena.data_ptr()
-            for b, (i, (y0, x0)) in enumerate(zip(indices, origins)):
-                it = items[b]
-                it["left"], it["right"] = base + self.offsets[i][0], base + self.offsets[i][1]
-                it["pitch_px"], it["rows"], it["x0"], it["y0"] = self.sizes[i][1], self.sizes[i][0], x0, y0
-        else:
-            slab, host = self._stream_slab(B, ph, pw)
-            crops = host.numpy().reshape(B, 2, ph, pw, 3)
-            with ThreadPoolExecutor(max_workers=self.workers) as pool:
-                for b, (a, c) in enumerate(pool.map(self._read, indices)):
-                    y0, x0 = origins[b]
-                    crops[b, 0], crops[b, 1] = a[y0:y0 + ph, x0:x0 + pw], c[y0:y0 + ph, x0:x0 + pw]
-            slab.copy_(host, non_blocking=True)
-            self._slab_event.record()
-            base, n = slab.data_ptr(), ph * pw * 3
-            for b in range(B):
-                it = items[b]
-                it["left"], it["right"] = base + (2 * b) * n, base + (2 * b + 1) * n
-                it["pitch_px"], it["rows"], it["x0"], it["y0"] = pw, ph, 0, 0
+        pairs, items["hy"], items["hx"], _, _ = zip(*geo)
+        items["h_index"] = [self.h_index[i] for i in pairs]
+        self._place(items, geo, (0, 1), ("left", "right"))
         gather = Fn.pair_batch_gather_aug if any(flags) else Fn.pair_batch_gather
         x1, x2, hm = gather(items, self.h_table, ph, pw, out=out)
         return x1, x2, hm, torch.tensor([self.has_h[i] for i in indices], dtype=torch.bool)
 
-    def _homonet_geometry(self, name, indices, origins, sizes, windows):
-        """``[(pair, y0, x0, ch, cw, wx, wy)]`` of a HomographyNet batch, checked against the listing (``name``: the calling method)."""
-        indices = [int(i) for i in indices]
-        B = len(indices)
-        if B < 1 or len(windows) != B or (sizes is None and origins is not None and len(origins) != B) or \
-                (sizes is not None and (len(sizes) != B or len(origins) != B)):
-            raise ValueError(f"DevicePairCache.{name}: {B} indices need as many origins, sizes and windows")
+    def _crops(self, name, indices, origins, sizes, sized=True):
+        """``[(pair, y0, x0, ch, cw)]`` of a batch, checked against the listing: every pair listed, every crop inside its pair's image and,
+        when ``sized``, of at least one pixel each way (``name``: the calling method).  ``sizes=None``: every whole image at (0, 0)."""
         geo = []
         for b, i in enumerate(indices):
             if not 0 <= i < len(self):
@@ -289,10 +259,36 @@ class DevicePairCache:
             h, w = self.sizes[i]
             (y0, x0), (ch, cw) = ((0, 0), (h, w)) if sizes is None else (origins[b], sizes[b])
             y0, x0, ch, cw = int(y0), int(x0), int(ch), int(cw)
-            if not (ch >= 1 and cw >= 1 and 0 <= x0 and x0 + cw <= w and 0 <= y0 and y0 + ch <= h):
+            if not ((not sized or (ch >= 1 and cw >= 1)) and 0 <= x0 and x0 + cw <= w and 0 <= y0 and y0 + ch <= h):
                 raise ValueError(f"DevicePairCache.{name}: crop ({ch}, {cw}) at ({y0}, {x0}) outside pair {i}'s image ({h}, {w})")
-            geo.append((i, y0, x0, ch, cw, int(windows[b][0]), int(windows[b][1])))
+            geo.append((i, y0, x0, ch, cw))
         return geo
+
+    def _place(self, items, geo, views, fields):
+        """Point the descriptors at their crops: per item the address of each of ``views`` (0: left, 1: right) in the field of ``fields`` that
+        goes with it, and the geometry of what that address holds -- the stored image in the arena, or the crop packed into the slab."""
+        if self.mode != "device":
+            return self._stream_crops(items, geo, views, fields)
+        base, (pairs, y0, x0, _, _) = self.arena.data_ptr(), zip(*geo)          # a column per field: an assignment per item costs twice the time
+        for f, v in zip(fields, views):
+            items[f] = [base + self.offsets[i][v] for i in pairs]
+        items["pitch_px"], items["rows"] = [self.sizes[i][1] for i in pairs], [self.sizes[i][0] for i in pairs]
+        items["x0"], items["y0"] = x0, y0
+
+    def _homonet_geometry(self, name, indices, origins, sizes, windows):
+        """The crops of a HomographyNet batch (``_crops``) after the count check its two methods share."""
+        indices = [int(i) for i in indices]
+        B = len(indices)
+        if B < 1 or len(windows) != B or (sizes is None and origins is not None and len(origins) != B) or \
+                (sizes is not None and (len(sizes) != B or len(origins) != B)):
+            raise ValueError(f"DevicePairCache.{name}: {B} indices need as many origins, sizes and windows")
+        return self._crops(name, indices, origins, sizes)
+
+    def _homonet_place(self, items, geo, windows, views, fields):
+        """The crop sizes and windows of a HomographyNet batch into its descriptors, then ``_place``."""
+        _, _, _, items["ch"], items["cw"] = zip(*geo)
+        items["wx"], items["wy"] = zip(*((int(wx), int(wy)) for wx, wy in windows))
+        self._place(items, geo, views, fields)
 
     def homonet_batch(self, indices, origins, sizes, windows, pic_size, patch_size, out=None):
         """HomographyNet's inputs ``(grey1, grey2, patch1, patch2, corners)`` of the pairs ``indices``, straight from the stored bytes in
@@ -305,27 +301,19 @@ class DevicePairCache:
         from .compressai.datasets import MEAN, STD
         geo = self._homonet_geometry("homonet_batch", indices, origins, sizes, windows)
         items = Fn.homonet_items(len(geo))
-        for it, (i, y0, x0, ch, cw, wx, wy) in zip(items, geo):
-            h, w = self.sizes[i]
-            it["pitch_px"], it["rows"], it["x0"], it["y0"], it["cw"], it["ch"], it["wx"], it["wy"] = w, h, x0, y0, cw, ch, wx, wy
-        if self.mode == "device":
-            base = self.arena.data_ptr()
-            for it, g in zip(items, geo):
-                it["left"], it["right"] = base + self.offsets[g[0]][0], base + self.offsets[g[0]][1]
-        else:
-            self._stream_crops(items, geo, (0, 1), ("left", "right"))
+        self._homonet_place(items, geo, windows, (0, 1), ("left", "right"))
         return Fn.homonet_prepare_items(items, pic_size, patch_size, float(MEAN), float(STD), out=out)
 
     def _stream_crops(self, items, geo, views, fields):
         """``"stream"`` mode: read the batch's pairs on the host, pack the crops of ``views`` (0: left, 1: right) back to back into the reused
         slab, start the upload, put each crop's address into the descriptor field of ``fields`` that goes with its view, and re-base the
         descriptors' geometry onto the packed crops."""
-        nbytes = [ch * cw * 3 for _, _, _, ch, cw, _, _ in geo]
+        nbytes = [ch * cw * 3 for _, _, _, ch, cw in geo]
         slab, host = self._stream_bytes(len(fields) * sum(nbytes))
         flat = host.numpy()
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             off = 0
-            for it, (_, y0, x0, ch, cw, _, _), n, pair in zip(items, geo, nbytes, pool.map(self._read, [g[0] for g in geo])):
+            for it, (_, y0, x0, ch, cw), n, pair in zip(items, geo, nbytes, pool.map(self._read, [g[0] for g in geo])):
                 for f, v in zip(fields, views):
                     flat[off:off + n].reshape(ch, cw, 3)[...] = pair[v][y0:y0 + ch, x0:x0 + cw]
                     it[f] = slab.data_ptr() + off
@@ -349,14 +337,6 @@ class DevicePairCache:
         if len(deltas) != len(geo) or any(len(d) != 8 for d in deltas):
             raise ValueError(f"DevicePairCache.homonet_synth_batch: {len(geo)} indices need as many deltas of eight integers")
         items = Fn.homonet_synth_items(len(geo))
-        for it, (i, y0, x0, ch, cw, wx, wy), d in zip(items, geo, deltas):
-            h, w = self.sizes[i]
-            it["pitch_px"], it["rows"], it["x0"], it["y0"], it["cw"], it["ch"], it["wx"], it["wy"] = w, h, x0, y0, cw, ch, wx, wy
-            it["delta"] = [int(v) for v in d]
-        if self.mode == "device":
-            base = self.arena.data_ptr()
-            for it, g in zip(items, geo):
-                it["view"] = base + self.offsets[g[0]][view == "right"]
-        else:
-            self._stream_crops(items, geo, (int(view == "right"),), ("view",))
+        items["delta"] = [[int(v) for v in d] for d in deltas]
+        self._homonet_place(items, geo, windows, (int(view == "right"),), ("view",))
         return Fn.homonet_synth(items, pic_size, patch_size, float(MEAN), float(STD), geometry.DEFAULT_ALIGN_CORNERS, out=out)

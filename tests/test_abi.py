@@ -34,6 +34,48 @@ def test_library_exports_every_declared_symbol(fmt):
     assert set(declared) == set(L._SIGS), (set(declared) ^ set(L._SIGS))
 
 
+def test_every_public_header_is_registered():
+    """The ``*.h`` files under include/ are exactly the keys of ``HEADERS``, hesic_hip.h first: a header nobody registered -- whose entry
+    points ``_load`` would then never bind -- fails here."""
+    L = _lib()
+    include = os.path.dirname(L.header_path("hesic_hip.h"))
+    assert sorted(f for f in os.listdir(include) if f.endswith(".h")) == sorted(L.HEADERS)
+    assert list(L.HEADERS)[0] == "hesic_hip.h" and L.HEADERS["hesic_hip.h"] is L._SIGS
+    assert all(os.path.isfile(L.header_path(h)) for h in L.HEADERS)
+
+
+@pytest.mark.parametrize("fmt", ["bf16", "f16"])
+def test_every_header_is_bound_and_exported(fmt):
+    """For every header: the functions its text declares are the keys of its dict, and the library exports each one."""
+    L = _lib()
+    exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
+    for header, sigs in L.HEADERS.items():
+        declared = L.declared_symbols(header)
+        assert declared and set(declared) == set(sigs), (header, set(declared) ^ set(sigs))
+        missing = [s for s in declared if f" T {s}\n" not in exported]
+        assert not missing, (header, missing)
+
+
+def test_headers_share_no_symbol_but_through_an_include():
+    """``declared_symbols`` reads a header's own text, so the dicts are pairwise disjoint without exception: every entry point is declared in
+    one header and bound once.  Where a public header includes another -- hesic_hip.h includes hesic_msssim_loss.h, hesic_homography_prep.h
+    includes hesic_homonet_items.h, among others -- a translation unit that includes the first sees the second's declarations too, and only
+    that way: the included header is a public one registered by itself, and the includer's text repeats none of its symbols."""
+    import itertools
+    import re
+    L = _lib()
+    for (ha, a), (hb, b) in itertools.combinations(L.HEADERS.items(), 2):
+        assert not set(a) & set(b), (ha, hb, set(a) & set(b))
+    includes = {(h, inc) for h in L.HEADERS for inc in re.findall(r'#include\s+"([^"]+)"', open(L.header_path(h)).read())}
+    assert {("hesic_hip.h", "hesic_msssim_loss.h"), ("hesic_homography_prep.h", "hesic_homonet_items.h")} <= includes
+    for includer, included in includes:
+        assert included in L.HEADERS and included != includer, (includer, included)
+        assert not set(L.declared_symbols(includer)) & set(L.HEADERS[included]), (includer, included)
+    # so what one include of the two includers named above declares is its own dict and the included header's, each symbol once
+    assert "hesic_ssim_scale_backward" in L.HEADERS["hesic_msssim_loss.h"] and "hesic_ssim_scale_backward" not in L._SIGS
+    assert "hesic_homonet_prepare_items" in L.HEADERS["hesic_homonet_items.h"] and "hesic_homonet_prepare_items" not in L._HOMOGRAPHY_PREP_SIGS
+
+
 def test_compute_dtype_selects_the_library():
     """set_compute_dtype(float16 / bfloat16) binds the library built for that format; a tensor of the OTHER 16-bit format is refused
     loudly (no silent reinterpretation of its bits); fp32 goes to whichever library is active."""

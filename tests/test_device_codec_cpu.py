@@ -159,7 +159,7 @@ def _L():
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_library_exports_every_codec_symbol(fmt):
     L = _L()
-    declared = L.declared_codec_symbols()
+    declared = L.declared_symbols("hesic_codec.h")
     assert len(declared) >= 4 and "hesic_gmm_rc_decode" in declared and "hesic_rc_encode_streams" in declared
     path = L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH
     L.lib(torch.float16 if fmt == "f16" else torch.bfloat16)

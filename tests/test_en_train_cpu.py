@@ -110,11 +110,11 @@ def test_mirror_equals_mirror_t(cout, cin, pad):
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_abi_header_bindings_exports(fmt):
     L = _lib()
-    declared = L.declared_en_train_symbols()
+    declared = L.declared_symbols("hesic_en_train.h")
     assert declared == ["hesic_c32_mirror_weights", "hesic_en_loss", "hesic_en_loss_grad", "hesic_en_loss_ws_bytes"]
     assert set(declared) == set(L._EN_TRAIN_SIGS)
     assert not set(declared) & set(L.declared_symbols())                # a header of its own: include/hesic_hip.h does not list it
-    assert "hesic_en_train.h" not in open(L.HEADER_PATH).read()
+    assert "hesic_en_train.h" not in open(L.header_path("hesic_hip.h")).read()
     assert C.sizeof(L.MirrorEntry) == 32
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in declared:

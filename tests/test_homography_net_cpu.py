@@ -142,15 +142,15 @@ def test_torch_fp32_linear_is_inside_the_bars(tag, act):
 # -------------------------------------------------------------------------------------------------------------------------- ABI
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_abi_header_bindings_exports(fmt):
-    declared = L.declared_homography_net_symbols()
+    declared = L.declared_symbols("hesic_homography_net.h")
     assert declared == ["hesic_bias_grad", "hesic_flatten_dropout_backward", "hesic_flatten_dropout_forward", "hesic_linear_dgrad",
                         "hesic_linear_forward", "hesic_linear_forward_ws_bytes", "hesic_linear_wgrad", "hesic_maxpool2_backward",
                         "hesic_narrow_in_wgrad"]
     assert set(declared) == set(L._HOMOGRAPHY_NET_SIGS)
     assert not set(declared) & set(L.declared_symbols())                # a header of its own: include/hesic_hip.h does not list them
-    assert f"#define HESIC_LINEAR_MAX_ROWS {L.LINEAR_MAX_ROWS}\n" in open(L.HOMOGRAPHY_NET_HEADER_PATH).read()
-    assert f"#define HESIC_DET_MAX_BLOCKS {L.DET_MAX_BLOCKS}\n" in open(L.HOMOGRAPHY_NET_HEADER_PATH).read()
-    assert "#define HESIC_ABI_VERSION 2" in open(L.HEADER_PATH).read() and L.ABI_VERSION == 2
+    assert f"#define HESIC_LINEAR_MAX_ROWS {L.LINEAR_MAX_ROWS}\n" in open(L.header_path("hesic_homography_net.h")).read()
+    assert f"#define HESIC_DET_MAX_BLOCKS {L.DET_MAX_BLOCKS}\n" in open(L.header_path("hesic_homography_net.h")).read()
+    assert "#define HESIC_ABI_VERSION 2" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 2
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in declared:
         assert f" T {s}\n" in exported, s

@@ -18,13 +18,13 @@ from hesic_amd.compressai.datasets import MEAN, STD
 # ------------------------------------------------------------------------------------------------------------------------ ABI
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_abi_header_bindings_exports(fmt):
-    declared = L.declared_homography_prep_symbols()
+    declared = L.declared_symbols("hesic_homography_prep.h")
     assert declared == ["hesic_homonet_prepare"]
     assert set(declared) == set(L._HOMOGRAPHY_PREP_SIGS)
     assert not set(declared) & set(L.declared_symbols())                # a header of its own: include/hesic_hip.h does not list it
-    text = open(L.HOMOGRAPHY_PREP_HEADER_PATH).read()
+    text = open(L.header_path("hesic_homography_prep.h")).read()
     assert f"#define HESIC_PREP_U8 {L.PREP_U8} " in text and f"#define HESIC_PREP_F32 {L.PREP_F32} " in text
-    assert "#define HESIC_ABI_VERSION 2" in open(L.HEADER_PATH).read() and L.ABI_VERSION == 2
+    assert "#define HESIC_ABI_VERSION 2" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 2
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in declared:
         assert f" T {s}\n" in exported, s

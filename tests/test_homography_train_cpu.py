@@ -18,15 +18,15 @@ def _rel(a, b):
 
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_abi_header_bindings_exports(fmt):
-    declared = L.declared_homography_train_symbols()
+    declared = L.declared_symbols("hesic_homography_train.h")
     assert declared == ["hesic_h_from_delta_backward", "hesic_perspective_transform_backward", "hesic_photometric_backward",
                         "hesic_photometric_forward", "hesic_warp_perspective_backward_m"]
     assert set(declared) == set(L._HOMOGRAPHY_TRAIN_SIGS)
     assert not set(declared) & set(L.declared_symbols())                # a header of its own: include/hesic_hip.h does not list them
-    text = open(L.HOMOGRAPHY_TRAIN_HEADER_PATH).read()
+    text = open(L.header_path("hesic_homography_train.h")).read()
     assert f"#define HESIC_HTRAIN_MAX_BLOCKS {L.HTRAIN_MAX_BLOCKS}\n" in text
     assert f"#define HESIC_HTRAIN_PARTIAL_WIDTH {L.HTRAIN_PARTIAL_WIDTH}\n" in text
-    assert "#define HESIC_ABI_VERSION 2" in open(L.HEADER_PATH).read() and L.ABI_VERSION == 2
+    assert "#define HESIC_ABI_VERSION 2" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 2
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in declared:
         assert f" T {s}\n" in exported, s

@@ -26,7 +26,7 @@ def test_item_dtype_is_the_headers_struct():
     assert C.sizeof(L.HomonetItem) == 48 and [(n, getattr(L.HomonetItem, n).offset) for n, _ in L.HomonetItem._fields_] == \
         [(n, dt.fields[n][1]) for n in FIELDS]
     # the struct as the header spells it: two pointers, then the eight int32 in this order
-    text = re.sub(r"/\*.*?\*/", "", open(L.HOMONET_ITEMS_HEADER_PATH).read(), flags=re.S)
+    text = re.sub(r"/\*.*?\*/", "", open(L.header_path("hesic_homonet_items.h")).read(), flags=re.S)
     body = re.search(r"typedef struct \{(.*?)\} hesic_homonet_item;", text, flags=re.S).group(1)
     assert tuple(re.findall(r"\b([a-z_0-9]+)\s*[,;]", body)) == FIELDS
     assert body.count("const uint8_t*") == 2 and body.count("int32_t") == 4
@@ -36,9 +36,9 @@ def test_item_dtype_is_the_headers_struct():
 
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_abi_header_bindings_exports(fmt):
-    declared = L.declared_homonet_items_symbols()
+    declared = L.declared_symbols("hesic_homonet_items.h")
     assert declared == ["hesic_homonet_prepare_items"] and set(declared) == set(L._HOMONET_ITEMS_SIGS)
-    assert '#include "hesic_homonet_items.h"' in open(L.HOMOGRAPHY_PREP_HEADER_PATH).read()       # one include serves both forms
+    assert '#include "hesic_homonet_items.h"' in open(L.header_path("hesic_homography_prep.h")).read()       # one include serves both forms
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     assert " T hesic_homonet_prepare_items\n" in exported
 

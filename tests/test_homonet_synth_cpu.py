@@ -29,7 +29,7 @@ def test_item_dtype_is_the_headers_struct():
     assert dt.fields["view"][0] == np.dtype("<u8") and dt.fields["delta"][0] == np.dtype(("<i4", (8,)))
     assert C.sizeof(L.HomonetSynthItem) == 72 and [(n, getattr(L.HomonetSynthItem, n).offset) for n, _ in L.HomonetSynthItem._fields_] == \
         [(n, dt.fields[n][1]) for n in FIELDS]
-    text = re.sub(r"/\*.*?\*/", "", open(L.HOMONET_SYNTH_HEADER_PATH).read(), flags=re.S)
+    text = re.sub(r"/\*.*?\*/", "", open(L.header_path("hesic_homonet_synth.h")).read(), flags=re.S)
     body = re.search(r"typedef struct \{(.*?)\} hesic_homonet_synth_item;", text, flags=re.S).group(1)
     assert tuple(re.findall(r"\b([a-z_0-9]+)(?:\[8\])?\s*[,;]", body)) == FIELDS
     assert body.count("const uint8_t*") == 1 and "int32_t delta[8]" in body
@@ -39,9 +39,9 @@ def test_item_dtype_is_the_headers_struct():
 
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_abi_header_bindings_exports(fmt):
-    declared = L.declared_homonet_synth_symbols()
+    declared = L.declared_symbols("hesic_homonet_synth.h")
     assert declared == ["hesic_homonet_synth_items"] and set(declared) == set(L._HOMONET_SYNTH_SIGS)
-    assert "hesic_homonet_synth" not in open(L.HEADER_PATH).read()                  # hesic_hip.h does not include it
+    assert "hesic_homonet_synth" not in open(L.header_path("hesic_hip.h")).read()                  # hesic_hip.h does not include it
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     assert " T hesic_homonet_synth_items\n" in exported
 

@@ -141,7 +141,7 @@ def _L():
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_both_libraries_export_the_new_symbols(fmt):
     L = _L()
-    declared = L.declared_codec_symbols()
+    declared = L.declared_symbols("hesic_codec.h")
     assert all(s in declared for s in NEW_SYMBOLS)
     path = L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH
     L.lib(torch.float16 if fmt == "f16" else torch.bfloat16)

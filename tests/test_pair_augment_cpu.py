@@ -207,11 +207,11 @@ def test_validation_and_unknown_names_are_refused():
 # ------------------------------------------------------------------------------------------------------------------------ ABI
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_abi_header_bindings_exports(fmt):
-    declared = L.declared_pair_augment_symbols()
+    declared = L.declared_symbols("hesic_pair_augment.h")
     assert declared == ["hesic_pair_batch_gather_aug"] and set(declared) == set(L._PAIR_AUGMENT_SIGS)
     assert L._PAIR_AUGMENT_SIGS["hesic_pair_batch_gather_aug"] == L._PAIR_BATCH_SIGS["hesic_pair_batch_gather"]        # the same arguments
     assert not set(declared) & set(L.declared_symbols()) and L.ABI_VERSION == 2
-    text = open(L.PAIR_AUGMENT_HEADER_PATH).read()
+    text = open(L.header_path("hesic_pair_augment.h")).read()
     for name, bit in (("HFLIP", L.PAIR_HFLIP), ("VFLIP", L.PAIR_VFLIP), ("SWAP", L.PAIR_SWAP)):
         assert f"#define HESIC_PAIR_{name} {bit}" in text and pair_cache.AUGMENT_BITS[name.lower()] == bit
     assert (Fn.PAIR_HFLIP, Fn.PAIR_VFLIP, Fn.PAIR_SWAP, Fn.PAIR_FLAG_MASK) == (1, 2, 4, 7)

@@ -218,12 +218,12 @@ def test_bytes_needed_by_hand_and_the_budget_refusal():
 # ------------------------------------------------------------------------------------------------------------------------ ABI
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_abi_header_bindings_exports(fmt):
-    declared = L.declared_pair_batch_symbols()
+    declared = L.declared_symbols("hesic_pair_batch.h")
     assert declared == ["hesic_pair_batch_gather"]
     assert set(declared) == set(L._PAIR_BATCH_SIGS)
     assert not set(declared) & set(L.declared_symbols())                # a header of its own: include/hesic_hip.h does not list it
-    assert "hesic_pair_batch.h" not in open(L.HEADER_PATH).read()
-    assert "#define HESIC_ABI_VERSION 2" in open(L.HEADER_PATH).read() and L.ABI_VERSION == 2
+    assert "hesic_pair_batch.h" not in open(L.header_path("hesic_hip.h")).read()
+    assert "#define HESIC_ABI_VERSION 2" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 2
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in declared:
         assert f" T {s}\n" in exported, s
@@ -234,7 +234,7 @@ def test_item_struct_is_48_bytes_in_every_form():
     assert np.dtype(Fn.PAIR_ITEM_DTYPE).itemsize == 48
     assert [n for n, _ in L.PairItem._fields_] == [n for n, _ in Fn.PAIR_ITEM_DTYPE]
     assert [getattr(L.PairItem, n).offset for n, _ in L.PairItem._fields_] == [np.dtype(Fn.PAIR_ITEM_DTYPE).fields[n][1] for n, _ in Fn.PAIR_ITEM_DTYPE]
-    text = open(L.PAIR_BATCH_HEADER_PATH).read()
+    text = open(L.header_path("hesic_pair_batch.h")).read()
     for n, _ in Fn.PAIR_ITEM_DTYPE:
         assert n in text
 

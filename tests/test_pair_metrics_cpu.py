@@ -168,12 +168,12 @@ def test_summarise_reproduces_average_meter_over_batch_one_updates():
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_abi_header_bindings_exports(fmt):
     L = _lib()
-    declared = L.declared_pair_metrics_symbols()
+    declared = L.declared_symbols("hesic_pair_metrics.h")
     assert declared == ["hesic_pair_metrics", "hesic_pair_metrics_ws_bytes"]
     assert set(declared) == set(L._PAIR_METRICS_SIGS)
     assert not set(declared) & set(L.declared_symbols())                # a header of its own: include/hesic_hip.h does not list it
-    assert "hesic_pair_metrics.h" not in open(L.HEADER_PATH).read()
-    assert "#define HESIC_PAIR_METRICS_MAX_LIK 8" in open(L.PAIR_METRICS_HEADER_PATH).read() and L.PAIR_METRICS_MAX_LIK == 8
+    assert "hesic_pair_metrics.h" not in open(L.header_path("hesic_hip.h")).read()
+    assert "#define HESIC_PAIR_METRICS_MAX_LIK 8" in open(L.header_path("hesic_pair_metrics.h")).read() and L.PAIR_METRICS_MAX_LIK == 8
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in declared:
         assert f" T {s}\n" in exported, s

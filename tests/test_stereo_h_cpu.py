@@ -153,7 +153,7 @@ def test_stereo_h_abi(fmt):
     if not os.path.exists(L.LIB_PATH):
         import __graft_entry__ as ge
         ge.build()
-    declared = L.declared_stereo_h_symbols()
+    declared = L.declared_symbols("hesic_stereo_h.h")
     assert set(declared) == set(L._STEREO_H_SIGS) and len(declared) >= 7
     assert not set(declared) & set(L.declared_symbols())
     path = L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH

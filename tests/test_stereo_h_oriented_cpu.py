@@ -99,7 +99,7 @@ def test_oriented_abi(fmt):
         import __graft_entry__ as ge
         ge.build()
     new = ("hesic_stereo_h_orient", "hesic_stereo_h_describe_ex", "hesic_stereo_h_match_ex")
-    declared = L.declared_stereo_h_symbols()
+    declared = L.declared_symbols("hesic_stereo_h.h")
     assert all(s in declared and s in L._STEREO_H_SIGS for s in new)
     assert not set(new) & set(L.declared_symbols())
     path = L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH

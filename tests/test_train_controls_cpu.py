@@ -21,10 +21,10 @@ def _lib():
 # ------------------------------------------------------------------------------------------------ header, table, exports, argument checks
 def test_header_declares_what_the_table_binds():
     L = _lib()
-    declared = L.declared_train_ctl_symbols()
+    declared = L.declared_symbols("hesic_train_ctl.h")
     assert declared == ["hesic_adam_step_ctl", "hesic_grad_norm_ctl"] and set(declared) == set(L._TRAIN_CTL_SIGS)
     assert not set(declared) & set(L.declared_symbols())                # a header of its own: include/hesic_hip.h does not list them
-    text = open(L.TRAIN_CTL_HEADER_PATH).read()
+    text = open(L.header_path("hesic_train_ctl.h")).read()
     for name, value in (("LR", L.CTL_LR), ("MAX_NORM", L.CTL_MAX_NORM), ("SKIP_NONFINITE", L.CTL_SKIP_NONFINITE), ("GRAD_NORM", L.CTL_GRAD_NORM),
                         ("CLIP_COEF", L.CTL_CLIP_COEF), ("APPLIED", L.CTL_APPLIED), ("SKIPPED", L.CTL_SKIPPED), ("FLOATS", L.CTL_FLOATS)):
         assert f"#define HESIC_TRAIN_CTL_{name} {value} " in text, name
