@@ -295,6 +295,13 @@ _HOMOGRAPHY_NET_SIGS = {
     "hesic_bias_grad": ([_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], _i32),
     "hesic_narrow_in_wgrad": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
 }
+# include/hesic_dropout_state.h: the same dropout masks with (seed, step) in device memory (functional.dropout_state_take,
+# homography.Net.dropout_on_device, train.GraphedHomographyTrainer), in both libraries
+_DROPOUT_STATE_SIGS = {
+    "hesic_dropout_state_take": ([_vp, _vp, _vp], _i32),
+    "hesic_flatten_dropout_forward_state": ([_vp, _vp, _i32, _i32, _i32, _u32, _f32, _vp, _u32, _i32, _vp], _i32),
+    "hesic_flatten_dropout_backward_state": ([_vp, _vp, _i32, _i32, _i32, _u32, _f32, _vp, _u32, _i32, _vp], _i32),
+}
 LINEAR_MAX_ROWS = 64            # HESIC_LINEAR_MAX_ROWS
 DET_MAX_BLOCKS = 256            # HESIC_DET_MAX_BLOCKS
 
@@ -391,6 +398,7 @@ HEADERS = {
     "hesic_train_ctl.h": _TRAIN_CTL_SIGS,
     "hesic_homography_train.h": _HOMOGRAPHY_TRAIN_SIGS,
     "hesic_homography_net.h": _HOMOGRAPHY_NET_SIGS,
+    "hesic_dropout_state.h": _DROPOUT_STATE_SIGS,
     "hesic_homography_prep.h": _HOMOGRAPHY_PREP_SIGS,
     "hesic_homonet_items.h": _HOMONET_ITEMS_SIGS,
     "hesic_homonet_synth.h": _HOMONET_SYNTH_SIGS,

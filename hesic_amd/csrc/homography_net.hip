@@ -15,6 +15,7 @@
 // No atomics; every sum has a fixed order.
 #include "common.h"
 #include "../../include/hesic_homography_net.h"
+#include "../../include/hesic_dropout_state.h"
 
 namespace {
 
@@ -84,6 +85,25 @@ __global__ void maxpool2_bwd_kernel(const T* __restrict__ x, const T* __restrict
 // ------------------------------------------------------------------------------------------------------------ flatten + dropout
 struct DropArgs { uint32_t thr; float scale; uint32_t k0, k1, step, site; };
 
+// Where a launch finds (k0, k1, step): in its kernel arguments, or in the 16 bytes {seed lo, seed hi, step, reserved} that
+// hesic_dropout_state_take left in device memory (wave-uniform: every thread loads the three words once).
+struct KeysByValue {
+    __device__ __forceinline__ DropArgs resolve(const DropArgs& a) const { return a; }
+};
+struct KeysFromState {
+    const uint32_t* __restrict__ taken;
+    __device__ __forceinline__ DropArgs resolve(const DropArgs& a) const { return DropArgs{a.thr, a.scale, taken[0], taken[1], taken[2], a.site}; }
+};
+
+// state -> taken, then state.step += 1 (mod 2^32): what Net._forward_train does to its host counter, as one lane's work
+__global__ void dropout_state_take_kernel(uint32_t* __restrict__ state, uint32_t* __restrict__ taken) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint32_t lo = state[0], hi = state[1], step = state[2], rsv = state[3];
+        taken[0] = lo; taken[1] = hi; taken[2] = step; taken[3] = rsv;
+        state[2] = step + 1u;
+    }
+}
+
 __device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -105,9 +125,11 @@ __device__ __forceinline__ f32x4 drop4(f32x4 v, int64_t e0, const DropArgs& a) {
 
 // HW % 4 == 0 and C % 4 == 0: a 32-pixel x 32-channel tile goes through LDS, so that the NHWC side is accessed in runs of four channels
 // and the flat side in runs of four pixels.  FWD: src = NHWC map, dst = flat rows; else src = flat gradient, dst = NHWC gradient.
-template <typename T, bool FWD>
-__global__ __launch_bounds__(256) void flatten_dropout_tile_kernel(const T* __restrict__ src, T* __restrict__ dst, int HW, int C, DropArgs a) {
+template <typename T, bool FWD, typename Keys>
+__global__ __launch_bounds__(256) void flatten_dropout_tile_kernel(const T* __restrict__ src, T* __restrict__ dst, int HW, int C, DropArgs a0,
+                                                                   Keys keys) {
     __shared__ float s[32][33];                     // [channel][pixel]
+    const DropArgs a = keys.resolve(a0);
     const int b = blockIdx.z, p0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int rl = threadIdx.x >> 3, g4 = (threadIdx.x & 7) * 4;
     const int64_t F = (int64_t)C * HW;
@@ -134,8 +156,9 @@ __global__ __launch_bounds__(256) void flatten_dropout_tile_kernel(const T* __re
 }
 
 // any HW (HW = 1: the second dropout site, where both orders coincide): one thread per four flat elements, the NHWC side element by element
-template <typename T, bool FWD>
-__global__ void flatten_dropout_flat_kernel(const T* __restrict__ src, T* __restrict__ dst, int B, int HW, int C, DropArgs a) {
+template <typename T, bool FWD, typename Keys>
+__global__ void flatten_dropout_flat_kernel(const T* __restrict__ src, T* __restrict__ dst, int B, int HW, int C, DropArgs a0, Keys keys) {
+    const DropArgs a = keys.resolve(a0);
     const int64_t F = (int64_t)C * HW, total = (int64_t)B * F / 4;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t e0 = 4 * i, b = e0 / F, j = e0 % F;
@@ -152,33 +175,47 @@ __global__ void flatten_dropout_flat_kernel(const T* __restrict__ src, T* __rest
     }
 }
 
-template <typename T, bool FWD>
-void launch_flatten_dropout(const void* src, void* dst, int B, int HW, int C, const DropArgs& a, hipStream_t st) {
+template <typename T, bool FWD, typename Keys>
+void launch_flatten_dropout(const void* src, void* dst, int B, int HW, int C, const DropArgs& a, Keys keys, hipStream_t st) {
     if (HW % 4 == 0)
-        hipLaunchKernelGGL((flatten_dropout_tile_kernel<T, FWD>), dim3((HW + 31) / 32, (C + 31) / 32, B), dim3(256), 0, st, (const T*)src,
-                           (T*)dst, HW, C, a);
+        hipLaunchKernelGGL((flatten_dropout_tile_kernel<T, FWD, Keys>), dim3((HW + 31) / 32, (C + 31) / 32, B), dim3(256), 0, st, (const T*)src,
+                           (T*)dst, HW, C, a, keys);
     else
-        hipLaunchKernelGGL((flatten_dropout_flat_kernel<T, FWD>), dim3(grid_for((int64_t)B * C * HW / 4, 256)), dim3(256), 0, st,
-                           (const T*)src, (T*)dst, B, HW, C, a);
+        hipLaunchKernelGGL((flatten_dropout_flat_kernel<T, FWD, Keys>), dim3(grid_for((int64_t)B * C * HW / 4, 256)), dim3(256), 0, st,
+                           (const T*)src, (T*)dst, B, HW, C, a, keys);
 }
 
-int flatten_dropout(const char* name, bool fwd, const void* src, void* dst, int B, int HW, int C, uint32_t thr, float scale, uint64_t seed,
-                    uint32_t step, uint32_t site, int dtype, void* stream) {
+// `a` holds thr, scale and site, and with KeysByValue the keys and the step too
+template <typename Keys>
+int flatten_dropout(const char* name, bool fwd, const void* src, void* dst, int B, int HW, int C, const DropArgs& a, Keys keys, int dtype,
+                    void* stream) {
     HESIC_CHECK_ARG(src && dst, "%s: null pointer", name);
     HESIC_CHECK_ARG(B > 0 && B <= 65535 && HW > 0 && C > 0, "%s: bad sizes B=%d HW=%d C=%d", name, B, HW, C);
     HESIC_CHECK_ARG(dtype == HESIC_H16 || dtype == HESIC_F32, "%s: bad dtype", name);
     HESIC_CHECK_ARG(((int64_t)C * HW) % 4 == 0, "%s: F = C * HW = %lld must be a multiple of 4", name, (long long)C * HW);
     HESIC_CHECK_ARG(HW == 1 || C % 4 == 0, "%s: C=%d must be a multiple of 4", name, C);
-    const DropArgs a{thr, scale, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), step, site};
     const hipStream_t st = (hipStream_t)stream;
     if (dtype == HESIC_H16) {
-        if (fwd) launch_flatten_dropout<h16_t, true>(src, dst, B, HW, C, a, st);
-        else launch_flatten_dropout<h16_t, false>(src, dst, B, HW, C, a, st);
+        if (fwd) launch_flatten_dropout<h16_t, true>(src, dst, B, HW, C, a, keys, st);
+        else launch_flatten_dropout<h16_t, false>(src, dst, B, HW, C, a, keys, st);
     } else {
-        if (fwd) launch_flatten_dropout<float, true>(src, dst, B, HW, C, a, st);
-        else launch_flatten_dropout<float, false>(src, dst, B, HW, C, a, st);
+        if (fwd) launch_flatten_dropout<float, true>(src, dst, B, HW, C, a, keys, st);
+        else launch_flatten_dropout<float, false>(src, dst, B, HW, C, a, keys, st);
     }
     HESIC_LAUNCH_RETURN(name);
+}
+
+int flatten_dropout_value(const char* name, bool fwd, const void* src, void* dst, int B, int HW, int C, uint32_t thr, float scale, uint64_t seed,
+                          uint32_t step, uint32_t site, int dtype, void* stream) {
+    const DropArgs a{thr, scale, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), step, site};
+    return flatten_dropout(name, fwd, src, dst, B, HW, C, a, KeysByValue{}, dtype, stream);
+}
+
+int flatten_dropout_state(const char* name, bool fwd, const void* src, void* dst, int B, int HW, int C, uint32_t thr, float scale,
+                          const void* taken, uint32_t site, int dtype, void* stream) {
+    HESIC_CHECK_ARG(taken, "%s: null taken (the 16 bytes hesic_dropout_state_take wrote)", name);
+    const DropArgs a{thr, scale, 0u, 0u, 0u, site};
+    return flatten_dropout(name, fwd, src, dst, B, HW, C, a, KeysFromState{(const uint32_t*)taken}, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------ small-batch Linear
@@ -542,12 +579,29 @@ extern "C" int hesic_maxpool2_backward(const void* x, const void* gy, void* gx, 
 
 extern "C" int hesic_flatten_dropout_forward(const void* x, void* y, int B, int HW, int C, uint32_t thr, float scale, uint64_t seed,
                                              uint32_t step, uint32_t site, int dtype, void* stream) {
-    return flatten_dropout("flatten_dropout_forward", true, x, y, B, HW, C, thr, scale, seed, step, site, dtype, stream);
+    return flatten_dropout_value("flatten_dropout_forward", true, x, y, B, HW, C, thr, scale, seed, step, site, dtype, stream);
 }
 
 extern "C" int hesic_flatten_dropout_backward(const void* gy, void* gx, int B, int HW, int C, uint32_t thr, float scale, uint64_t seed,
                                               uint32_t step, uint32_t site, int dtype, void* stream) {
-    return flatten_dropout("flatten_dropout_backward", false, gy, gx, B, HW, C, thr, scale, seed, step, site, dtype, stream);
+    return flatten_dropout_value("flatten_dropout_backward", false, gy, gx, B, HW, C, thr, scale, seed, step, site, dtype, stream);
+}
+
+extern "C" int hesic_dropout_state_take(void* state, void* taken, void* stream) {
+    HESIC_CHECK_ARG(state && taken, "dropout_state_take: null pointer");
+    HESIC_CHECK_ARG(state != taken, "dropout_state_take: state and taken are one buffer");
+    hipLaunchKernelGGL(dropout_state_take_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t*)state, (uint32_t*)taken);
+    HESIC_LAUNCH_RETURN("dropout_state_take");
+}
+
+extern "C" int hesic_flatten_dropout_forward_state(const void* x, void* y, int B, int HW, int C, uint32_t thr, float scale, const void* taken,
+                                                   uint32_t site, int dtype, void* stream) {
+    return flatten_dropout_state("flatten_dropout_forward_state", true, x, y, B, HW, C, thr, scale, taken, site, dtype, stream);
+}
+
+extern "C" int hesic_flatten_dropout_backward_state(const void* gy, void* gx, int B, int HW, int C, uint32_t thr, float scale, const void* taken,
+                                                    uint32_t site, int dtype, void* stream) {
+    return flatten_dropout_state("flatten_dropout_backward_state", false, gy, gx, B, HW, C, thr, scale, taken, site, dtype, stream);
 }
 
 extern "C" size_t hesic_linear_forward_ws_bytes(int B, int In, int Out) {

@@ -357,10 +357,23 @@ def repack_all():
         _pack_table = (sig, table, len(ents), blk)
     _, table, n, blk = _pack_table
     L.call("hesic_pack_conv_weights_batched", L.ptr(table), n, blk, L.stream())
+    _mark_packs_current(ents)
+    return n
+
+
+def _mark_packs_current(ents):
     for e in ents:
         w = e["weight"]()
         e["owner"]._cache[e["key"]] = ((w.data_ptr(), w._version, None if e["mask"] is None else e["mask"]._version, _cache_epoch), e["wp"])
-    return n
+
+
+def packs_replayed(params):
+    """After a graph replay whose captured ``repack_all()`` refreshed them on the device: mark the registered packs of ``params`` current,
+    the host half of ``repack_all()`` that a replay does not run (call it after bumping the parameters' version counters).  The packers
+    then keep handing out the buffers the graph reads and writes by address -- an eager step or an eval forward between two replays
+    allocates no replacement for them."""
+    mine = {id(p) for p in params}
+    _mark_packs_current([e for e in _pack_registry if e["weight"]() is not None and id(e["weight"]()) in mine])
 
 
 class PackedWeight:
@@ -2276,9 +2289,47 @@ def dropout_args(p, seed=0, step=0, site=0):
     return thr, scale, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, int(site) & 0xFFFFFFFF
 
 
+def dropout_state_args(p, taken, site=0):
+    """The arguments of ``hesic_flatten_dropout_*_state`` for drop probability ``p``: ``dropout_args``' (thr, scale, ., ., site) with
+    ``(seed, step)`` replaced by ``taken``, the 16-byte device tensor ``dropout_state_take`` wrote."""
+    if not (isinstance(taken, torch.Tensor) and taken.is_cuda and taken.is_contiguous() and taken.numel() * taken.element_size() == 16):
+        raise ValueError("dropout: taken must be a contiguous 16-byte device tensor (what dropout_state_take returns)")
+    thr, scale, _, _, site = dropout_args(p, 0, 0, site)
+    return thr, scale, taken, site
+
+
+def dropout_state(seed, step, device):
+    """The dropout state in device memory: int32 words {seed lo, seed hi, step, reserved = 0} (``include/hesic_dropout_state.h``)."""
+    return torch.from_numpy(_dropout_words(seed, step)).to(device)
+
+
+def _dropout_words(seed, step):
+    import numpy as np
+    seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF
+    return np.array([seed & 0xFFFFFFFF, seed >> 32, step, 0], dtype=np.uint32).view(np.int32)
+
+
+def dropout_state_take(state):
+    """One launch: a fresh 16-byte tensor with the four words of ``state``, whose step is then incremented on the device."""
+    L.require_cuda(state)
+    taken = torch.empty_like(state)
+    L.call("hesic_dropout_state_take", L.ptr(state), L.ptr(taken), L.stream())
+    return taken
+
+
 class _FlattenDropoutFn(torch.autograd.Function):
     """``x.reshape(B, -1)`` of the reference (NCHW flatten order) of a channels_last map -- or a (B, F) matrix as it is -- with inverted
-    dropout on the way; the mask is a Philox4x32-10 stream of (seed, step, site, logical index) that the backward regenerates."""
+    dropout on the way; the mask is a Philox4x32-10 stream of (seed, step, site, logical index) that the backward regenerates.  ``cfg`` is
+    ``dropout_args``' by-value tuple or ``dropout_state_args``' (the ``_state`` entries: seed and step read from ``taken`` on the device,
+    by the backward too)."""
+
+    @staticmethod
+    def _call(which, src, dst, B, HW, Cc, cfg, dt):
+        if len(cfg) == 4:
+            thr, scale, taken, site = cfg
+            L.call(f"hesic_flatten_dropout_{which}_state", L.ptr(src), L.ptr(dst), B, HW, Cc, thr, scale, L.ptr(taken), site, dt, L.stream())
+        else:
+            L.call(f"hesic_flatten_dropout_{which}", L.ptr(src), L.ptr(dst), B, HW, Cc, *cfg, dt, L.stream())
 
     @staticmethod
     def forward(ctx, x, cfg):
@@ -2290,7 +2341,7 @@ class _FlattenDropoutFn(torch.autograd.Function):
             x = x.contiguous()
             (B, Cc), HW = x.shape, 1
         y = torch.empty((B, Cc * HW), dtype=x.dtype, device=x.device)
-        L.call("hesic_flatten_dropout_forward", L.ptr(x), L.ptr(y), B, HW, Cc, *cfg, L.dt(x), L.stream())
+        _FlattenDropoutFn._call("forward", x, y, B, HW, Cc, cfg, L.dt(x))
         ctx.cfg, ctx.shape, ctx.dtype = cfg, tuple(x.shape), x.dtype
         return y
 
@@ -2304,12 +2355,12 @@ class _FlattenDropoutFn(torch.autograd.Function):
         else:
             gx = torch.empty(shape, dtype=ctx.dtype, device=gy.device)
             (B, Cc), HW = shape, 1
-        L.call("hesic_flatten_dropout_backward", L.ptr(gy), L.ptr(gx), B, HW, Cc, *ctx.cfg, L.dt(ctx.dtype), L.stream())
+        _FlattenDropoutFn._call("backward", gy, gx, B, HW, Cc, ctx.cfg, L.dt(ctx.dtype))
         return gx, None
 
 
 def flatten_dropout(x, cfg):
-    """``cfg`` = ``dropout_args(p, seed, step, site)``; p = 0 is the plain flatten."""
+    """``cfg`` = ``dropout_args(p, seed, step, site)`` or ``dropout_state_args(p, taken, site)``; p = 0 is the plain flatten."""
     return _apply(_FlattenDropoutFn, x, cfg)
 
 

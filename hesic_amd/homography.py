@@ -94,6 +94,7 @@ class Net(nn.Module):
         self._fc_pack = [Fn.PackedWeight(), Fn.PackedWeight(), Fn.PackedWeight(), Fn.PackedWeight()]      # inference fc.2 / fc.5; the > 64-row training route
         self._fc1_nhwc = None
         self._drop_seed, self._drop_step = 0, 0
+        self._drop_dev = None                       # dropout_on_device: int32 {seed lo, seed hi, step, 0} in device memory
 
     def _fc1_weight(self):
         """fc.2.weight with its columns moved from NCHW-flatten (c, y, x) to NHWC-flatten (y, x, c) order; cached."""
@@ -106,12 +107,34 @@ class Net(nn.Module):
         return self._fc1_nhwc[1]
 
     def set_dropout_state(self, seed, step=0):
-        """Seed and step counter of the dropout masks (both sites of ``fc``)."""
+        """Seed and step counter of the dropout masks (both sites of ``fc``).  With ``dropout_on_device`` the device copy is rewritten too
+        (device fills: not while a stream is capturing)."""
         self._drop_seed, self._drop_step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF
+        if self._drop_dev is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Net.set_dropout_state: the device copy of the dropout state cannot be rewritten while a stream is capturing")
+            for i, word in enumerate(Fn._dropout_words(self._drop_seed, self._drop_step).tolist()):
+                self._drop_dev[i:i + 1].fill_(word)      # device fills, as FlatAdam.sync_lr: no host buffer, no synchronisation
 
     def dropout_state(self):
-        """(seed, step): ``step`` is what the NEXT train-mode forward uses."""
+        """(seed, step): ``step`` is what the NEXT train-mode forward uses.  With ``dropout_on_device`` it is read back from the device
+        (synchronises)."""
+        if self._drop_dev is not None:
+            lo, hi, step, _ = (int(v) & 0xFFFFFFFF for v in self._drop_dev.tolist())
+            self._drop_seed, self._drop_step = lo | (hi << 32), step
         return self._drop_seed, self._drop_step
+
+    def dropout_on_device(self, flag=True):
+        """Keep the dropout ``(seed, step)`` in sixteen bytes of device memory (``hesic_dropout_state_take`` / ``hesic_flatten_dropout_*_state``):
+        a train-mode forward then takes the state in one tiny launch -- both sites use what it took, the step is incremented on the device --
+        so a forward recorded into a HIP graph draws a new mask at every replay (``train.GraphedHomographyTrainer``).  The masks are those
+        of the by-value route for the same ``(seed, step)``.  Off (the default), the forward issues exactly the by-value launches."""
+        if flag and self._drop_dev is None:
+            self._drop_dev = Fn.dropout_state(self._drop_seed, self._drop_step, self.fc[2].weight.device)
+        elif not flag and self._drop_dev is not None:
+            self.dropout_state()                    # the host copy takes over where the device copy stands
+            self._drop_dev = None
+        return self
 
     def forward(self, a, b):
         if self.training or torch.is_grad_enabled():
@@ -143,6 +166,10 @@ class Net(nn.Module):
         seed, step = self._drop_seed, self._drop_step
         cfgs = [Fn.dropout_args(self.fc[i].p if self.training else 0.0, seed, step, site) for site, i in enumerate((1, 4))]
         L.require_cuda(a, b)
+        on_device = self.training and self._drop_dev is not None       # eval mode with grad: p = 0, no state needed and none taken
+        if on_device:
+            taken = Fn.dropout_state_take(self._drop_dev)        # both sites use what it took; the device step is incremented
+            cfgs = [Fn.dropout_state_args(self.fc[i].p, taken, site) for site, i in enumerate((1, 4))]
         x = torch.cat((a, b), dim=1).to(self.dtype)
         prev = Fn.compute_dtype()
         Fn.set_compute_dtype(self.dtype)
@@ -156,7 +183,7 @@ class Net(nn.Module):
             x = Fn.linear(x, self.fc[5].weight, self.fc[5].bias, packer=self._fc_pack[3])
         finally:
             Fn.set_compute_dtype(prev)
-        if self.training:
+        if self.training and self._drop_dev is None:
             self._drop_step = (step + 1) & 0xFFFFFFFF
         return x.reshape(-1, 4, 2).float()
 

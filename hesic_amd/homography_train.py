@@ -7,7 +7,7 @@
     --crop H W            one random crop offset shared by both views (default: the whole image)
     --seed 0  --resume PATH|none  --out DIR  --clip-max-norm X  --skip-nonfinite
     --cache host|device|stream  --cache-gb G  -n/--num-workers 3  --mix-sizes
-    --supervision photometric|synthetic
+    --supervision photometric|synthetic  --graphed
 
 ``--cache host`` (the default): the host reads, decodes and crops every batch of every epoch on one thread; a batch is stacked as uint8
 and uploaded as bytes, and ``HomographyTrainer.step_pairs`` turns it into the net's inputs in one launch (resize, normalise, grey, random
@@ -40,6 +40,13 @@ pixels of the ``picsize`` frame), ``"identity_corner_error"`` (the same for a ne
 checkpoints gain ``"supervision"``.  ``--resume`` across supervisions is allowed -- synthetic pre-training, then photometric fine-tuning, is
 the intended use --; the two losses are not comparable, so the lowest validation loss so far then starts again at +inf and the first
 epoch's checkpoint becomes the best one.
+
+``--graphed`` (``--cache device|stream`` only) trains with ``train.GraphedHomographyTrainer``: after three eager steps the step of the
+run's batch shape is one HIP-graph launch, the dropout state lives on the device, and the batch's one prep launch writes straight into the
+graph's static inputs (``out=``).  An epoch's ragged last batch -- and every other shape -- runs eagerly through the same kernels; validation
+is eager.  Records, checkpoints and ``--resume`` are bit for bit those of a run without the flag, and a resume may switch it on or off.
+The device is busy for all but a few percent of this step, so the gain is small: 4.82 -> 4.73 ms per step at batch 16, nothing measurable
+at batch 64 (profiles/homography_graphed_bench.json).
 
 Determinism: the shuffle, the crop offsets and the windows of epoch ``e`` come from a ``random.Random`` keyed by ``(seed, e)``, the validation
 draws from one keyed by the seed alone (every epoch is judged on the same windows).  ``--epochs`` is the TOTAL number of epochs, as in QHtrain:
@@ -131,38 +138,63 @@ def draw_batch(items, crop, rng, picsize, patchsize, rho):
     return origins, sizes, homography.window_origins(len(items), None, picsize, patchsize, rho, rng)
 
 
-def cached_inputs(cache, items, a, rng):
+def cached_inputs(cache, items, a, rng, out=None):
     """``(grey1, patch1, patch2, corners)`` of the batch ``items`` from the split's ``DevicePairCache``, one launch: what ``step_pairs`` /
-    ``evaluate_pairs`` prepare from ``load_batch``'s upload."""
+    ``evaluate_pairs`` prepare from ``load_batch``'s upload.  ``out``: ``homonet_batch``'s five tensors to write into."""
     origins, sizes, windows = draw_batch(items, a.crop, rng, a.picsize, a.patchsize, a.rho)
     grey1, _, patch1, patch2, corners = cache.homonet_batch([cache.index_of[lf] for lf, _, _ in items], origins, sizes, windows, a.picsize,
-                                                            a.patchsize)
+                                                            a.patchsize, out=out)
     return grey1, patch1, patch2, corners
 
 
-def synthetic_inputs(cache, items, a, rng, srng):
+def synthetic_inputs(cache, items, a, rng, srng, out=None):
     """``(patch_a, patch_b, delta)`` of a synthetic-warp batch on the left views of ``items``: ``draw_batch`` on ``rng`` as ``cached_inputs``
-    does, the corner offsets from ``srng``, one call of ``DevicePairCache.homonet_synth_batch``."""
+    does, the corner offsets from ``srng``, one call of ``DevicePairCache.homonet_synth_batch`` (``out``: its seven tensors to write into)."""
     from . import homography
     origins, sizes, windows = draw_batch(items, a.crop, rng, a.picsize, a.patchsize, a.rho)
     deltas = homography.draw_deltas(len(items), windows, a.patchsize, a.rho, srng)
     _, patch_a, _, delta, _, _, patch_b = cache.homonet_synth_batch([cache.index_of[lf] for lf, _, _ in items], origins, sizes, windows, deltas,
-                                                                    a.picsize, a.patchsize)
+                                                                    a.picsize, a.patchsize, out=out)
     return patch_a, patch_b, delta
 
 
-def train_epoch(trainer, pairs, a, rng, device, cache=None, srng=None):
+def graph_outputs(trainer, kind, batch, picsize, spare):
+    """The ``out=`` tuple that makes a batch's prep launch write into the static inputs of ``trainer``'s ``kind`` slot, or ``None`` -- an
+    eager trainer, a slot not staged yet, a batch of another size (it runs eagerly).  The outputs the step does not read go to tensors kept
+    in ``spare``."""
+    static = trainer.static_inputs(kind) if hasattr(trainer, "static_inputs") else None
+    if static is None or static[0].shape[0] != batch:
+        return None
+    if kind == "step":
+        img_a, patch_a, patch_b, corners = static
+        if kind not in spare:
+            spare[kind] = torch.empty_like(img_a)
+        return img_a, spare[kind], patch_a, patch_b, corners
+    patch_a, patch_b, delta = static
+    if kind not in spare:
+        S, dev = picsize, patch_a.device
+        spare[kind] = (torch.empty((batch, 1, S, S), device=dev), torch.empty((batch, 4, 2), device=dev),
+                       torch.empty((batch, 9), dtype=torch.float64, device=dev), torch.empty((batch, 1, S, S), device=dev))
+    grey_a, corners, h, grey_b = spare[kind]
+    return grey_a, patch_a, corners, delta, h, grey_b, patch_b
+
+
+def train_epoch(trainer, pairs, a, rng, device, cache=None, srng=None, spare=None):
     """One pass over ``pairs`` (from ``cache`` when given, else read on the host); returns (mean training loss, steps, seconds).  The losses
-    stay on the device until the end.  ``srng``: the deltas' stream under ``--supervision synthetic``, which makes every step a supervised one."""
+    stay on the device until the end.  ``srng``: the deltas' stream under ``--supervision synthetic``, which makes every step a supervised one.
+    ``spare``: a dict that lives as long as a graphed ``trainer`` (``graph_outputs``)."""
     total, n, t0 = torch.zeros((), device=device), 0, time.time()
+    spare = {} if spare is None else spare
     for items in batches(pairs, a.batch_size, a.crop, rng, True, cache is not None and a.mix_sizes):
         if srng is not None:
-            total += trainer.step_supervised(*synthetic_inputs(cache, items, a, rng, srng))["loss"]
+            out = graph_outputs(trainer, "supervised", len(items), a.picsize, spare)
+            total += trainer.step_supervised(*synthetic_inputs(cache, items, a, rng, srng, out))["loss"]
         elif cache is None:
             x1, x2 = load_batch(items, a.crop, rng, device)
             total += trainer.step_pairs(x1, x2, None, a.picsize, a.rho, rng)["loss"]
         else:
-            total += trainer.step(*cached_inputs(cache, items, a, rng))["loss"]
+            out = graph_outputs(trainer, "step", len(items), a.picsize, spare)
+            total += trainer.step(*cached_inputs(cache, items, a, rng, out))["loss"]
         n += 1
     return float(total) / max(n, 1), n, time.time() - t0
 
@@ -240,6 +272,10 @@ def parser():
     p.add_argument("--supervision", choices=("photometric", "synthetic"), default="photometric",
                    help="photometric: the loss on the real pairs; synthetic: known random warps of the left views, MSE on the corner deltas "
                         "(--cache device|stream)")
+    p.add_argument("--graphed", action="store_true",
+                   help="record the training step into a HIP graph and replay it (--cache device|stream); the same bits as without the flag. "
+                        "Measured at batch 16: about 2 %% faster per step on the folder loop (4 %% on the step alone); at batch 64, and under "
+                        "--supervision synthetic, not faster than the eager step by more than its own run-to-run spread")
     return p
 
 
@@ -260,6 +296,8 @@ def main(argv=None, log=print):
         p.error("--mix-sizes needs --cache device or --cache stream (the host route uploads a batch as one tensor of one size)")
     if a.supervision == "synthetic" and a.cache == "host":
         p.error("--supervision synthetic needs --cache device or --cache stream (the warps are made from the stored bytes on the device)")
+    if a.graphed and a.cache == "host":
+        p.error("--graphed needs --cache device or --cache stream (the host route's step_pairs draws its windows between the launches)")
     if a.num_workers < 1 or (a.cache_gb is not None and a.cache_gb <= 0):
         p.error("--num-workers and --cache-gb must be positive")
     if not torch.cuda.is_available():
@@ -273,7 +311,8 @@ def main(argv=None, log=print):
     if resume is None:
         torch.manual_seed(seed)                     # the constructor's own initialisation, reproducibly
     net = homography.Net(patch_size=a.patchsize).to(device)
-    trainer = train.HomographyTrainer(net, lr=a.learning_rate, seed=seed, clip_max_norm=a.clip_max_norm, skip_nonfinite=a.skip_nonfinite)
+    trainer = (train.GraphedHomographyTrainer if a.graphed else train.HomographyTrainer)(
+        net, lr=a.learning_rate, seed=seed, clip_max_norm=a.clip_max_norm, skip_nonfinite=a.skip_nonfinite)
     out = Path(a.out)
     out.mkdir(parents=True, exist_ok=True)
     last, best = out / "checkpoint.pth.tar", out / "checkpoint_best_loss.pth.tar"
@@ -288,10 +327,10 @@ def main(argv=None, log=print):
     if a.cache != "host" and first_epoch < a.epochs:
         tcache = build_cache(a.root, "train", train_pairs, a)
         vcache = tcache if a.valid_split == "train" else build_cache(a.root, a.valid_split, valid_pairs, a)
-    history, synthetic = [], a.supervision == "synthetic"
+    history, synthetic, spare = [], a.supervision == "synthetic", {}
     for epoch in range(first_epoch, a.epochs):
         train_loss, steps, secs = train_epoch(trainer, train_pairs, a, random.Random(f"{seed}/{epoch}"), device, tcache,
-                                              random.Random(f"{seed}/{epoch}/synth") if synthetic else None)
+                                              random.Random(f"{seed}/{epoch}/synth") if synthetic else None, spare)
         if synthetic:
             valid_loss, corner_err, identity_err = validate_synthetic(trainer, valid_pairs, a, random.Random(f"{seed}/valid"),
                                                                       random.Random(f"{seed}/valid/synth"), device, vcache)

@@ -557,14 +557,36 @@ class _GraphedStep:
 
     _ADAM = "Adam launch"       # how ``set_lr``'s refusal names the captured optimiser work
 
+    class _Slot:
+        """One captured step: its call count, graph, static inputs and static outputs."""
+        __slots__ = ("calls", "graph", "inputs", "out")
+
+        def __init__(self):
+            self.calls, self.graph, self.inputs, self.out = 0, None, None, None
+
     def _init_graph(self, warmup, why):
         if int(warmup) < 1:
             raise ValueError(f"{type(self).__name__}: warmup >= 1 ({why})")
-        self.warmup, self.calls, self.graph = int(warmup), 0, None
-        self._in = self._out = None
+        self.warmup = int(warmup)
+        # one slot per key; ``calls`` / ``graph`` / ``_in`` / ``_out`` are those of the slot in use (a trainer with one kind of step never
+        # leaves the ``None`` slot)
+        self._slots = {None: _GraphedStep._Slot()}
+        self._slot = self._slots[None]
+
+    def _use_slot(self, key):
+        slot = self._slots.get(key)
+        if slot is None:
+            slot = self._slots[key] = _GraphedStep._Slot()
+        self._slot = slot
+        return slot
+
+    calls = property(lambda self: self._slot.calls, lambda self, v: setattr(self._slot, "calls", v))
+    graph = property(lambda self: self._slot.graph, lambda self, v: setattr(self._slot, "graph", v))
+    _in = property(lambda self: self._slot.inputs, lambda self, v: setattr(self._slot, "inputs", v))
+    _out = property(lambda self: self._slot.out, lambda self, v: setattr(self._slot, "out", v))
 
     def set_lr(self, *rates, **kw):
-        if self.graph is not None and not self.controls:
+        if any(slot.graph is not None for slot in self._slots.values()) and not self.controls:
             raise RuntimeError(f"{type(self).__name__}.set_lr: the captured step holds its learning rate by value in the kernel arguments of "
                                f"its {self._ADAM}, a replay cannot see a new one -- build the trainer with live_lr=True (the rate is then "
                                "read from device memory by every replay)")
@@ -586,14 +608,17 @@ class _GraphedStep:
     def _captured(self):
         pass
 
-    def _run(self, **kw):
-        """Count the call, then the eager step on the static inputs -- on a side stream (warm-up) or under capture -- or a replay."""
+    def _run(self, eager=None, **kw):
+        """Count the call, then the eager step on the static inputs -- on a side stream (warm-up) or under capture -- or a replay.  ``eager``:
+        the wrapped trainer's step method (default: its ``step``)."""
+        if eager is None:
+            eager = super().step
         self.calls += 1
         if self.graph is None and self.calls <= self.warmup:
             side = torch.cuda.Stream(device=self._in[0].device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                out = super().step(*self._in, **kw)
+                out = eager(*self._in, **kw)
             torch.cuda.current_stream().wait_stream(side)
             return out
         if self.graph is None:
@@ -604,7 +629,7 @@ class _GraphedStep:
             # rules to this thread.
             torch.cuda.synchronize()
             with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self._out = super().step(*self._in, **kw)
+                self._out = eager(*self._in, **kw)
             self._captured()
         self.graph.replay()
         self._replayed()            # a replay runs no Python: the captured Adam moved the parameters without touching their version counters
@@ -682,7 +707,10 @@ class HomographyTrainer:
     (``net.set_dropout_state(seed, 0)``).
 
     The trainer is EAGER: the dropout masks' step counter is a kernel argument passed by value, so a captured HIP graph would replay one
-    mask forever.  ``step`` raises while a stream is capturing."""
+    mask forever.  ``step`` raises while a stream is capturing.  ``GraphedHomographyTrainer`` is the same step with the counter in device
+    memory, recorded into a HIP graph."""
+
+    _CAPTURABLE = False         # GraphedHomographyTrainer: the dropout state lives on the device, the step may be recorded
 
     def __init__(self, net, lr=1e-4, seed=0, clip_max_norm=None, skip_nonfinite=False, live_lr=False):
         clip_max_norm, skip_nonfinite, live_lr = _step_controls("HomographyTrainer", clip_max_norm, skip_nonfinite, live_lr)
@@ -704,10 +732,12 @@ class HomographyTrainer:
 
     def _train_step(self, name, patch_a, patch_b, criterion):
         """zero the flat gradient -> train-mode forward -> ``criterion(delta)`` -> backward -> one Adam launch.  Returns device scalars."""
-        if torch.cuda.is_current_stream_capturing():
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing and not self._CAPTURABLE:
             raise RuntimeError(f"HomographyTrainer.{name} is eager: the dropout step counter is passed to the kernels by value, a captured "
                                "graph would replay one mask forever")
-        self.optimizer.sync_lr()
+        if not capturing:                         # a fill recorded into a graph would hold today's rate
+            self.optimizer.sync_lr()
         self.net.train()
         self.group.zero_grad()
         prev_dtype = Fn.compute_dtype()
@@ -728,7 +758,7 @@ class HomographyTrainer:
             Fn.set_compute_dtype(prev_dtype)
         out = {"loss": loss.detach()}
         if self.controls:
-            out.update(_control_readout(self.optimizer))         # copies: this step never runs under capture
+            out.update(_control_readout(self.optimizer))         # copies, unless GraphedHomographyTrainer is capturing
         return out
 
     def _eval_delta(self, patch_a, patch_b):
@@ -791,6 +821,82 @@ class HomographyTrainer:
         self.net.load_state_dict(sd["state_dict"])
         self.optimizer.load_state_dict(sd["optimizer"])
         self.net.set_dropout_state(*sd["dropout"])
+
+
+class GraphedHomographyTrainer(_GraphedStep, HomographyTrainer):
+    """``HomographyTrainer.step`` and ``step_supervised`` recorded into HIP graphs and replayed, by ``GraphedTrainer``'s protocol
+    (``_GraphedStep``).  What kept the eager trainer out of a graph -- the dropout step counter in the kernel arguments -- lives in device
+    memory here (``net.dropout_on_device()``): the captured forward begins with ``hesic_dropout_state_take``, so every replay draws the mask
+    the eager trainer would draw in that step, bit for bit, and a checkpoint moves between the two trainers in both directions.
+
+    Each KIND of step (``"step"``: ``(img_a, patch_a, patch_b, corners)``; ``"supervised"``: ``(patch_a, patch_b, delta)``) has its own
+    slot: the first ``warmup`` calls of a kind run eagerly on a side stream (real steps), the next one captures, every later one copies the
+    inputs into the slot's static tensors (nothing, when the producer wrote into ``static_inputs(kind)``) and launches the graph.  A kind's
+    graph belongs to the first input shapes that get through their warm-up; a call with other shapes (an epoch's ragged last batch) runs
+    eagerly through the same device-state kernels -- no second capture, no error, the same bits.  The returned dict holds the slot's static
+    device scalars (``loss``, and with controls ``grad_norm``, ``clip_coef``, ``skipped``), overwritten by the next call of that kind.
+
+    After a replay the parameters' version counters are bumped, as the eager Adam does, and the registered training packs -- refreshed on
+    the device by the captured ``repack_all`` -- are marked current: ``evaluate`` and eager steps between replays see the trained weights
+    and keep using the buffers the graphs hold by address.  Without step controls the captured Adam holds its learning rate by value and
+    ``set_lr`` refuses after the first capture.  ``step_pairs`` is not offered here (``NotImplementedError``): its input prep draws
+    windows on the host; prepare the batch (``homography.prepare_inputs`` or a ``DevicePairCache`` with ``out=static_inputs(kind)``) and
+    call ``step``."""
+
+    _CAPTURABLE = True
+    KINDS = ("step", "supervised")
+
+    def __init__(self, net, *args, warmup=3, **kw):
+        super().__init__(net, *args, **kw)
+        self._init_graph(warmup, "the packed-weight registry is created by an eager step")
+        net.dropout_on_device(True)
+        self._kind_key = {}         # kind -> the (kind, input shapes) key of its captured slot
+
+    def graph_slot(self, kind="step"):
+        """The captured slot of ``kind`` (``calls``, ``graph``, ``inputs``, ``out``), or ``None`` before its capture."""
+        if kind not in self.KINDS:
+            raise ValueError(f"GraphedHomographyTrainer: kind is one of {self.KINDS}, got {kind!r}")
+        key = self._kind_key.get(kind)
+        return None if key is None else self._slots[key]
+
+    def static_inputs(self, kind="step"):
+        """The static input tensors of ``kind``'s captured slot (in the order of that step's arguments), or ``None`` before its capture."""
+        slot = self.graph_slot(kind)
+        return None if slot is None else slot.inputs
+
+    def _replayed(self):
+        torch.autograd.graph.increment_version(self.group.params)       # Net._fc1_nhwc, the _fc_pack packers: keyed on the version counters
+        Fn.packs_replayed(self.group.params)
+
+    def _graphed(self, kind, eager, inputs):
+        key = (kind, tuple(tuple(t.shape) for t in inputs))
+        self.optimizer.sync_lr()                  # control path: this call's rate, filled in ahead of the capture / the replay
+        if self._kind_key.get(kind, key) != key:
+            return eager(*inputs)                 # not the shapes of this kind's graph: the eager route, on the same device state
+        slot = self._use_slot(key)
+        self._stage(*inputs)
+        out = self._run(eager=eager)
+        if slot.graph is not None and kind not in self._kind_key:
+            # the first shapes to get through their warm-up own the kind's graph; the other candidates' static tensors are let go
+            self._kind_key[kind] = key
+            for other in [k for k in self._slots if k is not None and k[0] == kind and k != key]:
+                del self._slots[other]
+        return out
+
+    def load_state_dict(self, sd):
+        """``HomographyTrainer.load_state_dict``, then the registered training packs are refreshed from the loaded parameters: a replay
+        starts at the forward and reads them as they stand (the eager step finds their tags stale and re-packs by itself)."""
+        super().load_state_dict(sd)
+        Fn.repack_all()
+
+    def step(self, img_a, patch_a, patch_b, corners):
+        return self._graphed("step", super().step, (img_a, patch_a, patch_b, corners))
+
+    def step_supervised(self, patch_a, patch_b, delta):
+        return self._graphed("supervised", super().step_supervised, (patch_a, patch_b, delta))
+
+    def step_pairs(self, *args, **kw):
+        raise NotImplementedError("GraphedHomographyTrainer.step_pairs: prepare the batch (homography.prepare_inputs) and call step")
 
 
 def comm_report(reducer):
