@@ -41,6 +41,12 @@ def lib():
     return _lib
 
 
+def rans_coder_revision():
+    """``hesic_rans_coder_revision`` of the loaded library (hesic_host.h); 1 for a library built before that entry point existed."""
+    l = lib()
+    return int(l.hesic_rans_coder_revision()) if hasattr(l, "hesic_rans_coder_revision") else 1
+
+
 def i32_array(seq):
     return (C.c_int32 * len(seq))(*seq)
 

@@ -383,6 +383,20 @@ _EN_TRAIN_SIGS = {
     "hesic_c32_mirror_weights": ([_vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp], _i32),
 }
 
+# include/hesic_rans.h: the device rANS coder for batches of independent streams, byte for byte the host coder's (functional.rans_encode /
+# rans_decode, EntropyBottleneck.compress_device / decompress_device, compress_batch / decompress_batch(z_coder="device")), in both libraries
+_RANS_SIGS = {
+    "hesic_rans_slot_bytes": ([_i64], _i64),
+    "hesic_rans_encode_ws_bytes": ([_i64, _i64], _i64),
+    "hesic_rans_encode": ([_vp, _i64, _i64, _i64, _i32, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
+                           _i32, _vp], _i32),
+    "hesic_rans_compact": ([_vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp], _i32),
+    "hesic_rans_decode": ([_vp, _i64, _vp, _vp, _i32, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp,
+                           _vp], _i32),
+}
+RANS_MAX_ROW = 512              # HESIC_RANS_MAX_ROW
+RANS_OVERFLOW, RANS_BAD_TABLE, RANS_BAD_ESCAPE, RANS_BAD_STREAM = 1, 2, 4, 8
+
 _libs = {}                      # torch 16-bit dtype -> CDLL
 _h16 = torch.bfloat16           # the active 16-bit format
 _lib = None                     # the active library (None until first use)
@@ -406,6 +420,7 @@ HEADERS = {
     "hesic_pair_augment.h": _PAIR_AUGMENT_SIGS,
     "hesic_pair_metrics.h": _PAIR_METRICS_SIGS,
     "hesic_en_train.h": _EN_TRAIN_SIGS,
+    "hesic_rans.h": _RANS_SIGS,
 }
 
 

@@ -87,8 +87,9 @@ def quantise(x):
     return (x.float().clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
 
 
-def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, log=print, homography_net=None):
-    """``homography_net=None``: the matrices come from the sidecars; a ``homography.Net``: from the net, for every pair."""
+def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, log=print, homography_net=None, z_coder="host"):
+    """``homography_net=None``: the matrices come from the sidecars; a ``homography.Net``: from the net, for every pair.  ``z_coder``: who
+    codes the z strings (``compress_batch``); the files are the same bytes either way."""
     from . import homography
     from .models import pad_to_multiple
     from .stereo_h import _image_size
@@ -115,7 +116,7 @@ def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, 
             else:
                 Hs = [np.load(hp).astype(np.float64).reshape(3, 3) for _, _, _, hp in chunk]
                 Hm = torch.from_numpy(np.stack(Hs)).float().cuda()
-            enc = net.compress_batch(x1, x2, Hm, channels_per_stream=channels_per_stream)
+            enc = net.compress_batch(x1, x2, Hm, channels_per_stream=channels_per_stream, z_coder=z_coder)
             for (stem, _, _, _), blob, Hn in zip(chunk, enc["blobs"], Hs):
                 (out / (stem + ".hsd")).write_bytes(blob)
                 (out / (stem + ".json")).write_text(json.dumps({"height": h, "width": w, "h_matrix": Hn.reshape(-1).tolist()}))
@@ -129,7 +130,7 @@ def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, 
     return res
 
 
-def decode_folder(net, src, recon, batch=8, log=print):
+def decode_folder(net, src, recon, batch=8, log=print, z_coder="host"):
     from PIL import Image
     src, recon = Path(src), Path(recon)
     recon.mkdir(parents=True, exist_ok=True)
@@ -145,7 +146,7 @@ def decode_folder(net, src, recon, batch=8, log=print):
         for c0 in range(0, len(items), batch):
             chunk = items[c0:c0 + batch]
             Hm = torch.tensor([s["h_matrix"] for _, _, s in chunk], dtype=torch.float64).reshape(-1, 3, 3).float().cuda()
-            dec = net.decompress_batch([b for _, b, _ in chunk], Hm)
+            dec = net.decompress_batch([b for _, b, _ in chunk], Hm, z_coder=z_coder)
             q1, q2 = quantise(dec["x1_hat"]), quantise(dec["x2_hat"])
             for i, (stem, _, s) in enumerate(chunk):
                 h, w = int(s["height"]), int(s["width"])
@@ -177,6 +178,8 @@ def main(argv=None):
         s.add_argument("--checkpoint", default=None)
         s.add_argument("--dtype", choices=sorted(_DTYPES), default="f16")
         s.add_argument("--model", choices=("hesic", "joint"), default="hesic", help="hesic: HSIC (default); joint: HESIC+ (HSICJoint)")
+        s.add_argument("--z-coder", choices=("host", "device"), default="host",
+                       help="who codes the z strings: the host rANS coder (default) or the device one; same bytes, same reconstructions")
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
         print("codec: needs a ROCm device (the range coder has no CPU path)", file=sys.stderr)
@@ -188,9 +191,9 @@ def main(argv=None):
         if a.homography_checkpoint and a.homography != "net":
             p.error("--homography-checkpoint needs --homography net")
         hnet = load_homography_net(a.homography_checkpoint) if a.homography == "net" else None
-        encode_folder(net, a.root, a.out, a.split, a.batch, a.channels_per_stream, homography_net=hnet)
+        encode_folder(net, a.root, a.out, a.split, a.batch, a.channels_per_stream, homography_net=hnet, z_coder=a.z_coder)
     else:
-        decode_folder(net, a.out, a.recon, a.batch)
+        decode_folder(net, a.out, a.recon, a.batch, z_coder=a.z_coder)
     return 0
 
 

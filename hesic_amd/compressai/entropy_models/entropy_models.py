@@ -316,6 +316,42 @@ class EntropyBottleneck(EntropyModel):
         medians = self._medians().detach().view(1, -1, 1, 1)
         return super().decompress(strings, indexes, medians)
 
+    # ------------------------------------------------------------------ the same strings, coded on the device (csrc/rans.hip)
+    def _device_tables(self, device):
+        """(table, lengths, offsets, medians) as the device coder takes them -- contiguous int32 / fp32 copies on ``device``, cached for as
+        long as the three table buffers and ``quantiles`` are the tensors they were copied from, unmodified: ``update(force=True)``
+        (new buffers), ``load_state_dict`` and an optimiser step (in-place writes) all change the tag, so the coder always sees what
+        ``compress`` / ``decompress`` see."""
+        tag = (device,) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in (self._quantized_cdf, self._cdf_length, self._offset, self.quantiles))
+        cache = getattr(self, "_rans_cache", None)
+        if cache is None or cache[0] != tag:
+            self._require_tables()
+            as_i32 = lambda t: t.detach().reshape(t.shape[0], -1).to(device, torch.int32).contiguous()
+            cache = (tag, as_i32(self._quantized_cdf), as_i32(self._cdf_length).reshape(-1), as_i32(self._offset).reshape(-1),
+                     self._medians().detach().reshape(-1).to(device, torch.float32).contiguous())
+            self._rans_cache = cache
+        return cache[1:]
+
+    def compress_device(self, x, out_dtype=None, launch_only=False):
+        """``compress`` for a batch with every symbol and table on the device: -> (data, counts, z_hat) -- ``data`` uint8 the strings of
+        ``compress(x)`` back to back, ``counts`` int32 (B) their lengths, z_hat = ``decompress(compress(x)).to(out_dtype)`` (default: the
+        compute dtype) channels-last, formed from the symbols that were coded, without decoding anything.  ``launch_only``: no
+        synchronisation -- (data, counts, status, z_hat) of ``Fn.rans_encode_launch``."""
+        if x.dim() != 4:
+            raise ValueError("Invalid `inputs` size. Expected a 4-D tensor.")
+        table, lengths, offsets, medians = self._device_tables(x.device)
+        symbols = self._quantize(x, "symbols", self._medians().detach().view(1, -1, 1, 1))       # the medians the cached copy was just checked against
+        fn = Fn.rans_encode_launch if launch_only else Fn.rans_encode
+        return fn(symbols, table, lengths, offsets, None, (medians, out_dtype or Fn.compute_dtype()))
+
+    def decompress_device(self, data, counts, size, out_dtype=None, check=True):
+        """``decompress`` for a batch on the device: ``data`` uint8 (device) the strings back to back, ``counts`` their lengths ->
+        z_hat (B, C, size[0], size[1]) channels-last in ``out_dtype`` (default: the compute dtype), the values of
+        ``decompress(strings, size).to(out_dtype)``.  ``check=False``: no synchronisation, -> (z_hat, status) for ``Fn.rans_check_status``."""
+        table, lengths, offsets, medians = self._device_tables(data.device)
+        return Fn.rans_decode(data, counts, (table.shape[0], int(size[0]), int(size[1])), table, lengths, offsets, None,
+                              (medians, out_dtype or Fn.compute_dtype()), check=check)
+
 
 class _GaussianBase(EntropyModel):
     """scale table / bound handling shared by the two conditional models."""

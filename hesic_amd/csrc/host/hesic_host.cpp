@@ -13,7 +13,8 @@ constexpr int kBypassBits = 4;        // raw-bit escape width
 constexpr uint32_t kBypassMax = (1u << kBypassBits) - 1;
 constexpr uint64_t kLow = 1ull << 31; // normalisation interval lower bound (ryg rans64)
 
-struct Item { uint16_t start, range; bool raw; };
+// range is 32 bits wide: a row that is its escape bin only (two entries) has the frequency 2^16, which a uint16 would turn into 0
+struct Item { uint16_t start; uint32_t range; bool raw; };
 
 // state update for a modelled symbol / for `bits` raw bits (freq = 2^(16-bits) in 16-bit terms)
 inline void put(uint64_t& x, std::vector<uint32_t>& words, uint32_t start, uint32_t freq, uint32_t scale_bits) {
@@ -79,6 +80,8 @@ extern "C" int hesic_pmf_rows_to_quantized_cdfs(const float* pmf, int rows, int 
     return 0;
 }
 
+extern "C" int hesic_rans_coder_revision(void) { return 2; }
+
 extern "C" hesic_rans_encoder* hesic_rans_encoder_new(void) { return new hesic_rans_encoder(); }
 extern "C" void hesic_rans_encoder_free(hesic_rans_encoder* e) { delete e; }
 
@@ -94,16 +97,16 @@ extern "C" int hesic_rans_encoder_push(hesic_rans_encoder* e, const int32_t* sym
         uint32_t raw = 0;
         if (v < 0) { raw = (uint32_t)(-2 * v - 1); v = last; }        // odd  => below the support
         else if (v >= last) { raw = (uint32_t)(2 * (v - last)); v = last; }  // even => at/above it
-        e->q.push_back({(uint16_t)cdf[v], (uint16_t)(cdf[v + 1] - cdf[v]), false});
+        e->q.push_back({(uint16_t)cdf[v], (uint32_t)(cdf[v + 1] - cdf[v]), false});
         if (v == last) {
             int32_t nib = 0;
-            while ((raw >> (nib * kBypassBits)) != 0) ++nib;
+            while (nib < 8 && (raw >> (nib * kBypassBits)) != 0) ++nib;    // 8 nibbles hold any raw (a shift by 32 would not end the loop)
             int32_t c = nib;                          // nibble count in unary-ish base-15 chunks
-            while (c >= (int32_t)kBypassMax) { e->q.push_back({(uint16_t)kBypassMax, (uint16_t)(kBypassMax + 1), true}); c -= kBypassMax; }
-            e->q.push_back({(uint16_t)c, (uint16_t)(c + 1), true});
+            while (c >= (int32_t)kBypassMax) { e->q.push_back({(uint16_t)kBypassMax, kBypassMax + 1, true}); c -= kBypassMax; }
+            e->q.push_back({(uint16_t)c, (uint32_t)(c + 1), true});
             for (int32_t j = 0; j < nib; ++j) {
                 const uint16_t d = (uint16_t)((raw >> (j * kBypassBits)) & kBypassMax);
-                e->q.push_back({d, (uint16_t)(d + 1), true});
+                e->q.push_back({d, (uint32_t)(d + 1), true});
             }
         }
     }

@@ -24,6 +24,11 @@ int hesic_pmf_rows_to_quantized_cdfs(const float* pmf, int rows, int pmf_stride,
 typedef struct hesic_rans_encoder hesic_rans_encoder;
 typedef struct hesic_rans_decoder hesic_rans_decoder;
 
+/* Revision of the rANS coder below.  2: codes every int32 symbol under every valid row -- a row that is its escape bin only
+ * (frequency 2^16) and escapes whose raw value needs 29 .. 32 bits.  A library without this entry point is revision 1, whose
+ * encoder divides by zero on the first and does not terminate on the second; the streams it does write are unchanged. */
+int hesic_rans_coder_revision(void);
+
 hesic_rans_encoder* hesic_rans_encoder_new(void);
 void hesic_rans_encoder_free(hesic_rans_encoder*);
 /* Queue n symbols.  cdfs: [ncdf][cdf_stride] int32 row-major; cdf_sizes/offsets: [ncdf]. */

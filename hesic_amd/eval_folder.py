@@ -54,6 +54,7 @@ def parser():
                    help="run Independent_EN on the reconstructions: a second_checkpoint*.pth.tar, or 'synthetic' for the deterministic weights")
     p.add_argument("--coded", action="store_true", help="also range-code every pair (compress_batch) and record coded_bpp")
     p.add_argument("--channels-per-stream", type=int, default=1)
+    p.add_argument("--z-coder", choices=("host", "device"), default="host", help="with --coded: who codes the z strings (same bytes)")
     p.add_argument("--out", default=None, help="also write the summary line to this file")
     return p
 
@@ -118,7 +119,7 @@ def load_enhancer(spec, device="cuda"):
     return en.to(device).eval()
 
 
-def evaluate_folder(net, root, split="test", batch=8, homography_net=None, enhancer=None, coded=False, channels_per_stream=1, log=print):
+def evaluate_folder(net, root, split="test", batch=8, homography_net=None, enhancer=None, coded=False, channels_per_stream=1, log=print, z_coder="host"):
     """(records, summary) of ROOT/<split>; every record and the summary are logged as one JSON line each."""
     from . import homography, models
     chunks, skipped = plan(root, split, batch, sidecars=homography_net is None)
@@ -149,7 +150,7 @@ def evaluate_folder(net, root, split="test", batch=8, homography_net=None, enhan
             else:
                 cols += [torch.full_like(m["bpp"], float("nan"))] * len(MS_SSIM_FIELDS)
             rows.append(torch.stack(cols, 1))                           # (B, columns) fp64, stays on the device
-            blobs = net.compress_batch(x1p, x2p, Hm, channels_per_stream=channels_per_stream)["blobs"] if coded else [None] * len(chunk)
+            blobs = net.compress_batch(x1p, x2p, Hm, channels_per_stream=channels_per_stream, z_coder=z_coder)["blobs"] if coded else [None] * len(chunk)
             for (stem, _, _, _), blob in zip(chunk, blobs):
                 meta.append((stem, h, w, with_ssim, None if blob is None else len(blob) * 8 / (2 * h * w)))   # against the ORIGINAL pixels
         table = torch.cat(rows).cpu().tolist() if rows else []          # the one read-back of the folder
@@ -192,7 +193,7 @@ def main(argv=None, log=print):
         net = codec.load_model(a.checkpoint, codec._DTYPES[a.dtype], model=a.model)
         hnet = codec.load_homography_net(a.homography_checkpoint) if a.homography == "net" else None
         enhancer = load_enhancer(a.enhancer) if a.enhancer else None
-        records, summary = evaluate_folder(net, a.root, a.split, a.batch, hnet, enhancer, a.coded, a.channels_per_stream, log)
+        records, summary = evaluate_folder(net, a.root, a.split, a.batch, hnet, enhancer, a.coded, a.channels_per_stream, log, z_coder=a.z_coder)
         if a.out:
             with open(a.out, "w") as f:
                 f.write(json.dumps(summary) + "\n")

@@ -2888,6 +2888,154 @@ def gmm_rc_decode_step(sm, B, P, M, meta, channels_per_stream, data, offsets, co
            L.ptr(state), int(bool(first)), L.ptr(centre), int(group_offset), centre.numel(), L.ptr(y_rows), L.dt(y_rows), y_rows.shape[1], L.stream())
 
 
+# ----------------------------------------------------------------------------------- device rANS coder (include/hesic_rans.h)
+_RANS_STATUS = ((L.RANS_OVERFLOW, "the stream overflowed its slot of 8 bytes per symbol + 16"),
+                (L.RANS_BAD_TABLE, "a row index outside the table, a row size outside [2, row stride] or a zero frequency"),
+                (L.RANS_BAD_ESCAPE, "an escape claims more than 8 data nibbles"),
+                (L.RANS_BAD_STREAM, "the stream is shorter than 8 bytes, not whole 32-bit words or outside the payload"))
+
+
+def rans_check_status(who, status):
+    """``status``: the per-stream int32 words of a device rANS launch, already on the host (a list or tensor).  A non-zero word raises
+    ``ValueError`` naming the first such stream."""
+    for t, st in enumerate(status.tolist() if torch.is_tensor(status) else status):
+        if st:
+            raise ValueError(f"{who}: stream {t}: " + " and ".join(msg for bit, msg in _RANS_STATUS if st & bit))
+
+
+def _rans_tables(who, table, lengths, offsets, indexes, dequant, B, n):
+    L.require_cuda(table, lengths, offsets, indexes)
+    if (table.dim() != 2 or any(t.dtype != torch.int32 or not t.is_contiguous() for t in (table, lengths, offsets))
+            or lengths.numel() != table.shape[0] or offsets.numel() != table.shape[0]):
+        raise ValueError(f"{who}: table (rows, stride), lengths (rows) and offsets (rows) must be contiguous int32 tensors")
+    if table.shape[1] > L.RANS_MAX_ROW:
+        raise ValueError(f"{who}: rows of {table.shape[1]} entries; the device coder holds a row in one wave's registers, up to {L.RANS_MAX_ROW}")
+    istride = 0
+    if indexes is not None:
+        if indexes.dtype != torch.int32 or not indexes.is_contiguous() or indexes.numel() not in (n, B * n):
+            raise ValueError(f"{who}: indexes must be a contiguous int32 tensor of {n} (shared) or {B * n} (per stream) entries in coding order")
+        istride = n if indexes.numel() == B * n and B > 1 else 0
+    med, zdt = None, None
+    if dequant is not None:
+        med, zdt = dequant
+        L.require_cuda(med)
+        med = med.detach().reshape(-1)
+        if med.dtype != torch.float32 or med.numel() != table.shape[0] or not med.is_contiguous():
+            raise ValueError(f"{who}: dequant = (medians, dtype) with one contiguous fp32 median per table row")
+    return istride, med, zdt
+
+
+def _rans_strides(t):
+    """(B, n, P, (sb, sc, sp)) of a (B, n) / (B, C, P) / (B, C, H, W) tensor whose pixels lie at one stride (contiguous or channels-last)."""
+    if t.dim() == 2:
+        return t.shape[0], t.shape[1], t.shape[1], (t.stride(0), 0, t.stride(1))
+    if t.dim() == 3:
+        return t.shape[0], t.shape[1] * t.shape[2], t.shape[2], t.stride()
+    if t.dim() == 4 and t.shape[3] == 1:             # a column: the stride of a size-1 dimension means nothing
+        return t.shape[0], t.shape[1] * t.shape[2], t.shape[2], (t.stride(0), t.stride(1), t.stride(2))
+    if t.dim() == 4 and (t.shape[2] == 1 or t.stride(2) == t.shape[3] * t.stride(3)):
+        return t.shape[0], t.shape[1] * t.shape[2] * t.shape[3], t.shape[2] * t.shape[3], (t.stride(0), t.stride(1), t.stride(3))
+    return None
+
+
+def rans_encode_launch(symbols, table, lengths, offsets, indexes=None, dequant=None):
+    """The launches of ``rans_encode`` without a synchronisation: (data, counts, status[, z_hat]) with ``data`` of the worst-case size --
+    the streams lie back to back in its first ``counts.sum()`` bytes -- and ``status`` the per-stream int32 words for ``rans_check_status``."""
+    L.require_cuda(symbols)
+    if symbols.dtype != torch.int32 or symbols.dim() not in (2, 3, 4):
+        raise ValueError("rans_encode: symbols must be an int32 (B, n), (B, C, P) or (B, C, H, W) tensor")
+    geo = _rans_strides(symbols)
+    if geo is None:
+        symbols = symbols.contiguous()
+        geo = _rans_strides(symbols)
+    B, n, P, (sb, sc, sp) = geo
+    if B < 1 or n < 1:
+        raise ValueError("rans_encode: empty batch")
+    istride, med, zdt = _rans_tables("rans_encode", table, lengths, offsets, indexes, dequant, B, n)
+    z_hat = None
+    if med is not None:
+        # the kernel writes z_hat with the SYMBOLS' strides.  empty_like keeps them for a dense tensor only: for a sliced view (a channel
+        # or column range of a larger map) it packs them, so such symbols are copied first and both tensors are dense
+        def used(t):
+            _, _, _, st = _rans_strides(t)
+            return tuple(s_ for s_, k in zip(st, (B, n // P, P)) if k > 1)
+        z_hat = torch.empty_like(symbols, dtype=zdt)
+        if used(z_hat) != used(symbols):
+            symbols = symbols.contiguous()
+            _, _, _, (sb, sc, sp) = _rans_strides(symbols)
+            z_hat = torch.empty_like(symbols, dtype=zdt)
+            if used(z_hat) != used(symbols):
+                raise RuntimeError("rans_encode: z_hat does not share the symbols' strides")
+    dev = symbols.device
+    slot = 8 * n + 16
+    ws = torch.empty(((B * n * 9 + 7) // 8,), dtype=torch.int64, device=dev)
+    slots = torch.empty((B, slot), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    L.call("hesic_rans_encode", L.ptr(symbols), sb, sc, sp, B, n, P, L.ptr(indexes), istride, L.ptr(table), table.shape[0], table.shape[1],
+           L.ptr(lengths), L.ptr(offsets), L.ptr(ws), ws.numel() * 8, L.ptr(slots), slot, L.ptr(counts), L.ptr(status), L.ptr(med), L.ptr(z_hat),
+           L.F32 if z_hat is None else L.dt(z_hat), L.stream())
+    out_offsets = torch.cumsum(counts, 0, dtype=torch.int64) - counts
+    data = torch.empty((B * slot,), dtype=torch.uint8, device=dev)
+    L.call("hesic_rans_compact", L.ptr(slots), slot, L.ptr(counts), L.ptr(out_offsets), B, L.ptr(data), data.numel(), L.stream())
+    return (data, counts, status) if z_hat is None else (data, counts, status, z_hat)
+
+
+def rans_encode(symbols, table, lengths, offsets, indexes=None, dequant=None):
+    """A batch of independent rANS streams on the device (``hesic_rans_encode``), each byte for byte ``_host.rans_encode_arrays`` of its
+    symbols: ``symbols`` int32 (B, n), (B, C, P) or (B, C, H, W), contiguous or channels-last (read in place), stream b = symbols[b] in
+    (C, P) order; ``table`` / ``lengths`` / ``offsets`` the int32 ``_quantized_cdf`` (rows, stride), ``_cdf_length`` and ``_offset``;
+    ``indexes`` None -- the row of a symbol is its channel (row 0 for a (B, n) tensor) -- or int32 rows in coding order, n entries shared
+    by the batch or B * n per stream; ``dequant`` = (medians fp32 (rows), dtype) also returns z_hat = (symbols + medians[row]).to(dtype) in
+    the symbols' layout.  -> (data uint8 the streams back to back, counts int32 (B)[, z_hat]), all on the device.  A non-zero status
+    raises ``ValueError`` naming the stream."""
+    data, counts, status, *z = rans_encode_launch(symbols, table, lengths, offsets, indexes, dequant)
+    host = torch.cat([status, counts]).cpu()
+    B = counts.numel()
+    rans_check_status("rans_encode", host[:B])
+    return (data[:int(host[B:].sum())], counts, *z)
+
+
+def rans_decode(data, counts, n, table, lengths, offsets, indexes=None, dequant=None, want_symbols=None, check=True):
+    """Inverse of ``rans_encode`` (``hesic_rans_decode``): ``data`` uint8 (device) the streams back to back, ``counts`` their B lengths, ``n``
+    the symbols per stream as an int (-> (B, n)), (C, P) (-> (B, C, P)) or (C, H, W) (-> (B, C, H, W) channels-last).  Returns the int32
+    symbols, or with ``dequant`` = (medians, dtype) z_hat = (symbols + medians[row]).to(dtype) (``want_symbols=True``: both).  A word past
+    a stream's end reads as zero, as the host decoder's.  ``check=False`` skips the synchronising status check and returns
+    (result, status) for ``rans_check_status``."""
+    L.require_cuda(data)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise ValueError("rans_decode: data must be a contiguous 1-d uint8 tensor")
+    if data.data_ptr() % 4:
+        data = data.clone()
+    dev = data.device
+    counts = torch.as_tensor(counts, dtype=torch.int32, device=dev).reshape(-1).contiguous()
+    B = counts.numel()
+    shape = (int(n),) if isinstance(n, int) else tuple(int(v) for v in n)
+    if B < 1 or len(shape) not in (1, 2, 3) or any(v < 1 for v in shape):
+        raise ValueError("rans_decode: n must be an int, (C, P) or (C, H, W), and counts non-empty")
+    want_symbols = dequant is None if want_symbols is None else bool(want_symbols)
+    if not want_symbols and dequant is None:
+        raise ValueError("rans_decode: nothing to return")
+    fmt = _CL if len(shape) == 3 else torch.contiguous_format
+    like = torch.empty((B,) + shape, dtype=torch.int32, device=dev, memory_format=fmt) if want_symbols else None
+    nsym = 1
+    for v in shape:
+        nsym *= v
+    istride, med, zdt = _rans_tables("rans_decode", table, lengths, offsets, indexes, dequant, B, nsym)
+    z_hat = None if med is None else torch.empty((B,) + shape, dtype=zdt, device=dev, memory_format=fmt)
+    _, _, P, (sb, sc, sp) = _rans_strides(like if like is not None else z_hat)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    data_offsets = torch.cumsum(counts, 0, dtype=torch.int64) - counts
+    L.call("hesic_rans_decode", L.ptr(data), data.numel(), L.ptr(data_offsets), L.ptr(counts), B, nsym, P, L.ptr(indexes), istride, L.ptr(table),
+           table.shape[0], table.shape[1], L.ptr(lengths), L.ptr(offsets), L.ptr(like), sb, sc, sp, L.ptr(med), L.ptr(z_hat),
+           L.F32 if z_hat is None else L.dt(z_hat), L.ptr(status), L.stream())
+    out = like if z_hat is None else (z_hat if like is None else (like, z_hat))
+    if not check:
+        return out, status
+    rans_check_status("rans_decode", status.cpu())
+    return out
+
+
 def quantize_symbols(y, means=None):
     """EntropyModel._quantize(x, 'symbols', means) (entropy_models.py:98-125): int32 indices."""
     L.require_cuda(y)

@@ -637,6 +637,65 @@ def _decompress_z(bottleneck, strings, size):
     return EntropyModel.decompress(bottleneck, list(strings), bottleneck._build_indexes(shape), medians)
 
 
+Z_CODERS = ("host", "device")
+
+
+def _check_z_coder(who, z_coder):
+    if z_coder not in Z_CODERS:
+        raise ValueError(f'{who}: z_coder must be "host" or "device", got {z_coder!r}')
+    return z_coder == "device"
+
+
+def _code_z(bottleneck, z, device, cdt):
+    """The z side of one view in the analysis chain of ``compress_batch``: -> (strings, z_hat).  Host coder: the strings of
+    ``bottleneck.compress`` and what decoding them yields (two synchronising round trips).  Device coder (csrc/rans.hip): the same bytes
+    stay on the device as a pending (data, counts, status) triple for ``_read_z_strings``, z_hat comes from the symbols that were
+    coded, and nothing synchronises."""
+    if not device:
+        strings = bottleneck.compress(z)
+        return strings, _decompress_z(bottleneck, strings, z.size()[-2:]).to(cdt)
+    data, counts, status, z_hat = bottleneck.compress_device(z, cdt, launch_only=True)
+    return (data, counts, status), z_hat
+
+
+def _read_z_strings(who, pending):
+    """The pending device z strings of both views -> per view the list of B ``bytes``: one read of the counts and status words, one of
+    the bytes of both views."""
+    host = torch.cat([t for _d, counts, status in pending for t in (status, counts)]).cpu().tolist()
+    blocks, lens, pos = [], [], 0
+    for vi, (data, counts, _status) in enumerate(pending):
+        B = counts.numel()
+        Fn.rans_check_status(f"{who}: z string of view {vi + 1}", host[pos:pos + B])
+        lens.append(host[pos + B:pos + 2 * B])
+        blocks.append(data[:sum(lens[-1])])
+        pos += 2 * B
+    raw = torch.cat(blocks).cpu().numpy().tobytes()
+    out, pos = [], 0
+    for ls in lens:
+        strings = []
+        for n in ls:
+            strings.append(raw[pos:pos + n])
+            pos += n
+        out.append(strings)
+    return out
+
+
+def _decode_z_device(who, bottlenecks, per_view, zs, dev, cdt):
+    """The z strings of both views of a batch, uploaded in one copy and decoded on the device: -> (z1_hat, z2_hat, status) with the
+    per-stream status words of both launches for ``Fn.rans_check_status`` at the end of the call (no synchronisation here).  The lengths
+    are validated on the host first."""
+    strings = [list(per_view[vi][2]) for vi in range(2)]
+    for vi in range(2):
+        for b, s_ in enumerate(strings[vi]):
+            if len(s_) < 8 or len(s_) % 4:
+                raise ValueError(f"{who}: the z string of pair {b}, view {vi + 1} has {len(s_)} bytes: not whole 32-bit words of a rANS stream")
+    buf = torch.frombuffer(bytearray(b"".join(strings[0] + strings[1])), dtype=torch.uint8).to(dev)
+    cut = sum(len(s_) for s_ in strings[0])
+    outs = [bottlenecks[vi].decompress_device(part, [len(s_) for s_ in strings[vi]], zs, cdt, check=False)
+            for vi, part in enumerate((buf[:cut], buf[cut:]))]
+    return outs[0][0], outs[1][0], torch.cat([outs[0][1], outs[1][1]])
+
+
 def _batch_blobs(who, kind, blobs, h_matrix, M):
     """The host-side validation of ``decompress_batch`` (both codecs), before anything is launched: every blob parses
     (``bitstream.parse_pair``), is of ``kind``, and they agree on size and channels_per_stream; alphabets and channel lists are what the
@@ -744,21 +803,19 @@ class HSIC(StereoCompressionModel):
                 sym = (y_hat[0, ch].float().cpu().numpy().astype(np.int64) + minmax).reshape(-1).astype(np.int32)
             yield ch, sym, cdf
 
-    def _analysis(self, x1, x2, h_matrix):
+    def _analysis(self, x1, x2, h_matrix, device_z=False):
         size = (x1.shape[-2], x1.shape[-1])
         cdt = Fn.compute_dtype()
         y1_lo, y1 = self.encoder1.latent(x1, exact=True, lo_abs=self._LO_ABS)
         z1 = self._h_a1.latent(y1_lo)
-        z1_strings = self.entropy_bottleneck1.compress(z1)
-        z1_hat = _decompress_z(self.entropy_bottleneck1, z1_strings, z1.size()[-2:]).to(cdt)
+        z1_strings, z1_hat = _code_z(self.entropy_bottleneck1, z1, device_z, cdt)
         gmm1 = self._h_s1(z1_hat, hi=True)
         y1_hat = _round_latent(self.gaussian1, y1)
         x1_hat = self.decoder1(y1_hat)
         x1_warp = warp_perspective(x1, h_matrix, size)
         y2_lo, y2 = self.encoder2.latent(x1_warp, x2, exact=True, lo_abs=self._LO_ABS)
         z2 = self._h_a2.latent(y2_lo)
-        z2_strings = self.entropy_bottleneck2.compress(z2)
-        z2_hat = _decompress_z(self.entropy_bottleneck2, z2_strings, z2.size()[-2:]).to(cdt)
+        z2_strings, z2_hat = _code_z(self.entropy_bottleneck2, z2, device_z, cdt)
         x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
         y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
         gmm2 = self._h_s2(z2_hat, y1_hat_w, hi=True)
@@ -858,15 +915,20 @@ class HSIC(StereoCompressionModel):
     # ------------------------------------------------------------------------------- batched bit-stream, coded on the device
     # The same flow for a whole batch, with the range coder on the GPU (csrc/codec.hip): per view one launch for the coding intervals of
     # every latent of every image, one for the streams (one per ``channels_per_stream`` coded channels), one to compact them -- no table
-    # and no symbol leaves the device.  One self-contained blob per pair (hesic_amd/bitstream.py); the z strings stay on the host rANS
-    # coder.  Pairs are independent: blob i does not depend on what else is in the batch.
-    def compress_batch(self, x1, x2, h_matrix, channels_per_stream=1):
+    # and no symbol of y leaves the device.  One self-contained blob per pair (hesic_amd/bitstream.py).  The z strings are coded by the host
+    # rANS coder (``z_coder="host"``, the default: z is quantised, copied to the host, coded one image at a time and decoded again for
+    # z_hat -- two synchronising round trips inside the analysis chain) or by the device rANS coder (``z_coder="device"``, csrc/rans.hip:
+    # the same bytes, no round trip; the z bytes are read back after the y streams).  Pairs are independent: blob i does not depend on what
+    # else is in the batch.
+    def compress_batch(self, x1, x2, h_matrix, channels_per_stream=1, z_coder="host"):
         """(B, 3, H, W) pairs -> dict(blobs: one ``bytes`` per pair (``bitstream.pack_pair``), bpp_real: one figure per pair over its
         2 H W pixels, y1_hat, y2_hat, z1_hat, z2_hat).  ``channels_per_stream``: coded channels per range-coder stream -- 1 gives the
         shortest serial chains (fastest), larger values fewer stream terminations and lengths (smaller blobs).  An image whose latents
-        need an alphabet beyond the device coder's 1024 symbols raises ``ValueError``: code that pair with ``compress``."""
+        need an alphabet beyond the device coder's 1024 symbols raises ``ValueError``: code that pair with ``compress``.  ``z_coder``:
+        "host" or "device", who codes the z strings -- the blobs are the same bytes either way."""
         from . import bitstream
         _check_pair(x1, x2, h_matrix)
+        device_z = _check_z_coder("HSIC.compress_batch", z_coder)
         if not x1.is_cuda:
             raise RuntimeError("HSIC.compress_batch: the device range coder needs tensors on a ROCm device (no CPU fallback)")
         cps = int(channels_per_stream)
@@ -876,7 +938,7 @@ class HSIC(StereoCompressionModel):
             self.update()
         B, _, H, W = x1.shape
         with torch.no_grad():
-            v1, v2 = self._analysis(x1, x2, h_matrix)
+            v1, v2 = self._analysis(x1, x2, h_matrix, device_z)
             # one small device -> host read: per image, view and channel max |y_hat| (minmax and the flags follow from it)
             peak = torch.stack([v[0].float().abs().amax(dim=(2, 3)) for v in (v1, v2)]).cpu()
             views = [[None, None] for _ in range(B)]
@@ -892,15 +954,23 @@ class HSIC(StereoCompressionModel):
                     for n in counts[b][:bitstream.n_streams(flags[b], cps)]:
                         streams.append(data[pos:pos + n])
                         pos += n
-                    views[b][vi] = {"minmax": minmax[b], "flags": tuple(int(f) for f in flags[b]), "z": z_strings[b], "streams": streams}
+                    views[b][vi] = {"minmax": minmax[b], "flags": tuple(int(f) for f in flags[b]), "z": None if device_z else z_strings[b],
+                                    "streams": streams}
+            if device_z:
+                for vi, strings in enumerate(_read_z_strings("HSIC.compress_batch", (v1[2], v2[2]))):
+                    for b in range(B):
+                        views[b][vi]["z"] = strings[b]
         blobs = [bitstream.pack_pair({"mode": payload_mode_bytes(), "height": H, "width": W, "channels": self.M, "channels_per_stream": cps,
                                       "views": views[b]}) for b in range(B)]
         return {"blobs": blobs, "bpp_real": [len(bl) * 8 / (H * W * 2) for bl in blobs],
                 "y1_hat": v1[0], "y2_hat": v2[0], "z1_hat": v1[1], "z2_hat": v2[1]}
 
-    def decompress_batch(self, blobs, h_matrix):
+    def decompress_batch(self, blobs, h_matrix, z_coder="host"):
         """``blobs``: what ``compress_batch`` returned, in any grouping and order (all of one image size); ``h_matrix`` (B, 3, 3) the
-        matching homographies.  Everything is validated on the host before the first launch."""
+        matching homographies.  Everything is validated on the host before the first launch.  ``z_coder``: "host" decodes the 2 B z
+        strings on the host before the first launch, "device" uploads them in one copy and decodes them there; either reads the blobs of
+        either encoder setting."""
+        device_z = _check_z_coder("HSIC.decompress_batch", z_coder)
         B, H, W, cps, per_view = _batch_blobs("HSIC.decompress_batch", "hesic", blobs, h_matrix, self.M)
         if self.entropy_bottleneck1._offset.numel() == 0:
             self.update()
@@ -913,8 +983,13 @@ class HSIC(StereoCompressionModel):
             return Fn.gmm_rc_decode(gmm[0], gmm[1], gmm[2], minmax, channels, self.K, data, counts, cdt, cps, gauss._bound())
 
         with torch.no_grad():
-            z1_hat = _decompress_z(self.entropy_bottleneck1, per_view[0][2], zs).to(dev, cdt)
-            z2_hat = _decompress_z(self.entropy_bottleneck2, per_view[1][2], zs).to(dev, cdt)
+            z_status = None
+            if device_z:
+                z1_hat, z2_hat, z_status = _decode_z_device("HSIC.decompress_batch", (self.entropy_bottleneck1, self.entropy_bottleneck2),
+                                                            per_view, zs, dev, cdt)
+            else:
+                z1_hat = _decompress_z(self.entropy_bottleneck1, per_view[0][2], zs).to(dev, cdt)
+                z2_hat = _decompress_z(self.entropy_bottleneck2, per_view[1][2], zs).to(dev, cdt)
             gmm1 = self._h_s1(z1_hat, hi=True)
             y1_hat = decode_view(gmm1, per_view[0], self.gaussian1)
             x1_hat = self.decoder1(y1_hat)
@@ -923,6 +998,8 @@ class HSIC(StereoCompressionModel):
             gmm2 = self._h_s2(z2_hat, y1_hat_w, hi=True)
             y2_hat = decode_view(gmm2, per_view[1], self.gaussian2)
             x2_hat = self.decoder2(y2_hat, x1_hat_warp)
+            if z_status is not None:
+                Fn.rans_check_status("HSIC.decompress_batch: z string", z_status.cpu())
         return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
 
     def _forward_eval(self, x1, x2, h_matrix, two_streams=True):
@@ -1309,7 +1386,7 @@ class HSICJoint(StereoCompressionModel):
         cuts = np.flatnonzero(np.diff(t[order])) + 1
         return np.split(order.astype(np.int64), cuts)
 
-    def _coder_inputs(self, x1, x2, h_matrix):
+    def _coder_inputs(self, x1, x2, h_matrix, device_z=False):
         """The encoder's side of the real bit-stream for B pairs, shared by ``compress`` and ``compress_batch`` (their streams must be formed
         from the same numbers): per view (y_hat, z strings, z_hat, scales, means) with the context model evaluated on the whole maps.
         Call it under ``torch.no_grad()`` and ``Fn.no_split_k()`` with the context masks applied to the weights."""
@@ -1317,16 +1394,14 @@ class HSICJoint(StereoCompressionModel):
         cdt = Fn.compute_dtype()
         y1_lo, y1 = self.encoder1.latent(x1, exact=True, lo_abs=self._LO_ABS)
         z1 = _seq3_hi(self.h_a1, y1_lo)
-        z1_strings = self.entropy_bottleneck1.compress(z1)
-        z1_hat = _decompress_z(self.entropy_bottleneck1, z1_strings, z1.size()[-2:]).to(cdt)
+        z1_strings, z1_hat = _code_z(self.entropy_bottleneck1, z1, device_z, cdt)
         y1_hat = _round_latent(self.gaussian_conditional1, y1)
         sc1, mu1 = self._gauss_full(1, self._params_view(1, z1_hat), y1_hat)
         x1_hat = self.decoder1(y1_hat)
         x1_warp = warp_perspective(x1, h_matrix, size)
         y2_lo, y2 = self.encoder2.latent(x1_warp, x2, exact=True, lo_abs=self._LO_ABS)
         z2 = _seq3_hi(self.h_a2, y2_lo)
-        z2_strings = self.entropy_bottleneck2.compress(z2)
-        z2_hat = _decompress_z(self.entropy_bottleneck2, z2_strings, z2.size()[-2:]).to(cdt)
+        z2_strings, z2_hat = _code_z(self.entropy_bottleneck2, z2, device_z, cdt)
         x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
         y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
         y2_hat = _round_latent(self.gaussian_conditional2, y2)
@@ -1708,13 +1783,14 @@ class HSICJoint(StereoCompressionModel):
     # images together: per group a gather of the B * P crops and feature rows, the masked 5x5 conv, the three 1x1 layers and the step
     # decoder, which writes the symbols straight into the padded maps -- six dependent launches, no host in the loop; the walk of a view is
     # captured as one HIP graph and replayed.  As in the per-pair path the convs run unsplit, so that the decoder sums in the encoder's order.
-    def compress_batch(self, x1, x2, h_matrix, channels_per_stream=1):
+    def compress_batch(self, x1, x2, h_matrix, channels_per_stream=1, z_coder="host"):
         """(B, 3, H, W) pairs -> dict(blobs: one ``bytes`` per pair (``bitstream.pack_pair``, kind "joint"), bpp_real: one figure per pair
-        over its 2 H W pixels, y1_hat, y2_hat, z1_hat, z2_hat).  ``channels_per_stream`` as in ``HSIC.compress_batch``.  An image whose
-        latents need an alphabet beyond the device coder's 1024 symbols raises ``ValueError``: code that pair with ``compress``."""
+        over its 2 H W pixels, y1_hat, y2_hat, z1_hat, z2_hat).  ``channels_per_stream`` and ``z_coder`` as in ``HSIC.compress_batch``.  An
+        image whose latents need an alphabet beyond the device coder's 1024 symbols raises ``ValueError``: code that pair with ``compress``."""
         import numpy as np
         from . import bitstream
         _check_pair(x1, x2, h_matrix)
+        device_z = _check_z_coder("HSICJoint.compress_batch", z_coder)
         if not x1.is_cuda:
             raise RuntimeError("HSICJoint.compress_batch: the device range coder needs tensors on a ROCm device (no CPU fallback)")
         cps = int(channels_per_stream)
@@ -1726,7 +1802,7 @@ class HSICJoint(StereoCompressionModel):
         with torch.no_grad(), Fn.no_split_k():
             self.context_prediction1.weight.data *= self.context_prediction1.mask
             self.context_prediction2.weight.data *= self.context_prediction2.mask
-            (y1_hat, z1_strings, z1_hat, sc1, mu1), (y2_hat, z2_strings, z2_hat, sc2, mu2) = self._coder_inputs(x1, x2, h_matrix)
+            (y1_hat, z1_strings, z1_hat, sc1, mu1), (y2_hat, z2_strings, z2_hat, sc2, mu2) = self._coder_inputs(x1, x2, h_matrix, device_z)
             order = torch.from_numpy(np.concatenate(self._wavefronts(H // 16, W // 16)).astype(np.int32)).to(x1.device)
             bound = self.gaussian_conditional1._bound()
             # one small device -> host read: per image, view and channel max |y_hat| (minmax and the flags follow from it)
@@ -1744,7 +1820,12 @@ class HSICJoint(StereoCompressionModel):
                     for n in counts[b][:bitstream.n_streams(flags[b], cps)]:
                         streams.append(data[pos:pos + n])
                         pos += n
-                    views[b][vi] = {"minmax": minmax[b], "flags": tuple(int(f) for f in flags[b]), "z": z_strings[b], "streams": streams}
+                    views[b][vi] = {"minmax": minmax[b], "flags": tuple(int(f) for f in flags[b]), "z": None if device_z else z_strings[b],
+                                    "streams": streams}
+            if device_z:
+                for vi, strings in enumerate(_read_z_strings("HSICJoint.compress_batch", (z1_strings, z2_strings))):
+                    for b in range(B):
+                        views[b][vi]["z"] = strings[b]
         blobs = [bitstream.pack_pair({"kind": "joint", "mode": payload_mode_bytes(), "height": H, "width": W, "channels": self.M,
                                       "channels_per_stream": cps, "views": views[b]}) for b in range(B)]
         return {"blobs": blobs, "bpp_real": [len(bl) * 8 / (H * W * 2) for bl in blobs],
@@ -1847,9 +1928,11 @@ class HSICJoint(StereoCompressionModel):
         st["graph"].replay()
         return st["y_pad"][:, :, 2:-2, 2:-2].contiguous(memory_format=torch.channels_last)
 
-    def decompress_batch(self, blobs, h_matrix):
+    def decompress_batch(self, blobs, h_matrix, z_coder="host"):
         """``blobs``: what ``compress_batch`` returned, in any grouping and order (all of one image size and channels_per_stream);
-        ``h_matrix`` (B, 3, 3) the matching homographies.  Everything is validated on the host before the first launch."""
+        ``h_matrix`` (B, 3, 3) the matching homographies.  Everything is validated on the host before the first launch.  ``z_coder`` as in
+        ``HSIC.decompress_batch``."""
+        device_z = _check_z_coder("HSICJoint.decompress_batch", z_coder)
         B, H, W, cps, per_view = _batch_blobs("HSICJoint.decompress_batch", "joint", blobs, h_matrix, self.M)
         if self.entropy_bottleneck1._offset.numel() == 0:
             self.update()
@@ -1859,14 +1942,21 @@ class HSICJoint(StereoCompressionModel):
         with torch.no_grad(), Fn.no_split_k():
             self.context_prediction1.weight.data *= self.context_prediction1.mask
             self.context_prediction2.weight.data *= self.context_prediction2.mask
-            z1_hat = _decompress_z(self.entropy_bottleneck1, per_view[0][2], zs).to(dev, cdt)
-            z2_hat = _decompress_z(self.entropy_bottleneck2, per_view[1][2], zs).to(dev, cdt)
+            z_status = None
+            if device_z:
+                z1_hat, z2_hat, z_status = _decode_z_device("HSICJoint.decompress_batch", (self.entropy_bottleneck1, self.entropy_bottleneck2),
+                                                            per_view, zs, dev, cdt)
+            else:
+                z1_hat = _decompress_z(self.entropy_bottleneck1, per_view[0][2], zs).to(dev, cdt)
+                z2_hat = _decompress_z(self.entropy_bottleneck2, per_view[1][2], zs).to(dev, cdt)
             y1_hat = self._decode_view_batch(1, self._params_view(1, z1_hat), per_view[0], cps, None, yh, yw)
             x1_hat = self.decoder1(y1_hat)
             x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
             y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
             y2_hat = self._decode_view_batch(2, self._params_view(2, z2_hat), per_view[1], cps, y1_hat_w, yh, yw)
             x2_hat = self.decoder2(y2_hat, x1_hat_warp)
+            if z_status is not None:
+                Fn.rans_check_status("HSICJoint.decompress_batch: z string", z_status.cpu())
         return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
 
 
