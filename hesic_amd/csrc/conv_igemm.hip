@@ -2678,3 +2678,21 @@ extern "C" size_t hesic_conv2d_hilo_ws_bytes(const hesic_conv_desc* d) {
     o.hilo = 1;
     return igemm_ws_query(d, o);
 }
+
+/* The plan of a pair launch: hesic_conv2d_variant plans with the default options, which no pair launch has.  Host arithmetic only. */
+extern "C" int hesic_conv2d_hilo_variant(const hesic_conv_desc* d, int products, int gdn, int* bm_bn_bk_ksplit) {
+    HESIC_CHECK_ARG(d && bm_bn_bk_ksplit, "conv2d_hilo_variant: null pointer");
+    HESIC_CHECK_ARG(products >= 1 && products <= 3 && (gdn == 0 || gdn == 3 || gdn == 4),
+                    "conv2d_hilo_variant: products must be 3, 2 or 1 (the hilo_out form), gdn 0, 3 or 4");
+    HESIC_CHECK_ARG(products != 1 || gdn, "conv2d_hilo_variant: the one-product form exists with the fused (I)GDN only");
+    HESIC_CHECK_ARG(d->dtype == HESIC_H16, "conv2d_hilo_variant: 16-bit storage");
+    IgemmOpts o;
+    o.hilo = products == 3 ? 1 : (products == 2 ? 2 : 0);
+    o.gdn_mode = gdn;
+    o.y_hilo = (products != 1 && !gdn) ? 1 : 0;
+    o.assume_ws = true;                      // as the size query: the wrappers hand the plain launch the workspace it asks for
+    IgemmPlan pl;
+    if (int rc = igemm_plan(d, o, pl)) return rc;
+    bm_bn_bk_ksplit[0] = pl.variant[0]; bm_bn_bk_ksplit[1] = pl.variant[1]; bm_bn_bk_ksplit[2] = pl.variant[2]; bm_bn_bk_ksplit[3] = pl.ksplit;
+    return 0;
+}

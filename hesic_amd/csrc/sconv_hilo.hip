@@ -33,14 +33,18 @@ __device__ __forceinline__ void split2_img(float p, float q, uint32_t& hi, uint3
     hi = pack_h2_raw(p, q);
     lo = pack_h2_raw(sub_h2_lo(p, hi), sub_h2_hi(q, hi));
 }
-// fp32 -> 16-bit terms whose sum is the value to ~2^-22 (binary16: two terms, bfloat16: three)
-constexpr int H16_TERMS = HESIC_H16_IS_F16 ? 2 : 3;
+// fp32 -> three 16-bit terms a, b, c with v = a + b + c * H16_TERM3_UNIT to ~2^-24.  binary16: the third term is carried times 2^14 against a
+// B entry of 2^-14 (the smallest normal half: the product is exact in the fp32 accumulator) -- a beta' * 2^-6 below binary16's subnormal
+// range (beta' = 1e-6, GDN's lower bound) is then still a normal third term instead of 0, which left the norm of an all-zero pixel at 0
+// and its output at 0 * rsqrt(0)
+constexpr float H16_TERM3_SCALE = HESIC_H16_IS_F16 ? 16384.f : 1.f;
+constexpr uint32_t H16_TERM3_UNIT = HESIC_H16_IS_F16 ? 0x0400u : (H16_ONE_PAIR & 0xffffu);       // 2^-14 | 1.0
 __device__ __forceinline__ void terms3(float v, uint32_t& t01, uint32_t& t2) {
     const uint32_t a = pack_h2_raw(h16_clamp(v), 0.f) & 0xffffu;
     const float r1 = h16_clamp(v) - h2f_lo(a);
     const uint32_t b = pack_h2_raw(r1, 0.f) & 0xffffu;
     t01 = a | (b << 16);
-    t2 = H16_TERMS == 3 ? (pack_h2_raw(r1 - h2f_lo(b), 0.f) & 0xffffu) : 0u;
+    t2 = pack_h2_raw((r1 - h2f_lo(b)) * H16_TERM3_SCALE, 0.f) & 0xffffu;
 }
 
 // OUT1 = 1: the output leaves as ONE 16-bit value per channel (128 channels per pixel; half the stores) -- for a consumer that multiplies
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void n2w_gdn_hilo_kernel(const HAr
             terms3(ev * H16_SQ_SCALE, ce01[i], ce2[i]);     // the output v * rsqrt(norm) is unchanged, the squares need no scaling multiply
             if (fh) { cb01[i] = cb2[i] = ce01[i] = ce2[i] = 0u; }
         }
-        ones_b = u32x4{H16_ONE_PAIR, H16_ONE_PAIR & 0xffffu, 0u, 0u};
+        ones_b = u32x4{H16_ONE_PAIR, H16_TERM3_UNIT, 0u, 0u};
     }
     [[maybe_unused]] int it_dbg = -1;
     for (; tile < ntiles; tile += tstride) {
@@ -305,7 +309,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void n2w_gdn_hilo_kernel(const HAr
         }
         N2W_T(4);
         N2W_T(5);
-        // y = v * rsqrt(nrm) (GDN) / v * sqrt(nrm) (IGDN) in fp32, kept in acc
+        // y = v * rsqrt(nrm) (GDN) / v * sqrt(nrm) (IGDN) in fp32, kept in acc.  OUT1 holds v * sqrt(H16_SQ_SCALE) and nrm * H16_SQ_SCALE: the
+        // factors cancel in GDN's quotient and multiply in IGDN's product, which is therefore unscaled (a power of two: exact; 1 in the bfloat16 build)
+        constexpr float INV_UNSCALE = OUT1 ? H16_SQ_UNSCALE : 1.f;
         if constexpr (DYN_SQ) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -319,7 +325,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void n2w_gdn_hilo_kernel(const HAr
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] *= INV ? __builtin_amdgcn_sqrtf(nrm[i][r]) : __builtin_amdgcn_rsqf(nrm[i][r]);
+            for (int r = 0; r < 16; ++r) acc[i][r] *= INV ? __builtin_amdgcn_sqrtf(nrm[i][r]) * INV_UNSCALE : __builtin_amdgcn_rsqf(nrm[i][r]);
         N2W_T(6);
         if constexpr (!EARLY_REQ) {
             // the next tile's rows are requested here: `raw` (48 registers) is then not live across the MFMA phases, and the loads have

@@ -1136,14 +1136,17 @@ class PackedN2wHiLo:
     def __init__(self):
         self._hit = {}
 
-    def get(self, weight, gamma, out1=False):
-        """``out1``: the image of the kernel's single-output form (w rounded with error feedback over the taps, lo halves unused)."""
+    def get(self, weight, gamma, out1=False, inverse=False):
+        """``out1``: the image of the kernel's single-output form (w rounded with error feedback over the taps, lo halves unused).
+        ``inverse``: the image for an IGDN launch -- never scaled: GDN's quotient is invariant under the binary16 weight scaling, IGDN's
+        product v sqrt(n) is not (it would come out times 4^s)."""
         tag = (weight.data_ptr(), weight._version, gamma.data_ptr(), gamma._version, _cache_epoch)
-        hit = self._hit.get(out1)
+        inverse = bool(inverse) and not out1
+        hit = self._hit.get((out1, inverse))
         if hit is not None and hit[0] == tag:
             return hit[1]
         img = torch.empty(128 * 1024, dtype=torch.uint8, device=weight.device)
-        sh = 0 if out1 else _pair_weight_shift(weight.detach().float())
+        sh = 0 if (out1 or inverse) else _pair_weight_shift(weight.detach().float())
         if sh:
             # pair form, binary16: weights times 2^s in the image (normal lo halves); sconv_gdn_hilo then passes bias 2^s and beta' 4^s
             L.call("hesic_sconv_pack_weight_image_hilo_scaled", L.ptr(_c(weight)), L.ptr(_c(gamma)), float(2 ** sh), L.ptr(img), L.stream())
@@ -1152,7 +1155,7 @@ class PackedN2wHiLo:
                    L.ptr(img), L.stream())
         img.hesic_wscale = float(2 ** sh)
         img.hesic_scaled = {}                              # (tensor address, version) -> the scaled copy of bias / beta'
-        self._hit[out1] = (tag, img)
+        self._hit[(out1, inverse)] = (tag, img)
         return img
 
 
@@ -1167,6 +1170,8 @@ def sconv_gdn_hilo(x, image, bias, beta_packed, inverse, out1=False):
     ``out1``: the same arithmetic, but the output is ONE 16-bit value per channel, (B, 128, H/2, W/2)."""
     L.require_cuda(x)
     wsc = getattr(image, "hesic_wscale", 1.0)
+    if wsc != 1.0 and inverse:
+        raise ValueError("sconv_gdn_hilo: an IGDN launch needs the unscaled weight image (PackedN2wHiLo.get(..., inverse=True))")
     if wsc != 1.0:
         def scaled(t, f):
             if t is None:

@@ -590,7 +590,7 @@ def gdn(mod, x):
                         t = Fn.sconv_gdn_hilo(src, cv._hl1.get(w, mod.gamma, out1=True), cv.bias, bp, mod.inverse, out1=True)
                         setattr(t, C2_TAG, True)
                         return t
-                    t = Fn.sconv_gdn_hilo(src, cv._hl1.get(w, mod.gamma), cv.bias, bp, mod.inverse)
+                    t = Fn.sconv_gdn_hilo(src, cv._hl1.get(w, mod.gamma, inverse=mod.inverse), cv.bias, bp, mod.inverse)
                     return value(None, pairs=t)
                 return _smooth(cv.run_gdn(src, mod))
             if sn is not None and sn.pair_route() and _hilo_capable(cv, n.transposed):

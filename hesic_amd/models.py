@@ -357,7 +357,7 @@ class Encoder1(nn.Module):
             lo, y = self.g_a_conv4.run_hilo(t, out="both", out_abs=lo_abs, products=np_)
             return Fn.HiLo((lo, self.g_a_conv4.weight.shape[0])), y
         if fused1:
-            t = Fn.sconv_gdn_hilo(x, self._hl1[2].get(c1.weight, g1.gamma), c1.bias, bp, g1.inverse)       # conv + GDN in one kernel
+            t = Fn.sconv_gdn_hilo(x, self._hl1[2].get(c1.weight, g1.gamma, inverse=g1.inverse), c1.bias, bp, g1.inverse)       # conv + GDN in one kernel
             if Fn.analysis_precision() == "x2":
                 # pairs everywhere, TWO products per MAC: x pairs x single error-feedback weights (no w_lo term)
                 p2, p3, p4 = X2_LAYERS

@@ -191,6 +191,11 @@ int hesic_im2col_hilo(const float* x, const int64_t x_strides[4], int B, int C, 
 /* Which kernel instantiation hesic_conv2d_forward picks for `d` (for profiling / roofline accounting):
  * out[0..3] = {pixel tile BM, cout tile BN, K step BK, 1 if the LDS-DMA (bf16) kernel else 0}.        */
 int hesic_conv2d_variant(const hesic_conv_desc* d, int* bm_bn_bk_glds);
+/* The same for a pair launch, whose options differ from the defaults hesic_conv2d_variant plans with.  products: 3 (hesic_conv2d_forward_hilo),
+ * 2 (_hilo_w1) or 1 (hesic_conv2d_gdn_forward_hilo_out: single operands, pair epilogue); gdn: 0 (plain; planned with the workspace
+ * hesic_conv2d_hilo_ws_bytes names), 3 (GDN) or 4 (IGDN).  d->Cin / d->Cout are the logical channel counts.  Host arithmetic, no HIP call.
+ * out[0..3] = {pixel tile BM, cout tile BN, K step BK, K slices}.                                                                    */
+int hesic_conv2d_hilo_variant(const hesic_conv_desc* d, int products, int gdn, int* bm_bn_bk_ksplit);
 
 /* deconv() (compressai/models/utils.py:112-118; g_s of ywz/mywork/newnet1.py:603-624, and the data gradient of the stride-2 analysis
  * convs): a transposed stride-2 layer is four stride-1 output phases.  By default (mode 1) hesic_conv2d_forward / _gdn_forward[_train]
@@ -267,7 +272,8 @@ int hesic_sconv2d_gdn_forward_hilo(const hesic_sconv_desc* d, const float* x, co
  * image_hilo must come from hesic_sconv_pack_weight_image_hilo_out1 (same 128 KB layout; its lo halves are not read).               */
 /* Pair form with the conv weights packed times `wscale` (a power of two): in the binary16 build the lo half of a weight of 0.02 is a subnormal
  * half (the pair then carries 2^-20 instead of 2^-22); with wscale = 2^s the caller hands hesic_sconv2d_gdn_forward_hilo bias * 2^s and
- * beta_packed * 4^s -- GDN's output is unchanged (v / sqrt(beta' + sum gamma' v^2) is invariant under v -> 2^s v, beta' -> 4^s beta').        */
+ * beta_packed * 4^s -- GDN's output is unchanged (v / sqrt(beta' + sum gamma' v^2) is invariant under v -> 2^s v, beta' -> 4^s beta').
+ * inverse == 0 only: IGDN's product v sqrt(.) would come out times 4^s, so an IGDN launch takes the unscaled image.                              */
 int hesic_sconv_pack_weight_image_hilo_scaled(const float* w, const float* gamma, float wscale, void* image, void* stream);
 int hesic_sconv_pack_weight_image_hilo_out1(const float* w, const float* gamma, void* image_hilo, void* stream);
 int hesic_sconv2d_gdn_forward_hilo_out1(const hesic_sconv_desc* d, const float* x, const void* image_hilo, const float* bias,

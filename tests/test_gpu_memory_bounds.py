@@ -1007,7 +1007,8 @@ NOT_LAUNCHING = {
     "hesic_abi_version": "library query", "hesic_h16_format": "library query", "hesic_last_error": "error string",
     "hesic_stream_synchronize": "host synchronisation", "hesic_memcpy_async": "a copy engine transfer, no kernel",
     "hesic_probe_mfma_loop": "a clock / throughput probe for profiling, no operator",
-    "hesic_conv2d_variant": "host query of the kernel variant", "hesic_conv2d_set_phase_fusion": "host switch",
+    "hesic_conv2d_variant": "host query of the kernel variant", "hesic_conv2d_hilo_variant": "host query of a pair launch's plan",
+    "hesic_conv2d_set_phase_fusion": "host switch",
     "hesic_conv2d_hilo_set_acc_scale": "host setting for the next hi/lo launch", "hesic_conv2d_wgrad_nsplit": "host query",
     "hesic_gdn_backward_partial_ok": "host query",
 }
