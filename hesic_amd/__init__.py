@@ -7,6 +7,7 @@ Layout
   compressai/      drop-in for the reference's ``compressai`` operator surface (import name: ``compressai``)
   geometry.py      warp_perspective / get_perspective_transform (the kornia calls of the path)
   models.py        HSIC / HSICJoint with the reference's module tree and state-dict keys
+  pair_coder.py    their real bit-streams: compress / decompress (+ _batch) as one mixin, the .bin payload container
   train.py         R-D loss, two-optimiser train step, data-parallel wrapper (RCCL)
   synthetic.py     deterministic weights / stereo pairs
 

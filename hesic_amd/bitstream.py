@@ -7,7 +7,7 @@ relies on -- magic, the mode bytes the cumulative-frequency tables depend on, ev
 Layout (little endian; ``varint`` = unsigned LEB128)::
 
     b"HSD\\x01" | b"HSJ\\x01"       magic + format version: the KIND of the blob -- "hesic" (HSD) or "joint" (HSJ, HESIC+)
-    mode        2 bytes            models.payload_mode_bytes() of the writer (as in the .bin payload of HSIC.compress)
+    mode        2 bytes            pair_coder.payload_mode_bytes() of the writer (as in the .bin payload of HSIC.compress)
     H, W        2 x uint16         image size (multiples of 64)
     M           uint16             latent channels
     cps         uint8              channels_per_stream
@@ -84,8 +84,8 @@ class _Reader:
 
 
 def _current_mode():
-    from . import models
-    return models.payload_mode_bytes()
+    from . import pair_coder
+    return pair_coder.payload_mode_bytes()
 
 
 def n_streams(flags, channels_per_stream):
@@ -143,7 +143,7 @@ def pack_pair(pair) -> bytes:
 
 def parse_pair(blob, mode=None):
     """Inverse of ``pack_pair``.  ``mode``: the two mode bytes the decoder runs in (default: this process').  Raises ``ValueError`` on a
-    wrong magic, a mode mismatch (the text of ``models.check_payload``), a truncated blob, lengths that do not add up and a CRC mismatch."""
+    wrong magic, a mode mismatch (the text of ``pair_coder.check_payload``), a truncated blob, lengths that do not add up and a CRC mismatch."""
     blob = bytes(blob)
     if len(blob) < len(MAGIC) or blob[:len(MAGIC)] not in (MAGIC, MAGIC_JOINT):
         raise ValueError("bitstream: not an .hsd blob of this package (bad magic; format 1 starts with b'HSD\\x01', HESIC+ blobs with "
@@ -154,8 +154,8 @@ def parse_pair(blob, mode=None):
     got = bytes(r.take(2, "mode bytes"))
     here = bytes(mode) if mode is not None else _current_mode()
     if got != here:
-        from . import models
-        raise ValueError(models.mode_mismatch_message(got, here))
+        from . import pair_coder
+        raise ValueError(pair_coder.mode_mismatch_message(got, here))
     H, W, M, cps = struct.unpack("<HHHB", r.take(7, "size header"))
     if H == 0 or W == 0 or M == 0 or cps == 0 or cps > M:
         raise ValueError(f"bitstream: header fields out of range ({H}x{W}, {M} channels, {cps} per stream)")

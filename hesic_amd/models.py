@@ -7,6 +7,7 @@ operators of ``hesic_amd.functional``: activations and ``abs`` ride in the conv 
 ``Upsample x4 + cat`` is one buffer, the Python double loop of ``spatial_pool2d`` is one reduction, the
 1x1 conv + softmax head is one kernel, and the duplicated ``warp(x1_hat)`` (:753 == :767) runs once.
 """
+import contextlib
 import math
 
 import torch
@@ -20,6 +21,8 @@ from . import _lib as L
 from . import functional as Fn
 from . import handover as _ho
 from .geometry import warp_perspective
+from .pair_coder import (PAYLOAD_MAGIC, TABLE_KERNEL_VERSION, Z_CODERS, PairCoder, _check_pair, _decompress_z, _nhwc_rows,  # noqa: F401 (re-exports)
+                         _round_latent, check_payload, describe_mode_bytes, mode_mismatch_message, payload_header, payload_mode_byte, payload_mode_bytes)
 
 RELU, LEAKY, NONE = L.ACT_RELU, L.ACT_LEAKY, L.ACT_NONE
 
@@ -31,12 +34,8 @@ CAT_FREE_EP = True          # module switch (HESIC+): False = torch.cat in front
 _side_streams = {}
 
 
-_RECORD = True
-
-
 def _rec(t, stream):
-    if _RECORD:
-        t.record_stream(stream)
+    t.record_stream(stream)
 
 
 def _side_stream(device, idx=0):
@@ -65,9 +64,7 @@ def metrics_stream(device):
 
 
 def hand_over(tensors, stream):
-    """Tell the caching allocator that ``tensors`` (an iterable) are also in use on ``stream`` (``Tensor.record_stream``); with
-    HESIC_NO_RECORD_STREAM set -- an UNSAFE debugging switch: a side-stream tensor can then be reused while a kernel on another
-    stream still reads it -- nothing is recorded."""
+    """Tell the caching allocator that ``tensors`` (an iterable) are also in use on ``stream`` (``Tensor.record_stream``)."""
     for t in tensors:
         _rec(t, stream)
 
@@ -587,20 +584,6 @@ class gmm_hyper_y2(nn.Module):
         return sigma, means, weights
 
 
-def _check_pair(x1, x2, h_matrix):
-    """Argument errors up front, with a usable message (the reference fails deep inside with a size mismatch: SURVEY.md 5)."""
-    if x1.dim() != 4 or x1.shape != x2.shape or x1.shape[1] != 3:
-        raise RuntimeError(f"HSIC.forward: x1 and x2 must be (B, 3, H, W) tensors of one shape, got {tuple(x1.shape)} and {tuple(x2.shape)}")
-    B, _, H, W = x1.shape
-    if B == 0:
-        raise RuntimeError("HSIC.forward: empty batch")
-    if H % 64 or W % 64:
-        raise RuntimeError(f"HSIC.forward: H and W must be multiples of 64 (the hyper path down-samples by 64), got {H}x{W}; "
-                           "zero-pad with hesic_amd.models.pad_to_multiple and crop the reconstructions")
-    if h_matrix.shape[-2:] != (3, 3) or h_matrix.dim() != 3 or h_matrix.shape[0] not in (1, B):
-        raise RuntimeError(f"HSIC.forward: h_matrix must be (B, 3, 3) (or (1, 3, 3)), got {tuple(h_matrix.shape)}")
-
-
 def _noise(nz, key, like, training):
     if not training:
         return None
@@ -616,129 +599,11 @@ def _quant(model, y, nz, key, training):
     return model._quantize(y, "dequantize")
 
 
-def _round_latent(model, y_hi):
-    """``_quantize(y, "dequantize")`` without means at inference: an fp32 latent of the bf16 mode is rounded in fp32 and
-    stored in the storage dtype (integers: exact) for the convs that read it."""
-    cdt = Fn.compute_dtype()
-    if y_hi.is_cuda and y_hi.dtype == torch.float32 and cdt != torch.float32:
-        return Fn.round_to(y_hi, cdt)
-    return model._quantize(y_hi, "dequantize")
-
-
-def _decompress_z(bottleneck, strings, size):
-    """``EntropyBottleneck.decompress`` for a batch.  The reference's form holds its (1, C, 1, 1) medians against an (N, C, H, W) index
-    map and refuses N > 1; here the medians are expanded over the batch and the strings go through ``EntropyModel.decompress`` in one
-    call (each string is its own rANS stream, the values are those of N single calls)."""
-    if len(strings) == 1:
-        return bottleneck.decompress(strings, size)
-    from .compressai.entropy_models.entropy_models import EntropyModel
-    shape = (len(strings), bottleneck._quantized_cdf.size(0), int(size[0]), int(size[1]))
-    medians = bottleneck._medians().detach().view(1, -1, 1, 1).expand(shape[0], -1, -1, -1)
-    return EntropyModel.decompress(bottleneck, list(strings), bottleneck._build_indexes(shape), medians)
-
-
-Z_CODERS = ("host", "device")
-
-
-def _check_z_coder(who, z_coder):
-    if z_coder not in Z_CODERS:
-        raise ValueError(f'{who}: z_coder must be "host" or "device", got {z_coder!r}')
-    return z_coder == "device"
-
-
-def _code_z(bottleneck, z, device, cdt):
-    """The z side of one view in the analysis chain of ``compress_batch``: -> (strings, z_hat).  Host coder: the strings of
-    ``bottleneck.compress`` and what decoding them yields (two synchronising round trips).  Device coder (csrc/rans.hip): the same bytes
-    stay on the device as a pending (data, counts, status) triple for ``_read_z_strings``, z_hat comes from the symbols that were
-    coded, and nothing synchronises."""
-    if not device:
-        strings = bottleneck.compress(z)
-        return strings, _decompress_z(bottleneck, strings, z.size()[-2:]).to(cdt)
-    data, counts, status, z_hat = bottleneck.compress_device(z, cdt, launch_only=True)
-    return (data, counts, status), z_hat
-
-
-def _read_z_strings(who, pending):
-    """The pending device z strings of both views -> per view the list of B ``bytes``: one read of the counts and status words, one of
-    the bytes of both views."""
-    host = torch.cat([t for _d, counts, status in pending for t in (status, counts)]).cpu().tolist()
-    blocks, lens, pos = [], [], 0
-    for vi, (data, counts, _status) in enumerate(pending):
-        B = counts.numel()
-        Fn.rans_check_status(f"{who}: z string of view {vi + 1}", host[pos:pos + B])
-        lens.append(host[pos + B:pos + 2 * B])
-        blocks.append(data[:sum(lens[-1])])
-        pos += 2 * B
-    raw = torch.cat(blocks).cpu().numpy().tobytes()
-    out, pos = [], 0
-    for ls in lens:
-        strings = []
-        for n in ls:
-            strings.append(raw[pos:pos + n])
-            pos += n
-        out.append(strings)
-    return out
-
-
-def _decode_z_device(who, bottlenecks, per_view, zs, dev, cdt):
-    """The z strings of both views of a batch, uploaded in one copy and decoded on the device: -> (z1_hat, z2_hat, status) with the
-    per-stream status words of both launches for ``Fn.rans_check_status`` at the end of the call (no synchronisation here).  The lengths
-    are validated on the host first."""
-    strings = [list(per_view[vi][2]) for vi in range(2)]
-    for vi in range(2):
-        for b, s_ in enumerate(strings[vi]):
-            if len(s_) < 8 or len(s_) % 4:
-                raise ValueError(f"{who}: the z string of pair {b}, view {vi + 1} has {len(s_)} bytes: not whole 32-bit words of a rANS stream")
-    buf = torch.frombuffer(bytearray(b"".join(strings[0] + strings[1])), dtype=torch.uint8).to(dev)
-    cut = sum(len(s_) for s_ in strings[0])
-    outs = [bottlenecks[vi].decompress_device(part, [len(s_) for s_ in strings[vi]], zs, cdt, check=False)
-            for vi, part in enumerate((buf[:cut], buf[cut:]))]
-    return outs[0][0], outs[1][0], torch.cat([outs[0][1], outs[1][1]])
-
-
-def _batch_blobs(who, kind, blobs, h_matrix, M):
-    """The host-side validation of ``decompress_batch`` (both codecs), before anything is launched: every blob parses
-    (``bitstream.parse_pair``), is of ``kind``, and they agree on size and channels_per_stream; alphabets and channel lists are what the
-    device coder takes.  Returns (B, H, W, cps, per view (minmax, channels, z strings, stream bytes back to back, (B, S) lengths))."""
-    from . import bitstream
-    blobs = list(blobs)
-    if not blobs:
-        raise ValueError(f"{who}: no blobs")
-    pairs = [bitstream.parse_pair(bl) for bl in blobs]
-    for p in pairs:
-        bitstream.require_kind(p, kind, who)
-    B, p0 = len(pairs), pairs[0]
-    H, W, cps = p0["height"], p0["width"], p0["channels_per_stream"]
-    for p in pairs:
-        if (p["height"], p["width"]) != (H, W):
-            raise ValueError(f"{who}: all blobs of one call must have the same size, got {H}x{W} and {p['height']}x{p['width']}; "
-                             "decode each size in a call of its own")
-        if p["channels_per_stream"] != cps:
-            raise ValueError(f"{who}: all blobs of one call must have the same channels_per_stream")
-        if p["channels"] != M:
-            raise ValueError(f"{who}: the blob codes {p['channels']} latent channels, this model has {M}")
-    if H % 64 or W % 64:
-        raise ValueError(f"{who}: the header's size {H}x{W} is not a multiple of 64")
-    per_view = []
-    for vi in range(2):
-        vs = [p["views"][vi] for p in pairs]
-        minmax = [v["minmax"] for v in vs]
-        channels = [[c for c, f in enumerate(v["flags"]) if f] for v in vs]
-        Fn.rc_check(minmax, channels, M)                   # alphabets beyond the kernels' limit: refused here
-        S = (M + cps - 1) // cps
-        counts = [[len(s) for s in v["streams"]] + [0] * (S - len(v["streams"])) for v in vs]
-        per_view.append((minmax, channels, [v["z"] for v in vs], b"".join(s for v in vs for s in v["streams"]), counts))
-    if h_matrix.dim() != 3 or h_matrix.shape[-2:] != (3, 3) or h_matrix.shape[0] not in (1, B):
-        raise ValueError(f"{who}: h_matrix must be ({B}, 3, 3) (or (1, 3, 3)), got {tuple(h_matrix.shape)}")
-    if not h_matrix.is_cuda:
-        raise RuntimeError(f"{who}: the device range coder needs h_matrix on a ROCm device (no CPU fallback)")
-    return B, H, W, cps, per_view
-
-
 # --------------------------------------------------------------------------------------------- HESIC
-class HSIC(StereoCompressionModel):
-    """HESIC (reference ``HSIC``, ywz/mywork/newnet1.py:696-783)."""
+class HSIC(PairCoder, StereoCompressionModel):
+    """HESIC (reference ``HSIC``, ywz/mywork/newnet1.py:696-783).  compress / decompress / compress_batch / decompress_batch: ``PairCoder``."""
     _LO_ABS = True            # encode_hyper reads |y| (newnet1.py:434)
+    _CODER, _PAIR_WHO, _BLOB_KIND = "HSIC", "HSIC.compress", "hesic"
 
     def __init__(self, N=128, M=192, K=5, **kwargs):
         super().__init__(entropy_bottleneck_channels=N, **kwargs)
@@ -780,12 +645,44 @@ class HSIC(StereoCompressionModel):
 
 
     # ---------------------------------------------------------------------------------------- real bit-stream
-    # HSIC.compress / decompress of the reference (ywz/mywork/newnet1.py:823-1073, :1076-1273).  Same
-    # flow and the same header file; the per-pixel Python loops of the reference are one HIP launch per view for the
-    # cumulative-frequency tables (hesic_gmm_cdf) + one pass of the host range coder.  The .bin payload is coded by
-    # libhesic_host's own carry-less range coder: the reference's `range_coder` package is third party, absent and
-    # unpinned, so byte-compatibility of that file is not claimed (round trips are exact).  Batch size 1, like the reference.
+    # HESIC's side of ``PairCoder`` (reference HSIC.compress / decompress: ywz/mywork/newnet1.py:823-1073, :1076-1273):
+    # the per-pixel Python loops of the reference are one HIP launch per view for the cumulative-frequency tables (hesic_gmm_cdf) + one
+    # pass of the host range coder; the batched calls code a view's y in one device encode / decode (csrc/codec.hip).
     _CDF_CHUNK_BYTES = 256 << 20
+
+    def _hyper_analysis(self, which, y_lo):
+        return (self._h_a1 if which == 1 else self._h_a2).latent(y_lo)
+
+    def _entropy_params(self, which, z_hat, y_hat, extra):
+        """The mixture triple (scales, means, weights)."""
+        return self._h_s1(z_hat, hi=True) if which == 1 else self._h_s2(z_hat, extra, hi=True)
+
+    def _y_quantiser(self, which):
+        return self.gaussian1 if which == 1 else self.gaussian2
+
+    def _encode_y(self, enc, which, y_hat, gmm, minmax, channels, order):
+        for _ch, sym, cdf in self._cdf_chunks(gmm, channels, minmax, self._y_quantiser(which)._bound(), y_hat):
+            enc.encode(sym, cdf)
+
+    def _decode_y(self, dec, which, z_hat, extra, minmax, channels, yh, yw, order):
+        import numpy as np
+        gmm = self._entropy_params(which, z_hat, None, extra)
+        y_hat = torch.zeros((1, self.M, yh, yw), dtype=torch.float32)
+        for ch, _sym, cdf in self._cdf_chunks(gmm, channels, minmax, self._y_quantiser(which)._bound()):
+            sym = dec.decode(cdf).reshape(len(ch), yh, yw)
+            y_hat[0, ch] = torch.from_numpy(sym.astype(np.float32) - minmax)
+        return y_hat.to(z_hat.device, Fn.compute_dtype()).contiguous(memory_format=torch.channels_last)
+
+    def _rc_encode(self, which, y_hat, gmm, minmax, channels, cps, order):
+        return Fn.gmm_rc_encode(gmm[0], gmm[1], gmm[2], y_hat, minmax, channels, self.K, cps, self._y_quantiser(which)._bound())
+
+    def _rc_decode(self, which, z_hat, extra, view, cps, yh, yw):
+        gmm = self._entropy_params(which, z_hat, None, extra)
+        minmax, channels, _z, data, counts = view
+        dev = z_hat.device
+        data = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.zeros(0, dtype=torch.uint8, device=dev)
+        return Fn.gmm_rc_decode(gmm[0], gmm[1], gmm[2], minmax, channels, self.K, data, counts, Fn.compute_dtype(), cps,
+                                self._y_quantiser(which)._bound())
 
     def _cdf_chunks(self, gmm, channels, minmax, scale_bound, y_hat=None):
         """(channels, symbols | None, cdf) numpy chunks in the reference's coding order: channel-major, rows, columns."""
@@ -802,205 +699,6 @@ class HSIC(StereoCompressionModel):
             if y_hat is not None:
                 sym = (y_hat[0, ch].float().cpu().numpy().astype(np.int64) + minmax).reshape(-1).astype(np.int32)
             yield ch, sym, cdf
-
-    def _analysis(self, x1, x2, h_matrix, device_z=False):
-        size = (x1.shape[-2], x1.shape[-1])
-        cdt = Fn.compute_dtype()
-        y1_lo, y1 = self.encoder1.latent(x1, exact=True, lo_abs=self._LO_ABS)
-        z1 = self._h_a1.latent(y1_lo)
-        z1_strings, z1_hat = _code_z(self.entropy_bottleneck1, z1, device_z, cdt)
-        gmm1 = self._h_s1(z1_hat, hi=True)
-        y1_hat = _round_latent(self.gaussian1, y1)
-        x1_hat = self.decoder1(y1_hat)
-        x1_warp = warp_perspective(x1, h_matrix, size)
-        y2_lo, y2 = self.encoder2.latent(x1_warp, x2, exact=True, lo_abs=self._LO_ABS)
-        z2 = self._h_a2.latent(y2_lo)
-        z2_strings, z2_hat = _code_z(self.entropy_bottleneck2, z2, device_z, cdt)
-        x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
-        y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
-        gmm2 = self._h_s2(z2_hat, y1_hat_w, hi=True)
-        y2_hat = _round_latent(self.gaussian2, y2)
-        return (y1_hat, z1_hat, z1_strings, gmm1), (y2_hat, z2_hat, z2_strings, gmm2)
-
-    def compress(self, x1, x2, h_matrix, output_name, output_path="", device=None):
-        import os
-        import time
-        import numpy as np
-        from ._host import RangeEncoder
-        if x1.shape[0] != 1:
-            raise ValueError("HSIC.compress codes one stereo pair per call (batch size 1, as the reference)")
-        if self.entropy_bottleneck1._offset.numel() == 0:
-            self.update()
-        with torch.no_grad():
-            v1, v2 = self._analysis(x1, x2, h_matrix)
-        out1 = os.path.join(output_path, str(output_name) + ".npz")      # the reference's name for its raw header file
-        out2 = os.path.join(output_path, str(output_name) + ".bin")
-        head = bytearray(np.array(x1.shape[2:], dtype=np.uint16).tobytes())
-        enc = RangeEncoder()
-        start = time.time()
-        for (y_hat, _z_hat, z_strings, gmm), gauss in ((v1, self.gaussian1), (v2, self.gaussian2)):
-            yi = y_hat[0].float()
-            flag = (yi.abs().sum(dim=(1, 2)) > 0).cpu().numpy().astype(np.uint8)
-            minmax = int(max(float(yi.abs().max()), 1.0))
-            if len(z_strings[0]) > 65535 or minmax > 32767:
-                raise ValueError("HSIC.compress: z string longer than the uint16 header field or latent range beyond the table kernel's 32767")
-            head += np.array([len(z_strings[0]), minmax], dtype=np.uint16).tobytes()
-            head += np.packbits(flag).tobytes()
-            head += z_strings[0]
-            channels = [int(c) for c in np.nonzero(flag)[0]]
-            for _ch, sym, cdf in self._cdf_chunks(gmm, channels, minmax, gauss._bound(), y_hat):
-                enc.encode(sym, cdf)
-        payload = payload_header() + enc.finish()
-        with open(out1, "wb") as f:
-            f.write(bytes(head))
-        with open(out2, "wb") as f:
-            f.write(payload)
-        num_pixels = x1.shape[2] * x1.shape[3] * 2
-        return {"bpp_real": (len(head) + len(payload)) * 8 / num_pixels, "bpp_side": len(head) * 8 / num_pixels,
-                "enctime": time.time() - start, "y1_hat": v1[0], "y2_hat": v2[0], "z1_hat": v1[1], "z2_hat": v2[1]}
-
-    def decompress(self, x1, x2, h_matrix, output_name, output_path="", device=None):
-        """x1 / x2 are unused (the reference only reads their size, which the header carries); kept for its signature."""
-        import os
-        import time
-        import numpy as np
-        from ._host import RangeDecoder
-        if self.entropy_bottleneck1._offset.numel() == 0:
-            self.update()
-        dev = h_matrix.device
-        with open(os.path.join(output_path, str(output_name) + ".npz"), "rb") as f:
-            blob = f.read()
-        pos = 4
-        x_shape = np.frombuffer(blob[:4], dtype=np.uint16).astype(int)
-        views = []
-        for _ in range(2):
-            length, minmax = (int(v) for v in np.frombuffer(blob[pos:pos + 4], dtype=np.uint16))
-            pos += 4
-            flag = np.unpackbits(np.frombuffer(blob[pos:pos + (self.M + 7) // 8], dtype=np.uint8))[:self.M]
-            pos += (self.M + 7) // 8
-            views.append((minmax, [int(c) for c in np.nonzero(flag)[0]], blob[pos:pos + length]))
-            pos += length
-        y_shape = x_shape // 16
-        z_shape = y_shape // 4
-        with open(os.path.join(output_path, str(output_name) + ".bin"), "rb") as f:
-            payload = f.read()
-        _, off = check_payload(payload)
-        dec = RangeDecoder(payload[off:])
-        start = time.time()
-        cdt = Fn.compute_dtype()
-        size = (int(x_shape[0]), int(x_shape[1]))
-
-        def decode_view(gmm, minmax, channels, gauss):
-            y_hat = torch.zeros((1, self.M, int(y_shape[0]), int(y_shape[1])), dtype=torch.float32)
-            for ch, _sym, cdf in self._cdf_chunks(gmm, channels, minmax, gauss._bound()):
-                sym = dec.decode(cdf).reshape(len(ch), int(y_shape[0]), int(y_shape[1]))
-                y_hat[0, ch] = torch.from_numpy(sym.astype(np.float32) - minmax)
-            return y_hat.to(dev, cdt).contiguous(memory_format=torch.channels_last)
-
-        with torch.no_grad():
-            zs = (int(z_shape[0]), int(z_shape[1]))
-            z1_hat = self.entropy_bottleneck1.decompress([views[0][2]], zs).to(dev, cdt)
-            z2_hat = self.entropy_bottleneck2.decompress([views[1][2]], zs).to(dev, cdt)
-            gmm1 = self._h_s1(z1_hat, hi=True)
-            y1_hat = decode_view(gmm1, views[0][0], views[0][1], self.gaussian1)
-            x1_hat = self.decoder1(y1_hat)
-            x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
-            y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
-            gmm2 = self._h_s2(z2_hat, y1_hat_w, hi=True)
-            y2_hat = decode_view(gmm2, views[1][0], views[1][1], self.gaussian2)
-            x2_hat = self.decoder2(y2_hat, x1_hat_warp)
-        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat,
-                "dectime": time.time() - start}
-
-    # ------------------------------------------------------------------------------- batched bit-stream, coded on the device
-    # The same flow for a whole batch, with the range coder on the GPU (csrc/codec.hip): per view one launch for the coding intervals of
-    # every latent of every image, one for the streams (one per ``channels_per_stream`` coded channels), one to compact them -- no table
-    # and no symbol of y leaves the device.  One self-contained blob per pair (hesic_amd/bitstream.py).  The z strings are coded by the host
-    # rANS coder (``z_coder="host"``, the default: z is quantised, copied to the host, coded one image at a time and decoded again for
-    # z_hat -- two synchronising round trips inside the analysis chain) or by the device rANS coder (``z_coder="device"``, csrc/rans.hip:
-    # the same bytes, no round trip; the z bytes are read back after the y streams).  Pairs are independent: blob i does not depend on what
-    # else is in the batch.
-    def compress_batch(self, x1, x2, h_matrix, channels_per_stream=1, z_coder="host"):
-        """(B, 3, H, W) pairs -> dict(blobs: one ``bytes`` per pair (``bitstream.pack_pair``), bpp_real: one figure per pair over its
-        2 H W pixels, y1_hat, y2_hat, z1_hat, z2_hat).  ``channels_per_stream``: coded channels per range-coder stream -- 1 gives the
-        shortest serial chains (fastest), larger values fewer stream terminations and lengths (smaller blobs).  An image whose latents
-        need an alphabet beyond the device coder's 1024 symbols raises ``ValueError``: code that pair with ``compress``.  ``z_coder``:
-        "host" or "device", who codes the z strings -- the blobs are the same bytes either way."""
-        from . import bitstream
-        _check_pair(x1, x2, h_matrix)
-        device_z = _check_z_coder("HSIC.compress_batch", z_coder)
-        if not x1.is_cuda:
-            raise RuntimeError("HSIC.compress_batch: the device range coder needs tensors on a ROCm device (no CPU fallback)")
-        cps = int(channels_per_stream)
-        if not 1 <= cps <= min(self.M, 255):
-            raise ValueError(f"HSIC.compress_batch: channels_per_stream must be in [1, {min(self.M, 255)}], got {channels_per_stream}")
-        if self.entropy_bottleneck1._offset.numel() == 0:
-            self.update()
-        B, _, H, W = x1.shape
-        with torch.no_grad():
-            v1, v2 = self._analysis(x1, x2, h_matrix, device_z)
-            # one small device -> host read: per image, view and channel max |y_hat| (minmax and the flags follow from it)
-            peak = torch.stack([v[0].float().abs().amax(dim=(2, 3)) for v in (v1, v2)]).cpu()
-            views = [[None, None] for _ in range(B)]
-            for vi, ((y_hat, _z_hat, z_strings, gmm), gauss) in enumerate(((v1, self.gaussian1), (v2, self.gaussian2))):
-                flags = (peak[vi] > 0).tolist()
-                minmax = [int(max(float(peak[vi, b].max()), 1.0)) for b in range(B)]
-                channels = [[c for c, f in enumerate(flags[b]) if f] for b in range(B)]
-                data, counts = Fn.gmm_rc_encode(gmm[0], gmm[1], gmm[2], y_hat, minmax, channels, self.K, cps, gauss._bound())
-                data, counts = data.cpu().numpy().tobytes(), counts.cpu().tolist()
-                pos = 0
-                for b in range(B):
-                    streams = []
-                    for n in counts[b][:bitstream.n_streams(flags[b], cps)]:
-                        streams.append(data[pos:pos + n])
-                        pos += n
-                    views[b][vi] = {"minmax": minmax[b], "flags": tuple(int(f) for f in flags[b]), "z": None if device_z else z_strings[b],
-                                    "streams": streams}
-            if device_z:
-                for vi, strings in enumerate(_read_z_strings("HSIC.compress_batch", (v1[2], v2[2]))):
-                    for b in range(B):
-                        views[b][vi]["z"] = strings[b]
-        blobs = [bitstream.pack_pair({"mode": payload_mode_bytes(), "height": H, "width": W, "channels": self.M, "channels_per_stream": cps,
-                                      "views": views[b]}) for b in range(B)]
-        return {"blobs": blobs, "bpp_real": [len(bl) * 8 / (H * W * 2) for bl in blobs],
-                "y1_hat": v1[0], "y2_hat": v2[0], "z1_hat": v1[1], "z2_hat": v2[1]}
-
-    def decompress_batch(self, blobs, h_matrix, z_coder="host"):
-        """``blobs``: what ``compress_batch`` returned, in any grouping and order (all of one image size); ``h_matrix`` (B, 3, 3) the
-        matching homographies.  Everything is validated on the host before the first launch.  ``z_coder``: "host" decodes the 2 B z
-        strings on the host before the first launch, "device" uploads them in one copy and decodes them there; either reads the blobs of
-        either encoder setting."""
-        device_z = _check_z_coder("HSIC.decompress_batch", z_coder)
-        B, H, W, cps, per_view = _batch_blobs("HSIC.decompress_batch", "hesic", blobs, h_matrix, self.M)
-        if self.entropy_bottleneck1._offset.numel() == 0:
-            self.update()
-        dev, cdt, size = h_matrix.device, Fn.compute_dtype(), (H, W)
-        zs = (H // 64, W // 64)
-
-        def decode_view(gmm, view, gauss):
-            minmax, channels, _z, data, counts = view
-            data = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.zeros(0, dtype=torch.uint8, device=dev)
-            return Fn.gmm_rc_decode(gmm[0], gmm[1], gmm[2], minmax, channels, self.K, data, counts, cdt, cps, gauss._bound())
-
-        with torch.no_grad():
-            z_status = None
-            if device_z:
-                z1_hat, z2_hat, z_status = _decode_z_device("HSIC.decompress_batch", (self.entropy_bottleneck1, self.entropy_bottleneck2),
-                                                            per_view, zs, dev, cdt)
-            else:
-                z1_hat = _decompress_z(self.entropy_bottleneck1, per_view[0][2], zs).to(dev, cdt)
-                z2_hat = _decompress_z(self.entropy_bottleneck2, per_view[1][2], zs).to(dev, cdt)
-            gmm1 = self._h_s1(z1_hat, hi=True)
-            y1_hat = decode_view(gmm1, per_view[0], self.gaussian1)
-            x1_hat = self.decoder1(y1_hat)
-            x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
-            y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
-            gmm2 = self._h_s2(z2_hat, y1_hat_w, hi=True)
-            y2_hat = decode_view(gmm2, per_view[1], self.gaussian2)
-            x2_hat = self.decoder2(y2_hat, x1_hat_warp)
-            if z_status is not None:
-                Fn.rans_check_status("HSIC.decompress_batch: z string", z_status.cpu())
-        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
 
     def _forward_eval(self, x1, x2, h_matrix, two_streams=True):
         """Inference schedule.  The chain that bounds the step is encoder1 -> round -> decoder1 -> warp -> {decoder2 | encoder1 ->
@@ -1081,21 +779,11 @@ class HSIC(StereoCompressionModel):
 
 
 # -------------------------------------------------------------------------------------------- HESIC+
-def _nhwc_rows(t):
-    """(1, C, H, W) map -> (H * W, C) rows, one per pixel (a view when the map is channels_last)."""
-    return t.permute(0, 2, 3, 1).reshape(t.shape[2] * t.shape[3], t.shape[1])
-
-
-# ---- the .bin payload container (this repository's own file: the reference's third-party `range_coder` is absent, DESIGN.md section 7).
-# A payload can only be decoded by a decoder that forms the SAME cumulative-frequency tables, bit for bit: they come out of the
-# hyper-synthesis (and, for view 2, the decoder1 -> warp -> encoder1 pass) run in the encoder's storage format.  Since round 4 every payload
-# starts with 4 magic bytes + one MODE byte naming what the tables depend on; a decoder in another mode raises instead of desynchronising.
 # A/B switch, OFF: g_a_conv3 / conv4 of "x3c2" on pairs x single error-feedback weights (hesic_conv2d_forward_hilo_w1, two products per pair).
 # Measured (round 4, same box, alternating runs): 3617 / 3586 pairs/s against 3582 / 3567 at three products (+0.7 %), flips 5.4e-4 vs 5.3e-4 at
 # 512^2 but 7.7e-4 vs 6.3e-4 on the 256^2 golden -- not worth a quarter of the margin to the 1e-3 bar
 X3C2_TWO_PRODUCT_TAIL = False
 X2_LAYERS = (2, 2, 2)          # "x2" mode (measured and not the default): products per MAC of g_a_conv2 / conv3 / conv4
-WAVEFRONT_GRAPHS = True      # module switch: False = round 3's per-group launches from Python
 # A/B switch: 1 = the device reads the decoded symbols from, and writes the tables into, pinned host memory itself (no copy nodes)
 WAVEFRONT_ZEROCOPY = True
 # A/B switch, off: 1 = the table launch of a group is the sixth node of its captured step (hesic_gmm_cdf_dyn: channel list and alphabet read on
@@ -1105,62 +793,6 @@ _CDF_WAVE_MAX = 1024          # csrc/entropy.hip: alphabets the wave-per-row tab
 # A/B switch: 1 = the C loop replays each group's recorded launches one by one instead of launching its graph
 WAVEFRONT_TAPE = True
 WAVEFRONT_C_LOOP = True      # module switch: False = the group loop in Python (six C calls per group)
-PAYLOAD_MAGIC = b"HSC\x03"               # format 3 (round 5: two mode bytes).  Format 2 (round 4) had one; format 1 (rounds 2-3) no header
-TABLE_KERNEL_VERSION = 2                  # bump when hesic_gmm_cdf / the table-producing launches change their arithmetic
-_MODE_BYTES = 2
-
-
-def payload_mode_bytes():
-    """Everything the cumulative-frequency tables depend on besides the weights (round 4's single byte left out the warp convention
-    and the summation-order switches, so a decoder differing in one of them passed the check and desynchronised on view 2).
-    byte 0 -- bits 0-1: storage format of the maps (0 fp32, 1 bfloat16, 2 float16); bit 2: error-feedback weight rounding on the
-    single-operand analysis launches (the third analysis pass feeds view 2's tables); bit 3: fp32 latents; bits 4-7: table-kernel version.
-    byte 1 -- bit 0: warp convention (``geometry.DEFAULT_ALIGN_CORNERS``: x1_hat_warp, hence round(encoder1(warp(x1_hat))), hence view 2's
-    tables); bit 1: split-K launches allowed (``Fn.SPLIT_K``); bit 2: grouped hyper-synthesis launches (``Fn.GROUP_HYPER``) -- both reorder
-    the fp32 sums of the hyper-synthesis; bits 3-4: analysis precision of the third pass' producer chain (0 x3, 1 x3c2, 2 x1, 3 x2: x1_hat is
-    decoded from y1_hat alone, but the mode is recorded so that a mismatch is reported rather than argued about)."""
-    from . import geometry as _geo
-    dt = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[Fn.compute_dtype()]
-    b0 = dt | (int(bool(Fn.SHAPED_WEIGHTS) and dt != 0) << 2) | (int(bool(Fn.FP32_LATENTS)) << 3) | (TABLE_KERNEL_VERSION << 4)
-    an = 0 if dt == 0 else {"x3": 0, "x3c2": 1, "x1": 2, "x2": 3}[Fn.analysis_precision()]
-    b1 = int(bool(_geo.DEFAULT_ALIGN_CORNERS)) | (int(bool(Fn.SPLIT_K)) << 1) | (int(bool(Fn.GROUP_HYPER)) << 2) | (an << 3)
-    return bytes([b0, b1])
-
-
-def payload_mode_byte():
-    """Byte 0 of ``payload_mode_bytes()`` (the round-4 name; tests and tools that look at the storage format use it)."""
-    return payload_mode_bytes()[0]
-
-
-def describe_mode_bytes(b):
-    b0, b1 = b[0], b[1]
-    return (f"{('float32', 'bfloat16', 'float16', '?')[b0 & 3]} maps, error-feedback analysis weights {'on' if b0 & 4 else 'off'}, "
-            f"fp32 latents {'on' if b0 & 8 else 'off'}, table kernels v{b0 >> 4}, warp align_corners={'True' if b1 & 1 else 'False'}, "
-            f"split-K {'on' if b1 & 2 else 'off'}, grouped hyper-synthesis {'on' if b1 & 4 else 'off'}, analysis {('x3', 'x3c2', 'x1', 'x2')[(b1 >> 3) & 3]}")
-
-
-def payload_header(extra=b""):
-    return PAYLOAD_MAGIC + payload_mode_bytes() + extra
-
-
-def mode_mismatch_message(mode, here):
-    """What a decoder in mode ``here`` says about a payload written in ``mode`` (the .bin payload and the .hsd container)."""
-    return (f"decompress: the payload was written with [{describe_mode_bytes(mode)}] but this process decodes with "
-            f"[{describe_mode_bytes(here)}]; the cumulative-frequency tables would differ in the last count and the range decoder "
-            "would desynchronise.  Select the writer's mode (hesic_amd.set_compute_dtype, set_analysis_precision, "
-            "geometry.use_reference_era_warp / HESIC_WARP_ALIGN_CORNERS, HESIC_SHAPED_WEIGHTS, HESIC_BF16_LATENTS, HESIC_NO_GROUP_HYPER)")
-
-
-def check_payload(payload, n_extra=0):
-    """Validate the container header; returns (extra bytes, offset of the range-coder stream)."""
-    n = len(PAYLOAD_MAGIC)
-    if len(payload) < n + _MODE_BYTES + n_extra or payload[:n] != PAYLOAD_MAGIC:
-        raise ValueError("decompress: the .bin payload does not start with this coder's format-3 header (a file written by rounds 2-4 of "
-                         "this package, or not one of its payloads): re-encode it -- the header names the mode the tables were formed in")
-    mode, here = bytes(payload[n:n + _MODE_BYTES]), payload_mode_bytes()
-    if mode != here:
-        raise ValueError(mode_mismatch_message(mode, here))
-    return payload[n + _MODE_BYTES:n + _MODE_BYTES + n_extra], n + _MODE_BYTES + n_extra
 
 
 def _seq3(seq, x, last_act=NONE):
@@ -1177,10 +809,12 @@ def _seq3_hi(seq, x):
     return seq[4].run_latent(seq[2].run(seq[0].run(x, act=LEAKY), act=LEAKY), want_lo=False)[1]
 
 
-class HSICJoint(StereoCompressionModel):
+class HSICJoint(PairCoder, StereoCompressionModel):
     """HESIC+ (reference ``HSIC`` of ywz/mywork/newnet1_joint.py:585-753): Minnen-style hyperprior +
-    masked-conv context model + 1x1 entropy-parameter nets + single Gaussian."""
+    masked-conv context model + 1x1 entropy-parameter nets + single Gaussian.  compress / decompress / compress_batch /
+    decompress_batch: ``PairCoder``."""
     _LO_ABS = False           # h_a reads y itself (newnet1_joint.py:611-617)
+    _CODER, _PAIR_WHO, _BLOB_KIND = "HSICJoint", "compress", "joint"
 
     def __init__(self, N=128, M=192, K=5, **kwargs):
         super().__init__(entropy_bottleneck_channels=N, **kwargs)
@@ -1313,13 +947,30 @@ class HSICJoint(StereoCompressionModel):
                 "likelihoods": {"y1": y1_lik, "y2": y2_lik, "z1": z1_lik, "z2": z2_lik}}
 
     # ---------------------------------------------------------------------------------------- real bit-stream
-    # compress / decompress of the reference's HESIC+ (ywz/mywork/newnet1_joint.py:793-1079, :1081-1321): same header
+    # HESIC+'s side of ``PairCoder`` (reference compress / decompress: ywz/mywork/newnet1_joint.py:793-1079, :1081-1321): same header
     # file as HESIC, y coded pixel by pixel in raster order (all non-zero channels of a pixel together) under a single
     # Gaussian whose (scale, mean) come from the hyper-decoder and the masked-conv context of the ALREADY CODED latents.
     # The encoder knows every latent, so it evaluates the context model for the whole map in one pass; the decoder walks
     # the map like the reference does (5x5 crop -> masked conv -> 1x1 entropy-parameter net -> tables -> decode -> write
     # back).  Both run their convs without split-K: the kernels then accumulate every output element in the same order
     # whatever the map size, which makes the decoder's per-pixel numbers bit-identical to the encoder's (tested).
+    @contextlib.contextmanager
+    def _coding(self):
+        with torch.no_grad(), Fn.no_split_k():
+            self.context_prediction1.weight.data *= self.context_prediction1.mask
+            self.context_prediction2.weight.data *= self.context_prediction2.mask
+            yield
+
+    def _hyper_analysis(self, which, y_lo):
+        return _seq3_hi(self.h_a1 if which == 1 else self.h_a2, y_lo)
+
+    def _entropy_params(self, which, z_hat, y_hat, extra):
+        """(scales, means), the context model evaluated on the whole map."""
+        return self._gauss_full(which, self._params_view(which, z_hat), y_hat, extra)
+
+    def _y_quantiser(self, which):
+        return self.gaussian_conditional1 if which == 1 else self.gaussian_conditional2
+
     def _params_view(self, which, z_hat):
         h_s = self.h_s1 if which == 1 else self.h_s2
         return _seq3(h_s, z_hat)
@@ -1363,17 +1014,6 @@ class HSICJoint(StereoCompressionModel):
         return _seq3_hi(ep, torch.cat(parts, 1).contiguous(memory_format=torch.channels_last)).chunk(2, 1)
 
     @staticmethod
-    def _header_view(y_hat, z_strings):
-        import numpy as np
-        yi = y_hat[0].float()
-        flag = (yi.abs().sum(dim=(1, 2)) > 0).cpu().numpy().astype(np.uint8)
-        minmax = int(max(float(yi.abs().max()), 1.0))
-        if len(z_strings[0]) > 65535 or minmax > 32767:
-            raise ValueError("compress: z string longer than the uint16 header field or latent range beyond the table kernel's 32767")
-        head = np.array([len(z_strings[0]), minmax], dtype=np.uint16).tobytes() + np.packbits(flag).tobytes() + z_strings[0]
-        return head, minmax, [int(c) for c in np.nonzero(flag)[0]]
-
-    @staticmethod
     def _wavefronts(H, W):
         """Pixels grouped by t = w + 3 h.  The 5x5 mask-'A' context of pixel (h, w) is rows h-2, h-1 (columns w-2 .. w+2) and
         (h, w-2), (h, w-1): every one of them has a smaller t, so the pixels of one group only depend on earlier groups and
@@ -1386,100 +1026,56 @@ class HSICJoint(StereoCompressionModel):
         cuts = np.flatnonzero(np.diff(t[order])) + 1
         return np.split(order.astype(np.int64), cuts)
 
-    def _coder_inputs(self, x1, x2, h_matrix, device_z=False):
-        """The encoder's side of the real bit-stream for B pairs, shared by ``compress`` and ``compress_batch`` (their streams must be formed
-        from the same numbers): per view (y_hat, z strings, z_hat, scales, means) with the context model evaluated on the whole maps.
-        Call it under ``torch.no_grad()`` and ``Fn.no_split_k()`` with the context masks applied to the weights."""
-        size = (x1.shape[-2], x1.shape[-1])
-        cdt = Fn.compute_dtype()
-        y1_lo, y1 = self.encoder1.latent(x1, exact=True, lo_abs=self._LO_ABS)
-        z1 = _seq3_hi(self.h_a1, y1_lo)
-        z1_strings, z1_hat = _code_z(self.entropy_bottleneck1, z1, device_z, cdt)
-        y1_hat = _round_latent(self.gaussian_conditional1, y1)
-        sc1, mu1 = self._gauss_full(1, self._params_view(1, z1_hat), y1_hat)
-        x1_hat = self.decoder1(y1_hat)
-        x1_warp = warp_perspective(x1, h_matrix, size)
-        y2_lo, y2 = self.encoder2.latent(x1_warp, x2, exact=True, lo_abs=self._LO_ABS)
-        z2 = _seq3_hi(self.h_a2, y2_lo)
-        z2_strings, z2_hat = _code_z(self.entropy_bottleneck2, z2, device_z, cdt)
-        x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
-        y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
-        y2_hat = _round_latent(self.gaussian_conditional2, y2)
-        sc2, mu2 = self._gauss_full(2, self._params_view(2, z2_hat), y2_hat, y1_hat_w)
-        return (y1_hat, z1_strings, z1_hat, sc1, mu1), (y2_hat, z2_strings, z2_hat, sc2, mu2)
-
     ORDER_RASTER, ORDER_WAVEFRONT = 0, 1
+    _ORDERS = {"raster": ORDER_RASTER, "wavefront": ORDER_WAVEFRONT}
+    _TIMES_ANALYSIS = True             # HSIC's timer starts behind the analysis, as the reference's does; this one has always started in front
+
+    def _order(self, order="wavefront"):
+        if order not in self._ORDERS:
+            raise ValueError('compress: order must be "raster" or "wavefront"')
+        return order, bytes([self._ORDERS[order]])
+
     _TABLE_BYTES = 256 << 20           # bound of one batch of cumulative-frequency tables (device buffer + its host copy)
 
-    def compress(self, x1, x2, h_matrix, output_name, output_path="", device=None, order="wavefront"):
-        """``order``: the sequence in which the pixels' symbols enter the range coder.  "raster" is the reference's (rows, then
-        columns; newnet1_joint.py:903-1040) and forces a decoder to walk the map pixel by pixel; "wavefront" (default) codes the
-        pixels group by group of ``_wavefronts`` so the decoder evaluates every group in one batch.  Same symbols, same
-        tables; the first payload byte says which (the payload is this repository's own range coder either way)."""
-        import os
-        import time
+    def _encode_y(self, enc, which, y_hat, params, minmax, channels, order):
         import numpy as np
-        from ._host import RangeEncoder
-        if x1.shape[0] != 1:
-            raise ValueError("compress codes one stereo pair per call (batch size 1, as the reference)")
-        if order not in ("raster", "wavefront"):
-            raise ValueError('compress: order must be "raster" or "wavefront"')
-        if self.entropy_bottleneck1._offset.numel() == 0:
-            self.update()
-        start = time.time()
-        with torch.no_grad(), Fn.no_split_k():
-            self.context_prediction1.weight.data *= self.context_prediction1.mask
-            self.context_prediction2.weight.data *= self.context_prediction2.mask
-            (y1_hat, z1_strings, z1_hat, sc1, mu1), (y2_hat, z2_strings, z2_hat, sc2, mu2) = self._coder_inputs(x1, x2, h_matrix)
-            head = bytearray(np.array(x1.shape[2:], dtype=np.uint16).tobytes())
-            enc = RangeEncoder()
-            bound = self.gaussian_conditional1._bound()
-            for y_hat, z_strings, sc, mu in ((y1_hat, z1_strings, sc1, mu1), (y2_hat, z2_strings, sc2, mu2)):
-                hv, minmax, channels = self._header_view(y_hat, z_strings)
-                head += hv
-                if not channels:
-                    continue
-                H, W = y_hat.shape[-2:]
-                n_tab = 2 * minmax + 2
-                if order == "raster":
-                    rows = max(1, self._TABLE_BYTES // (len(channels) * W * n_tab * 4))
-                    for r0 in range(0, H, rows):                     # row blocks keep the table buffers bounded
-                        r1 = min(H, r0 + rows)
-                        cdf = Fn.gmm_cdf_tables(sc[:, :, r0:r1], mu[:, :, r0:r1], None, channels, minmax, 1, scale_bound=bound)
-                        cdf = cdf.cpu().numpy().view(np.uint32).transpose(1, 2, 0, 3).reshape(-1, len(channels), n_tab)
-                        sym = y_hat[0, channels, r0:r1].float().cpu().numpy().astype(np.int64) + minmax
-                        sym = sym.transpose(1, 2, 0).reshape(-1, len(channels)).astype(np.int32)
-                        enc.encode(sym.reshape(-1), np.ascontiguousarray(cdf.reshape(-1, n_tab)))
-                else:
-                    # wavefront order: the pixels enter the coder group by group of equal t = w + 3 h.  Bands of whole groups, each at most
-                    # _TABLE_BYTES of tables: their (scale, mean) rows are gathered on the device, ONE table launch per band (the table
-                    # kernel is element-wise, so the numbers are those of the whole-map evaluation), one host copy -- host memory is
-                    # bounded by the band, whatever the image size or the latent range (round 3 built the whole map's tables at once)
-                    groups = self._wavefronts(H, W)
-                    cap = max(1, self._TABLE_BYTES // (len(channels) * n_tab * 4))
-                    sc_rows, mu_rows, y_rows = _nhwc_rows(sc), _nhwc_rows(mu), _nhwc_rows(y_hat)
-                    ch_t = torch.as_tensor(channels, device=y_hat.device)
-                    g0 = 0
-                    while g0 < len(groups):
-                        g1, P = g0, 0
-                        while g1 < len(groups) and (P == 0 or P + len(groups[g1]) <= cap):
-                            P += len(groups[g1])
-                            g1 += 1
-                        pix = torch.from_numpy(np.concatenate(groups[g0:g1])).to(y_hat.device)
-                        sc_r, mu_r = (t[pix].contiguous().t().reshape(1, self.M, 1, P) for t in (sc_rows, mu_rows))
-                        cdf = Fn.gmm_cdf_tables(sc_r, mu_r, None, channels, minmax, 1, scale_bound=bound)               # (C, 1, P, n)
-                        cdf = cdf.cpu().numpy().view(np.uint32).reshape(len(channels), P, n_tab).transpose(1, 0, 2)       # pixel-major
-                        sym = (y_rows[pix][:, ch_t].float().cpu().numpy().astype(np.int64) + minmax).astype(np.int32)      # (P, C)
-                        enc.encode(sym.reshape(-1), np.ascontiguousarray(cdf).reshape(-1, n_tab))
-                        g0 = g1
-        payload = payload_header(bytes([self.ORDER_WAVEFRONT if order == "wavefront" else self.ORDER_RASTER])) + enc.finish()
-        with open(os.path.join(output_path, str(output_name) + ".npz"), "wb") as f:
-            f.write(bytes(head))
-        with open(os.path.join(output_path, str(output_name) + ".bin"), "wb") as f:
-            f.write(payload)
-        num_pixels = x1.shape[2] * x1.shape[3] * 2
-        return {"bpp_real": (len(head) + len(payload)) * 8 / num_pixels, "bpp_side": len(head) * 8 / num_pixels,
-                "enctime": time.time() - start, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
+        if not channels:
+            return
+        sc, mu = params
+        bound = self.gaussian_conditional1._bound()
+        H, W = y_hat.shape[-2:]
+        n_tab = 2 * minmax + 2
+        if order == "raster":
+            rows = max(1, self._TABLE_BYTES // (len(channels) * W * n_tab * 4))
+            for r0 in range(0, H, rows):                     # row blocks keep the table buffers bounded
+                r1 = min(H, r0 + rows)
+                cdf = Fn.gmm_cdf_tables(sc[:, :, r0:r1], mu[:, :, r0:r1], None, channels, minmax, 1, scale_bound=bound)
+                cdf = cdf.cpu().numpy().view(np.uint32).transpose(1, 2, 0, 3).reshape(-1, len(channels), n_tab)
+                sym = y_hat[0, channels, r0:r1].float().cpu().numpy().astype(np.int64) + minmax
+                sym = sym.transpose(1, 2, 0).reshape(-1, len(channels)).astype(np.int32)
+                enc.encode(sym.reshape(-1), np.ascontiguousarray(cdf.reshape(-1, n_tab)))
+            return
+        # wavefront order: the pixels enter the coder group by group of equal t = w + 3 h.  Bands of whole groups, each at most
+        # _TABLE_BYTES of tables: their (scale, mean) rows are gathered on the device, ONE table launch per band (the table
+        # kernel is element-wise, so the numbers are those of the whole-map evaluation), one host copy -- host memory is
+        # bounded by the band, whatever the image size or the latent range (round 3 built the whole map's tables at once)
+        groups = self._wavefronts(H, W)
+        cap = max(1, self._TABLE_BYTES // (len(channels) * n_tab * 4))
+        sc_rows, mu_rows, y_rows = _nhwc_rows(sc), _nhwc_rows(mu), _nhwc_rows(y_hat)
+        ch_t = torch.as_tensor(channels, device=y_hat.device)
+        g0 = 0
+        while g0 < len(groups):
+            g1, P = g0, 0
+            while g1 < len(groups) and (P == 0 or P + len(groups[g1]) <= cap):
+                P += len(groups[g1])
+                g1 += 1
+            pix = torch.from_numpy(np.concatenate(groups[g0:g1])).to(y_hat.device)
+            sc_r, mu_r = (t[pix].contiguous().t().reshape(1, self.M, 1, P) for t in (sc_rows, mu_rows))
+            cdf = Fn.gmm_cdf_tables(sc_r, mu_r, None, channels, minmax, 1, scale_bound=bound)               # (C, 1, P, n)
+            cdf = cdf.cpu().numpy().view(np.uint32).reshape(len(channels), P, n_tab).transpose(1, 0, 2)       # pixel-major
+            sym = (y_rows[pix][:, ch_t].float().cpu().numpy().astype(np.int64) + minmax).astype(np.int32)      # (P, C)
+            enc.encode(sym.reshape(-1), np.ascontiguousarray(cdf).reshape(-1, n_tab))
+            g0 = g1
 
     # ---- wavefront decode with the device work of a group as a replayed HIP graph (round 4).  Round 3 issued every group's ~15 device
     # operations from Python (gathers, masked conv, cat, 1x1 net, layout copies, table kernel: ~270 us per group, 250 groups per 512^2
@@ -1489,38 +1085,52 @@ class HSICJoint(StereoCompressionModel):
     # a step is: copy the previous symbols up, replay, launch the table kernel (its width depends on the image's latent range; it reads
     # (scale, mean) straight from the net's fp32 output rows), copy the tables down, range-decode.  Graphs and their static buffers are
     # cached on the module per (view, map size, format, weights).
-    def _wavefront_state(self, which, yh, yw, dev):
-        import numpy as np
-        cdt = Fn.compute_dtype()
+    def _walk_nets(self, which):
+        """(masked context conv, entropy-parameter net, tag) of view ``which``; a cached walk state is current while its tag is this one
+        (same format, same weights)."""
         ctx_m = self.context_prediction1 if which == 1 else self.context_prediction2
         ep = self.entropy_parameters1 if which == 1 else self.entropy_parameters2
-        tag = (Fn._cache_epoch, cdt) + tuple((p_.data_ptr(), p_._version) for p_ in list(ctx_m.parameters()) + list(ep.parameters()))
-        cache = self.__dict__.setdefault("_wf_cache", {})
-        key = (which, yh, yw, dev.index)
-        st = cache.get(key)
-        if st is not None and st["tag"] == tag:
-            return st
+        tag = (Fn._cache_epoch, Fn.compute_dtype()) + tuple((p_.data_ptr(), p_._version) for p_ in list(ctx_m.parameters()) + list(ep.parameters()))
+        return ctx_m, ep, tag
+
+    def _walk_geometry(self, which, yh, yw):
+        """What the two decode walks of view ``which`` share (``_wavefront_state``, ``_batch_walk_state``): -> (a new state with the shared
+        entries, the raster index of every pixel in walk order, its row in the padded map)."""
+        import numpy as np
+        ctx_m, ep, tag = self._walk_nets(which)
         if not hasattr(ctx_m, "_packer"):
             ctx_m._packer = Fn.PackedWeight()
-        M, Wp = self.M, yw + 4
+        Wp = yw + 4
         groups = self._wavefronts(yh, yw)
-        pmax = max(len(g) for g in groups)
         all_pix = np.concatenate(groups)
         centre = (all_pix // yw + 2) * Wp + (all_pix % yw) + 2
         c_par = (self.h_s1 if which == 1 else self.h_s2)[4].out_channels
-        c_feat = c_par + ctx_m.out_channels + (M if which == 2 else 0)
-        st = {"tag": tag, "groups": [len(g) for g in groups], "pmax": pmax, "ctx_m": ctx_m, "ep": ep, "graphs": {}, "Wp": Wp,
-              "c_par": c_par, "c_feat": c_feat, "e_off": c_par + ctx_m.out_channels,
-              "y_pad": torch.zeros((1, M, yh + 4, Wp), dtype=cdt, device=dev).contiguous(memory_format=torch.channels_last),
-              "par": torch.zeros((yh * yw, c_par), dtype=cdt, device=dev),
-              "ext": torch.zeros((yh * yw, M), dtype=cdt, device=dev) if which == 2 else None,
-              "all_centre": torch.from_numpy(centre.astype(np.int64)).to(dev), "all_rows": torch.from_numpy(all_pix.astype(np.int64)).to(dev),
-              "pos": torch.zeros(1, dtype=torch.int64, device=dev), "cfg": torch.zeros(4 + M, dtype=torch.int32, device=dev),
-              "cfg_pin": torch.zeros(4 + M, dtype=torch.int32).pin_memory(), "tab": None, "tab_in_graph": False,
-              "sym": torch.zeros(pmax * M, dtype=torch.int32, device=dev),
-              "prev_centre": torch.zeros(pmax, dtype=torch.int64, device=dev),
-              "crops": torch.zeros((pmax, 5, 5, M), dtype=cdt, device=dev), "feat": torch.zeros((pmax, c_feat), dtype=cdt, device=dev),
-              "sym_pin": torch.zeros(pmax * M, dtype=torch.int32).pin_memory()}
+        e_off = c_par + ctx_m.out_channels
+        st = {"tag": tag, "groups": [len(g) for g in groups], "pmax": max(len(g) for g in groups), "ctx_m": ctx_m, "ep": ep, "Wp": Wp,
+              "c_par": c_par, "e_off": e_off, "c_feat": e_off + (self.M if which == 2 else 0)}
+        return st, all_pix, centre
+
+    def _wavefront_state(self, which, yh, yw, dev):
+        import numpy as np
+        cache = self.__dict__.setdefault("_wf_cache", {})
+        key = (which, yh, yw, dev.index)
+        st = cache.get(key)
+        if st is not None and st["tag"] == self._walk_nets(which)[2]:
+            return st
+        st, all_pix, centre = self._walk_geometry(which, yh, yw)
+        cdt, M, Wp, pmax, c_par, c_feat = Fn.compute_dtype(), self.M, st["Wp"], st["pmax"], st["c_par"], st["c_feat"]
+        st.update({
+            "graphs": {},
+            "y_pad": torch.zeros((1, M, yh + 4, Wp), dtype=cdt, device=dev).contiguous(memory_format=torch.channels_last),
+            "par": torch.zeros((yh * yw, c_par), dtype=cdt, device=dev),
+            "ext": torch.zeros((yh * yw, M), dtype=cdt, device=dev) if which == 2 else None,
+            "all_centre": torch.from_numpy(centre.astype(np.int64)).to(dev), "all_rows": torch.from_numpy(all_pix.astype(np.int64)).to(dev),
+            "pos": torch.zeros(1, dtype=torch.int64, device=dev), "cfg": torch.zeros(4 + M, dtype=torch.int32, device=dev),
+            "cfg_pin": torch.zeros(4 + M, dtype=torch.int32).pin_memory(), "tab": None, "tab_in_graph": False,
+            "sym": torch.zeros(pmax * M, dtype=torch.int32, device=dev),
+            "prev_centre": torch.zeros(pmax, dtype=torch.int64, device=dev),
+            "crops": torch.zeros((pmax, 5, 5, M), dtype=cdt, device=dev), "feat": torch.zeros((pmax, c_feat), dtype=cdt, device=dev),
+            "sym_pin": torch.zeros(pmax * M, dtype=torch.int32).pin_memory()})
         st["y_flat"] = st["y_pad"].permute(0, 2, 3, 1).reshape((yh + 4) * Wp, M)
         st["state"], st["channels"] = st["cfg"][:3], st["cfg"][4:]          # {nprev, C, minmax} and the coded channels: one upload per view
         cache[key] = st
@@ -1671,110 +1281,25 @@ class HSICJoint(StereoCompressionModel):
         self._wavefront_kernel(st, 0)                              # the last group's symbols
         return st["y_pad"][:, :, 2:-2, 2:-2].contiguous(memory_format=torch.channels_last)
 
-    def decompress(self, x1, x2, h_matrix, output_name, output_path="", device=None):
-        """x1 / x2 are unused (the header carries the size); kept for the reference's signature."""
-        import os
-        import time
+    def _decode_y(self, dec, which, z_hat, extra, minmax, channels, yh, yw, order):
+        """Raster payload: the reference's walk, one pixel per step (newnet1_joint.py:1190-1260).  Wavefront payload: one step per group
+        of mutually independent pixels (``_decode_view_graphed``)."""
         import numpy as np
-        from ._host import RangeDecoder
-        if self.entropy_bottleneck1._offset.numel() == 0:
-            self.update()
-        dev = h_matrix.device
-        with open(os.path.join(output_path, str(output_name) + ".npz"), "rb") as f:
-            blob = f.read()
-        x_shape = np.frombuffer(blob[:4], dtype=np.uint16).astype(int)
-        pos, views = 4, []
-        for _ in range(2):
-            length, minmax = (int(v) for v in np.frombuffer(blob[pos:pos + 4], dtype=np.uint16))
-            pos += 4
-            flag = np.unpackbits(np.frombuffer(blob[pos:pos + (self.M + 7) // 8], dtype=np.uint8))[:self.M]
-            pos += (self.M + 7) // 8
-            views.append((minmax, [int(c) for c in np.nonzero(flag)[0]], blob[pos:pos + length]))
-            pos += length
-        yh, yw = int(x_shape[0]) // 16, int(x_shape[1]) // 16
-        size = (int(x_shape[0]), int(x_shape[1]))
-        with open(os.path.join(output_path, str(output_name) + ".bin"), "rb") as f:
-            payload = f.read()
-        extra, off = check_payload(payload, 1)
-        if extra[0] not in (self.ORDER_RASTER, self.ORDER_WAVEFRONT):
-            raise ValueError("decompress: not a HESIC+ payload of this coder (unknown pixel-order byte)")
-        wavefront = extra[0] == self.ORDER_WAVEFRONT
-        dec = RangeDecoder(payload[off:])
-        cdt = Fn.compute_dtype()
+        params = self._params_view(which, z_hat)
+        dev, cdt = params.device, Fn.compute_dtype()
         bound = self.gaussian_conditional1._bound()
-        start = time.time()
-
-        def decode_view(which, params, minmax, channels, extra=None):
-            """Raster payload: the reference's walk, one pixel per step (newnet1_joint.py:1190-1260).  Wavefront payload: one step
-            per group of mutually independent pixels -- their 5x5 crops gathered into one batch, ONE masked-conv launch, ONE pass
-            of the 1x1 entropy-parameter net, ONE table launch and ONE device -> host copy for the whole group."""
-            y_pad = torch.zeros((1, self.M, yh + 4, yw + 4), dtype=cdt, device=dev).contiguous(memory_format=torch.channels_last)
-            if not channels:
-                return y_pad[:, :, 2:-2, 2:-2].contiguous(memory_format=torch.channels_last)
+        if channels and order == "wavefront":
+            return self._decode_view_graphed(dec, which, params, minmax, channels, extra, yh, yw, bound)
+        y_pad = torch.zeros((1, self.M, yh + 4, yw + 4), dtype=cdt, device=dev).contiguous(memory_format=torch.channels_last)
+        if channels:
             ch_t = torch.as_tensor(channels, device=dev)
-            if not wavefront:
-                for h in range(yh):
-                    for w in range(yw):
-                        sc, mu = self._gauss_pixel(which, params, y_pad, h, w, extra)
-                        cdf = Fn.gmm_cdf_tables(sc, mu, None, channels, minmax, 1, scale_bound=bound)
-                        sym = dec.decode(cdf.cpu().numpy().view(np.uint32).reshape(len(channels), -1))
-                        y_pad[0, ch_t, h + 2, w + 2] = torch.from_numpy(sym.astype(np.float32) - minmax).to(dev, cdt)
-                return y_pad[:, :, 2:-2, 2:-2].contiguous(memory_format=torch.channels_last)
-            if WAVEFRONT_GRAPHS and dev.type == "cuda":
-                return self._decode_view_graphed(dec, which, params, minmax, channels, extra, yh, yw, bound)
-            ctx_m = self.context_prediction1 if which == 1 else self.context_prediction2
-            ep = self.entropy_parameters1 if which == 1 else self.entropy_parameters2
-            if not hasattr(ctx_m, "_packer"):
-                ctx_m._packer = Fn.PackedWeight()
-            Wp = yw + 4
-            y_flat = y_pad.permute(0, 2, 3, 1).reshape((yh + 4) * Wp, self.M)            # views of the NHWC storage: one row per padded pixel
-            par_flat = _nhwc_rows(params)
-            ext_flat = None if extra is None else _nhwc_rows(extra)
-            groups = self._wavefronts(yh, yw)
-            # gather indices of every group, uploaded once: the 25 padded-map rows of each pixel's crop, its own padded row, its raster row
-            win = (np.arange(5)[:, None] * Wp + np.arange(5)[None, :]).reshape(-1)
-            all_pix = np.concatenate(groups)
-            top_left = (all_pix // yw) * Wp + (all_pix % yw)
-            crop_idx = torch.from_numpy((top_left[:, None] + win[None, :]).reshape(-1)).to(dev)
-            centre_idx = torch.from_numpy(top_left + 2 * Wp + 2).to(dev)
-            pix_idx = torch.from_numpy(all_pix).to(dev)
-            pos = 0
-            for grp in groups:
-                P = len(grp)
-                crops = y_flat[crop_idx[pos * 25:(pos + P) * 25]].view(P, 5, 5, self.M).permute(0, 3, 1, 2)      # (P, M, 5, 5), NHWC in memory
-                ctx = Fn.conv2d(crops, ctx_m.weight, ctx_m.bias, kernel_size=5, stride=1, padding=0, mask=ctx_m.mask,
-                                tap_mask=ctx_m._tap_mask, packer=ctx_m._packer)                                    # (P, 2M, 1, 1)
-                rows = pix_idx[pos:pos + P]
-                parts = [par_flat[rows], ctx.reshape(P, -1)]
-                if ext_flat is not None:
-                    parts.append(ext_flat[rows])
-                feat = torch.cat(parts, 1)
-                sc, mu = _seq3_hi(ep, feat.view(P, feat.shape[1], 1, 1).contiguous(memory_format=torch.channels_last)).chunk(2, 1)
-                # (P, M, 1, 1) -> one image row of P pixels for the table kernel: the same P x M memory
-                sc_r, mu_r = (t.reshape(P, self.M).contiguous().t().reshape(1, self.M, 1, P) for t in (sc, mu))
-                cdf = Fn.gmm_cdf_tables(sc_r, mu_r, None, channels, minmax, 1, scale_bound=bound)               # (C, 1, P, n)
-                tab = cdf.cpu().numpy().view(np.uint32).reshape(len(channels) * P, -1)                 # channel-major rows, as the kernel wrote them
-                sym = dec.decode_grid(tab, P, len(channels), 1, P)                                       # pixel-major stream order, no host transpose
-                vals = torch.from_numpy(sym.astype(np.float32) - minmax).to(dev, cdt)
-                y_flat[centre_idx[pos:pos + P].unsqueeze(1), ch_t.unsqueeze(0)] = vals
-                pos += P
-            return y_pad[:, :, 2:-2, 2:-2].contiguous(memory_format=torch.channels_last)
-
-        with torch.no_grad(), Fn.no_split_k():
-            self.context_prediction1.weight.data *= self.context_prediction1.mask
-            self.context_prediction2.weight.data *= self.context_prediction2.mask
-            zs = (yh // 4, yw // 4)
-            z1_hat = self.entropy_bottleneck1.decompress([views[0][2]], zs).to(dev, cdt)
-            z2_hat = self.entropy_bottleneck2.decompress([views[1][2]], zs).to(dev, cdt)
-            y1_hat = decode_view(1, self._params_view(1, z1_hat), views[0][0], views[0][1])
-            x1_hat = self.decoder1(y1_hat)
-            x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
-            y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
-            y2_hat = decode_view(2, self._params_view(2, z2_hat), views[1][0], views[1][1], y1_hat_w)
-            x2_hat = self.decoder2(y2_hat, x1_hat_warp)
-        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat,
-                "dectime": time.time() - start}
-
+            for h in range(yh):
+                for w in range(yw):
+                    sc, mu = self._gauss_pixel(which, params, y_pad, h, w, extra)
+                    cdf = Fn.gmm_cdf_tables(sc, mu, None, channels, minmax, 1, scale_bound=bound)
+                    sym = dec.decode(cdf.cpu().numpy().view(np.uint32).reshape(len(channels), -1))
+                    y_pad[0, ch_t, h + 2, w + 2] = torch.from_numpy(sym.astype(np.float32) - minmax).to(dev, cdt)
+        return y_pad[:, :, 2:-2, 2:-2].contiguous(memory_format=torch.channels_last)
 
     # ------------------------------------------------------------------------------- batched bit-stream, coded on the device
     # HESIC+ for a whole batch with the range coder on the GPU (csrc/codec.hip; stream definition in include/hesic_codec.h).  The encoder
@@ -1783,53 +1308,15 @@ class HSICJoint(StereoCompressionModel):
     # images together: per group a gather of the B * P crops and feature rows, the masked 5x5 conv, the three 1x1 layers and the step
     # decoder, which writes the symbols straight into the padded maps -- six dependent launches, no host in the loop; the walk of a view is
     # captured as one HIP graph and replayed.  As in the per-pair path the convs run unsplit, so that the decoder sums in the encoder's order.
-    def compress_batch(self, x1, x2, h_matrix, channels_per_stream=1, z_coder="host"):
-        """(B, 3, H, W) pairs -> dict(blobs: one ``bytes`` per pair (``bitstream.pack_pair``, kind "joint"), bpp_real: one figure per pair
-        over its 2 H W pixels, y1_hat, y2_hat, z1_hat, z2_hat).  ``channels_per_stream`` and ``z_coder`` as in ``HSIC.compress_batch``.  An
-        image whose latents need an alphabet beyond the device coder's 1024 symbols raises ``ValueError``: code that pair with ``compress``."""
+    def _rc_order(self, yh, yw, dev):
         import numpy as np
-        from . import bitstream
-        _check_pair(x1, x2, h_matrix)
-        device_z = _check_z_coder("HSICJoint.compress_batch", z_coder)
-        if not x1.is_cuda:
-            raise RuntimeError("HSICJoint.compress_batch: the device range coder needs tensors on a ROCm device (no CPU fallback)")
-        cps = int(channels_per_stream)
-        if not 1 <= cps <= min(self.M, 255):
-            raise ValueError(f"HSICJoint.compress_batch: channels_per_stream must be in [1, {min(self.M, 255)}], got {channels_per_stream}")
-        if self.entropy_bottleneck1._offset.numel() == 0:
-            self.update()
-        B, _, H, W = x1.shape
-        with torch.no_grad(), Fn.no_split_k():
-            self.context_prediction1.weight.data *= self.context_prediction1.mask
-            self.context_prediction2.weight.data *= self.context_prediction2.mask
-            (y1_hat, z1_strings, z1_hat, sc1, mu1), (y2_hat, z2_strings, z2_hat, sc2, mu2) = self._coder_inputs(x1, x2, h_matrix, device_z)
-            order = torch.from_numpy(np.concatenate(self._wavefronts(H // 16, W // 16)).astype(np.int32)).to(x1.device)
-            bound = self.gaussian_conditional1._bound()
-            # one small device -> host read: per image, view and channel max |y_hat| (minmax and the flags follow from it)
-            peak = torch.stack([y.float().abs().amax(dim=(2, 3)) for y in (y1_hat, y2_hat)]).cpu()
-            views = [[None, None] for _ in range(B)]
-            for vi, (y_hat, z_strings, sc, mu) in enumerate(((y1_hat, z1_strings, sc1, mu1), (y2_hat, z2_strings, sc2, mu2))):
-                flags = (peak[vi] > 0).tolist()
-                minmax = [int(max(float(peak[vi, b].max()), 1.0)) for b in range(B)]
-                channels = [[c for c, f in enumerate(flags[b]) if f] for b in range(B)]
-                data, counts = Fn.gmm_rc_encode(sc, mu, None, y_hat, minmax, channels, 1, cps, bound, order=order)
-                data, counts = data.cpu().numpy().tobytes(), counts.cpu().tolist()
-                pos = 0
-                for b in range(B):
-                    streams = []
-                    for n in counts[b][:bitstream.n_streams(flags[b], cps)]:
-                        streams.append(data[pos:pos + n])
-                        pos += n
-                    views[b][vi] = {"minmax": minmax[b], "flags": tuple(int(f) for f in flags[b]), "z": None if device_z else z_strings[b],
-                                    "streams": streams}
-            if device_z:
-                for vi, strings in enumerate(_read_z_strings("HSICJoint.compress_batch", (z1_strings, z2_strings))):
-                    for b in range(B):
-                        views[b][vi]["z"] = strings[b]
-        blobs = [bitstream.pack_pair({"kind": "joint", "mode": payload_mode_bytes(), "height": H, "width": W, "channels": self.M,
-                                      "channels_per_stream": cps, "views": views[b]}) for b in range(B)]
-        return {"blobs": blobs, "bpp_real": [len(bl) * 8 / (H * W * 2) for bl in blobs],
-                "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
+        return torch.from_numpy(np.concatenate(self._wavefronts(yh, yw)).astype(np.int32)).to(dev)
+
+    def _rc_encode(self, which, y_hat, params, minmax, channels, cps, order):
+        return Fn.gmm_rc_encode(params[0], params[1], None, y_hat, minmax, channels, 1, cps, self.gaussian_conditional1._bound(), order=order)
+
+    def _rc_decode(self, which, z_hat, extra, view, cps, yh, yw):
+        return self._decode_view_batch(which, self._params_view(which, z_hat), view, cps, extra, yh, yw)
 
     _BATCH_WALKS = 8          # cached walks kept per module (two per decoded (size, B, cps): one per view), least recently used first out
 
@@ -1841,40 +1328,29 @@ class HSICJoint(StereoCompressionModel):
         buffers may still be in use by a replay that has not finished: eviction happens at the start of a later call on the same stream,
         and the allocator defers the release of memory a stream still uses, so nothing is freed under a running replay."""
         import numpy as np
-        cdt = Fn.compute_dtype()
-        ctx_m = self.context_prediction1 if which == 1 else self.context_prediction2
-        ep = self.entropy_parameters1 if which == 1 else self.entropy_parameters2
-        tag = (Fn._cache_epoch, cdt) + tuple((p_.data_ptr(), p_._version) for p_ in list(ctx_m.parameters()) + list(ep.parameters()))
         cache = self.__dict__.setdefault("_bw_cache", {})
         key = (which, yh, yw, B, cps, dev.index)
         st = cache.pop(key, None)
-        if st is not None and st["tag"] == tag:
+        if st is not None and st["tag"] == self._walk_nets(which)[2]:
             cache[key] = st                                  # most recently used last
             return st
         while len(cache) >= self._BATCH_WALKS:               # every entry owns a captured graph and a worst-case payload buffer
             cache.pop(next(iter(cache)))
-        if not hasattr(ctx_m, "_packer"):
-            ctx_m._packer = Fn.PackedWeight()
-        M, Wp, HW = self.M, yw + 4, yh * yw
-        groups = self._wavefronts(yh, yw)
-        pmax = max(len(g) for g in groups)
-        all_pix = np.concatenate(groups)
-        centre = (all_pix // yw + 2) * Wp + (all_pix % yw) + 2
-        c_par = (self.h_s1 if which == 1 else self.h_s2)[4].out_channels
-        c_feat = c_par + ctx_m.out_channels + (M if which == 2 else 0)
+        st, all_pix, centre = self._walk_geometry(which, yh, yw)
+        cdt, M, Wp, HW, pmax, c_par = Fn.compute_dtype(), self.M, st["Wp"], yh * yw, st["pmax"], st["c_par"]
         S = (M + cps - 1) // cps
-        st = {"tag": tag, "groups": [len(g) for g in groups], "ctx_m": ctx_m, "ep": ep, "graph": None, "Wp": Wp, "c_par": c_par,
-              "e_off": c_par + ctx_m.out_channels,
-              "y_pad": torch.zeros((B, M, yh + 4, Wp), dtype=cdt, device=dev).contiguous(memory_format=torch.channels_last),
-              "par": torch.zeros((B, HW, c_par), dtype=cdt, device=dev),
-              "ext": torch.zeros((B, HW, M), dtype=cdt, device=dev) if which == 2 else None,
-              "centre": torch.from_numpy(centre.astype(np.int32)).to(dev), "rows": torch.from_numpy(all_pix.astype(np.int32)).to(dev),
-              "crops": torch.zeros((B * pmax, 5, 5, M), dtype=cdt, device=dev), "feat": torch.zeros((B * pmax, c_feat), dtype=cdt, device=dev),
-              "meta": torch.zeros((B, M + 2), dtype=torch.int32, device=dev),
-              # the payload's worst case is the encoder's slot: 4 bytes per symbol + 16 per stream (a stream is at most 2 per symbol + flush)
-              "data": torch.zeros(B * (4 * M * HW + 16 * S), dtype=torch.uint8, device=dev),
-              "offsets": torch.zeros(B * S, dtype=torch.int64, device=dev), "counts": torch.zeros(B * S, dtype=torch.int32, device=dev),
-              "coder": torch.zeros((B * S, 4), dtype=torch.int64, device=dev)}
+        st.update({
+            "graph": None,
+            "y_pad": torch.zeros((B, M, yh + 4, Wp), dtype=cdt, device=dev).contiguous(memory_format=torch.channels_last),
+            "par": torch.zeros((B, HW, c_par), dtype=cdt, device=dev),
+            "ext": torch.zeros((B, HW, M), dtype=cdt, device=dev) if which == 2 else None,
+            "centre": torch.from_numpy(centre.astype(np.int32)).to(dev), "rows": torch.from_numpy(all_pix.astype(np.int32)).to(dev),
+            "crops": torch.zeros((B * pmax, 5, 5, M), dtype=cdt, device=dev), "feat": torch.zeros((B * pmax, st["c_feat"]), dtype=cdt, device=dev),
+            "meta": torch.zeros((B, M + 2), dtype=torch.int32, device=dev),
+            # the payload's worst case is the encoder's slot: 4 bytes per symbol + 16 per stream (a stream is at most 2 per symbol + flush)
+            "data": torch.zeros(B * (4 * M * HW + 16 * S), dtype=torch.uint8, device=dev),
+            "offsets": torch.zeros(B * S, dtype=torch.int64, device=dev), "counts": torch.zeros(B * S, dtype=torch.int32, device=dev),
+            "coder": torch.zeros((B * S, 4), dtype=torch.int64, device=dev)})
         st["y_rows"] = st["y_pad"].permute(0, 2, 3, 1).reshape(B, (yh + 4) * Wp, M)          # a view of the NHWC storage
         cache[key] = st
         return st
@@ -1927,37 +1403,6 @@ class HSICJoint(StereoCompressionModel):
             st["y_pad"].zero_()
         st["graph"].replay()
         return st["y_pad"][:, :, 2:-2, 2:-2].contiguous(memory_format=torch.channels_last)
-
-    def decompress_batch(self, blobs, h_matrix, z_coder="host"):
-        """``blobs``: what ``compress_batch`` returned, in any grouping and order (all of one image size and channels_per_stream);
-        ``h_matrix`` (B, 3, 3) the matching homographies.  Everything is validated on the host before the first launch.  ``z_coder`` as in
-        ``HSIC.decompress_batch``."""
-        device_z = _check_z_coder("HSICJoint.decompress_batch", z_coder)
-        B, H, W, cps, per_view = _batch_blobs("HSICJoint.decompress_batch", "joint", blobs, h_matrix, self.M)
-        if self.entropy_bottleneck1._offset.numel() == 0:
-            self.update()
-        dev, cdt, size = h_matrix.device, Fn.compute_dtype(), (H, W)
-        yh, yw = H // 16, W // 16
-        zs = (yh // 4, yw // 4)
-        with torch.no_grad(), Fn.no_split_k():
-            self.context_prediction1.weight.data *= self.context_prediction1.mask
-            self.context_prediction2.weight.data *= self.context_prediction2.mask
-            z_status = None
-            if device_z:
-                z1_hat, z2_hat, z_status = _decode_z_device("HSICJoint.decompress_batch", (self.entropy_bottleneck1, self.entropy_bottleneck2),
-                                                            per_view, zs, dev, cdt)
-            else:
-                z1_hat = _decompress_z(self.entropy_bottleneck1, per_view[0][2], zs).to(dev, cdt)
-                z2_hat = _decompress_z(self.entropy_bottleneck2, per_view[1][2], zs).to(dev, cdt)
-            y1_hat = self._decode_view_batch(1, self._params_view(1, z1_hat), per_view[0], cps, None, yh, yw)
-            x1_hat = self.decoder1(y1_hat)
-            x1_hat_warp = warp_perspective(x1_hat, h_matrix, size)
-            y1_hat_w = _round_latent(self.gaussian1, self.encoder1.latent(x1_hat_warp, want_lo=False)[1])
-            y2_hat = self._decode_view_batch(2, self._params_view(2, z2_hat), per_view[1], cps, y1_hat_w, yh, yw)
-            x2_hat = self.decoder2(y2_hat, x1_hat_warp)
-            if z_status is not None:
-                Fn.rans_check_status("HSICJoint.decompress_batch: z string", z_status.cpu())
-        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
 
 
 # -------------------------------------------------------------------- enhancement (SURVEY 8f rank 1)
