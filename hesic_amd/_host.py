@@ -172,17 +172,10 @@ class RangeDecoder:
             raise ValueError("RangeDecoder.decode: bad table")
         return out
 
-    def decode_grid_raw(self, cdf_ptr, stride, n_outer, n_inner, row_step_outer, row_step_inner, out_ptr):
-        """``decode_grid`` on raw host addresses (table rows of ``stride`` uint32 at ``cdf_ptr``, int32 symbols to ``out_ptr``): no numpy
-        objects per call -- the HESIC+ wavefront decode calls this once per group."""
-        rc = lib().hesic_rc_decoder_decode_grid(self._h, C.cast(cdf_ptr, C.POINTER(C.c_uint32)), n_outer, n_inner, row_step_outer, row_step_inner,
-                                                stride, C.cast(out_ptr, _pi32))
-        if rc:
-            raise ValueError("RangeDecoder.decode_grid: bad table")
-
     def grid_callback(self):
-        """(function address, decoder handle) of ``hesic_rc_decoder_decode_grid`` for a C caller that drives the decoder itself
-        (``hesic_joint_decode_groups`` of the HIP library: the HESIC+ wavefront walk without a Python step per group)."""
+        """(function address, decoder handle) of ``hesic_rc_decoder_decode_grid`` for a C caller that drives the decoder itself: the HESIC+
+        wavefront walk of the HIP library (``hesic_joint_decode_groups_tape`` / ``hesic_joint_decode_groups``) calls it once per group on
+        raw host addresses, with no Python step in between."""
         return C.cast(lib().hesic_rc_decoder_decode_grid, C.c_void_p), self._h
 
     def decode_grid(self, cdf, n_outer, n_inner, row_step_outer, row_step_inner):

@@ -21,7 +21,7 @@ LIB_PATH_F16 = os.path.join(_HERE, "libhesic_hip_f16.so")
 _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 F32, H16 = 0, 1
-ABI_VERSION = 2      # include/hesic_hip.h HESIC_ABI_VERSION
+ABI_VERSION = 3      # include/hesic_hip.h HESIC_ABI_VERSION
 BF16 = H16       # historical name: the library's 16-bit format (hesic_h16_format())
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 EB_PARAM_STRIDE = 64
@@ -110,11 +110,9 @@ _SIGS = {
     "hesic_last_error": ([], C.c_char_p),
     "hesic_pack_conv_weight": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
     "hesic_joint_step": ([_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp], _i32),
-    "hesic_memcpy_async": ([_vp, _vp, C.c_size_t, _i32, _vp], _i32),
-    "hesic_stream_synchronize": ([_vp], _i32),
     "hesic_probe_mfma_loop": ([_vp, _vp, _i32, _P(C.c_double), _vp], _i32),
-    "hesic_joint_decode_groups": ([_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp], _i32),
-    "hesic_joint_decode_groups_tape": ([_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp], _i32),
+    "hesic_joint_decode_groups": ([_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp], _i32),
+    "hesic_joint_decode_groups_tape": ([_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp], _i32),
     "hesic_ssim_scale": ([_vp, _P(_i64), _vp, _P(_i64), _i32, _i32, _i32, _i32, _f32, _vp, _vp], _i32),
     "hesic_avgpool2_pad": ([_vp, _P(_i64), _vp, _i32, _i32, _i32, _i32, _vp], _i32),
     "hesic_pack_conv_weight_shaped": ([_vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
@@ -125,7 +123,6 @@ _SIGS = {
     "hesic_eb_prepare_params": ([_vp, _vp, _i32, _vp], _i32),
     "hesic_gmm_cdf": ([_P(GmmDesc), _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp], _i32),
     "hesic_gmm_cdf_rows": ([_P(GmmDesc), _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp], _i32),
-    "hesic_gmm_cdf_dyn": ([_P(GmmDesc), _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp], _i32),
     "hesic_maxpool2_forward": ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
     "hesic_perspective_transform": ([_vp, _vp, _vp, _i32, _vp], _i32),
     "hesic_h_from_delta": ([_vp, _vp, _f32, _f32, _i32, _vp, _i32, _vp], _i32),
@@ -146,7 +143,6 @@ _SIGS = {
     "hesic_sconv2d_forward_cat_gdn": ([_P(SConvDesc), _vp, _vp, C.POINTER(C.c_int64), _i32, _i32, _vp, _vp, _vp, _vp, C.c_float, _i32, _i32,
                                        _vp, _vp], _i32),
     "hesic_sconv2d_gdn_forward": ([_P(SConvDesc), _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp], _i32),
-    "hesic_sconv2d_gdn_forward_train": ([_P(SConvDesc), _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp], _i32),
     "hesic_sconv_pack_weight_image": ([_i32, _vp, _vp, _vp, _vp], _i32),
     "hesic_sconv2d_forward_prepacked": ([_P(SConvDesc), _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "hesic_sconv2d_gdn_forward_prepacked": ([_P(SConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp], _i32),

@@ -916,15 +916,6 @@ extern "C" int hesic_joint_step(void* y_rows, int dtype, int M, int Wp, const in
     HESIC_LAUNCH_RETURN("joint_step");
 }
 
-// Plain copies / a stream wait for host loops that sit between launches (the HESIC+ wavefront decode makes ~750 of them per pair): the
-// torch route costs ~10 us of dispatcher per call.  kind: 1 = host -> device, 2 = device -> host (pinned host memory for async behaviour).
-extern "C" int hesic_memcpy_async(void* dst, const void* src, size_t bytes, int kind, void* stream) {
-    HESIC_CHECK_ARG(dst && src && (kind == 1 || kind == 2), "memcpy_async: bad arguments");
-    if (bytes == 0) return 0;
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (e != hipSuccess) { hesic_set_error("memcpy_async: %s", hipGetErrorString(e)); return (int)e; }
-    return 0;
-}
 // A recorded launch of one of the entry points a HESIC+ group step is made of, replayed by address: the arguments as 64-bit words
 // (pointers and integers only; the trailing stream argument is supplied at replay).
 static int run_tape(const hesic_tape_call* t, int n, void* stream) {
@@ -959,21 +950,19 @@ static int run_tape(const hesic_tape_call* t, int n, void* stream) {
     return 0;
 }
 
-// The whole decode walk of one view behind one call (models.HSICJoint._decode_view_graphed): per group -- previous symbols up, the group's
-// device step (a captured hipGraphExec_t of torch's, or the recorded launches of the step replayed one by one: back-to-back launches
-// of a dependent chain of small kernels start closer together than the nodes of a graph), table launch, tables down, wait, range-decode
-// through the caller's decoder (libhesic_host.so: hesic_rc_decoder_decode_grid) into the pinned symbol buffer.  Six Python -> C crossings
-// per group became none; the wait polls hipStreamQuery (a blocked hipStreamSynchronize wakes up through an interrupt).
+// The whole decode walk of one view behind one call (models.HSICJoint._decode_view_graphed).  Per group: the group's device step (its
+// recorded launches replayed one by one -- back-to-back launches of a dependent chain of small kernels start closer together than the nodes
+// of a graph -- or, where the tape cannot express the step, its captured hipGraphExec_t), the table launch, a polled wait (hipStreamQuery: a
+// blocked hipStreamSynchronize wakes up through an interrupt), the range decoder of the caller (libhesic_host.so:
+// hesic_rc_decoder_decode_grid).  `tab` and `sym` are pinned host memory that the kernels address themselves: no copies.
 static int joint_decode_groups(int n_groups, const int32_t* group_size, void* const* graph_exec, const hesic_tape_call* const* tapes, const int32_t* tape_len,
                                const hesic_gmm_desc* descs, void* const* scale_mean, const int32_t* channels, int n_channels, int minmax,
-                               uint32_t* tab_dev, uint32_t* tab_host, int32_t* sym_dev, int32_t* sym_host, hesic_decode_grid_fn decode, void* decoder,
-                               int spin, void* stream) {
-    HESIC_CHECK_ARG(n_groups >= 0 && group_size && (graph_exec || (tapes && tape_len)) && (scale_mean || !descs) && channels && n_channels > 0 && minmax >= 0 &&
-                        tab_dev && tab_host && sym_dev && sym_host && decode && decoder,
+                               uint32_t* tab, int32_t* sym, hesic_decode_grid_fn decode, void* decoder, void* stream) {
+    HESIC_CHECK_ARG(n_groups >= 0 && group_size && (graph_exec || (tapes && tape_len)) && descs && scale_mean && channels && n_channels > 0 && minmax >= 0 &&
+                        tab && sym && decode && decoder,
                     "joint_decode_groups: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     const int n_tab = 2 * minmax + 2;
-    int nprev = 0;
     auto fail = [](const char* what, hipError_t e) { hesic_set_error("joint_decode_groups: %s: %s", what, hipGetErrorString(e)); return (int)e; };
     static const bool timing = getenv("HESIC_JOINT_TIMING") != nullptr;      // stderr: where the wall time of the walk went
     double t_submit = 0, t_wait = 0, t_decode = 0;
@@ -982,32 +971,18 @@ static int joint_decode_groups(int n_groups, const int32_t* group_size, void* co
         const int P = group_size[g];
         hipError_t e;
         const double t0 = timing ? now() : 0;
-        if (nprev && sym_dev != sym_host && (e = hipMemcpyAsync(sym_dev, sym_host, (size_t)nprev * n_channels * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
-            return fail("symbols up", e);
         if (graph_exec) {
             if ((e = hipGraphLaunch((hipGraphExec_t)graph_exec[g], st)) != hipSuccess) return fail("graph launch", e);
         } else if (int rc = run_tape(tapes[g], tape_len[g], stream)) {
             return rc;
         }
-        if (descs)
-            if (int rc = hesic_gmm_cdf_rows(&descs[g], 0, scale_mean[g], scale_mean[g], nullptr, channels, n_channels, minmax, 1, tab_dev, stream)) return rc;
-        if (tab_dev != tab_host && (e = hipMemcpyAsync(tab_host, tab_dev, (size_t)n_channels * P * n_tab * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
-            return fail("tables down", e);
+        if (int rc = hesic_gmm_cdf_rows(&descs[g], 0, scale_mean[g], scale_mean[g], nullptr, channels, n_channels, minmax, 1, tab, stream)) return rc;
         const double t1 = timing ? now() : 0;
-        if (spin) {
-            while ((e = hipStreamQuery(st)) == hipErrorNotReady) {}
-        } else {
-            e = hipStreamSynchronize(st);
-        }
+        while ((e = hipStreamQuery(st)) == hipErrorNotReady) {}
         if (e != hipSuccess) return fail("wait", e);
         const double t2 = timing ? now() : 0;
-        if (int rc = decode(decoder, tab_host, P, n_channels, n_channels, 1, n_tab, sym_host)) { hesic_set_error("joint_decode_groups: range decoder failed (%d) in group %d", rc, g); return HESIC_EINVAL; }
+        if (int rc = decode(decoder, tab, P, n_channels, n_channels, 1, n_tab, sym)) { hesic_set_error("joint_decode_groups: range decoder failed (%d) in group %d", rc, g); return HESIC_EINVAL; }
         if (timing) { const double t3 = now(); t_submit += t1 - t0; t_wait += t2 - t1; t_decode += t3 - t2; }
-        nprev = P;
-    }
-    if (nprev && sym_dev != sym_host) {
-        const hipError_t e = hipMemcpyAsync(sym_dev, sym_host, (size_t)nprev * n_channels * 4, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return fail("symbols up", e);
     }
     if (timing)
         fprintf(stderr, "joint_decode_groups: %d groups, %d channels, tables of %d: submit %.0f us, wait %.0f us, host decode %.0f us\n", n_groups, n_channels,
@@ -1016,27 +991,19 @@ static int joint_decode_groups(int n_groups, const int32_t* group_size, void* co
 }
 
 extern "C" int hesic_joint_decode_groups(int n_groups, const int32_t* group_size, void* const* graph_exec, const hesic_gmm_desc* descs,
-                                         void* const* scale_mean, const int32_t* channels, int n_channels, int minmax, uint32_t* tab_dev,
-                                         uint32_t* tab_host, int32_t* sym_dev, int32_t* sym_host, hesic_decode_grid_fn decode, void* decoder,
-                                         int spin, void* stream) {
+                                         void* const* scale_mean, const int32_t* channels, int n_channels, int minmax, uint32_t* tab, int32_t* sym,
+                                         hesic_decode_grid_fn decode, void* decoder, void* stream) {
     HESIC_CHECK_ARG(graph_exec, "joint_decode_groups: no graphs");
-    return joint_decode_groups(n_groups, group_size, graph_exec, nullptr, nullptr, descs, scale_mean, channels, n_channels, minmax, tab_dev, tab_host, sym_dev,
-                               sym_host, decode, decoder, spin, stream);
+    return joint_decode_groups(n_groups, group_size, graph_exec, nullptr, nullptr, descs, scale_mean, channels, n_channels, minmax, tab, sym, decode, decoder,
+                               stream);
 }
 
 extern "C" int hesic_joint_decode_groups_tape(int n_groups, const int32_t* group_size, const hesic_tape_call* const* tapes, const int32_t* tape_len,
                                               const hesic_gmm_desc* descs, void* const* scale_mean, const int32_t* channels, int n_channels, int minmax,
-                                              uint32_t* tab_dev, uint32_t* tab_host, int32_t* sym_dev, int32_t* sym_host, hesic_decode_grid_fn decode,
-                                              void* decoder, int spin, void* stream) {
+                                              uint32_t* tab, int32_t* sym, hesic_decode_grid_fn decode, void* decoder, void* stream) {
     HESIC_CHECK_ARG(tapes && tape_len, "joint_decode_groups_tape: no tapes");
-    return joint_decode_groups(n_groups, group_size, nullptr, tapes, tape_len, descs, scale_mean, channels, n_channels, minmax, tab_dev, tab_host, sym_dev,
-                               sym_host, decode, decoder, spin, stream);
-}
-
-extern "C" int hesic_stream_synchronize(void* stream) {
-    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) { hesic_set_error("stream_synchronize: %s", hipGetErrorString(e)); return (int)e; }
-    return 0;
+    return joint_decode_groups(n_groups, group_size, nullptr, tapes, tape_len, descs, scale_mean, channels, n_channels, minmax, tab, sym, decode, decoder,
+                               stream);
 }
 
 // ---- measurement aid (bench.py `roofline.power_state`; no product path calls it): a register-only loop of independent

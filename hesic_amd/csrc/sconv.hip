@@ -1400,13 +1400,6 @@ extern "C" int hesic_sconv2d_gdn_forward(const hesic_sconv_desc* d, const void* 
     return sconv_gdn_launch(d, x, w, nullptr, bias, gamma_packed, beta_packed, inverse, y, nullptr, stream);
 }
 
-extern "C" int hesic_sconv2d_gdn_forward_train(const hesic_sconv_desc* d, const void* x, const float* w, const float* bias,
-                                               const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* y_pre,
-                                               void* stream) {
-    HESIC_CHECK_ARG(y_pre, "sconv2d_gdn_forward_train: null pointer");
-    return sconv_gdn_launch(d, x, w, nullptr, bias, gamma_packed, beta_packed, inverse, y, y_pre, stream);
-}
-
 // dx of y = op(x): the opposite op (conv <-> transposed conv) applied to dy with the same weight tensor:
 // a Conv2d weight (Cout,Cin,k,k) read as a ConvTranspose2d weight maps Cout -> Cin, and vice versa.
 extern "C" int hesic_sconv2d_dgrad(const hesic_sconv_desc* d, const void* dy, const float* w, void* dx, void* stream) {

@@ -784,15 +784,6 @@ class HSIC(PairCoder, StereoCompressionModel):
 # 512^2 but 7.7e-4 vs 6.3e-4 on the 256^2 golden -- not worth a quarter of the margin to the 1e-3 bar
 X3C2_TWO_PRODUCT_TAIL = False
 X2_LAYERS = (2, 2, 2)          # "x2" mode (measured and not the default): products per MAC of g_a_conv2 / conv3 / conv4
-# A/B switch: 1 = the device reads the decoded symbols from, and writes the tables into, pinned host memory itself (no copy nodes)
-WAVEFRONT_ZEROCOPY = True
-# A/B switch, off: 1 = the table launch of a group is the sixth node of its captured step (hesic_gmm_cdf_dyn: channel list and alphabet read on
-# the device).  Measured neutral (per view: 1.0 vs 1.6 ms of launch calls, 8.3 vs 7.6 ms of waiting -- a graph node costs what a launch costs)
-WAVEFRONT_TABLE_IN_GRAPH = False
-_CDF_WAVE_MAX = 1024          # csrc/entropy.hip: alphabets the wave-per-row table kernel takes
-# A/B switch: 1 = the C loop replays each group's recorded launches one by one instead of launching its graph
-WAVEFRONT_TAPE = True
-WAVEFRONT_C_LOOP = True      # module switch: False = the group loop in Python (six C calls per group)
 
 
 def _seq3(seq, x, last_act=NONE):
@@ -1077,14 +1068,13 @@ class HSICJoint(PairCoder, StereoCompressionModel):
             enc.encode(sym.reshape(-1), np.ascontiguousarray(cdf).reshape(-1, n_tab))
             g0 = g1
 
-    # ---- wavefront decode with the device work of a group as a replayed HIP graph (round 4).  Round 3 issued every group's ~15 device
-    # operations from Python (gathers, masked conv, cat, 1x1 net, layout copies, table kernel: ~270 us per group, 250 groups per 512^2
-    # pair = 0.067 s).  Here the state of the walk lives on the device (csrc/glue.hip: hesic_joint_step -- position in the index tables,
-    # the previous group's symbols and rows, the crop / feature gathers in one block), so ONE five-node graph per group size (joint_step,
-    # masked conv into its slice of the feature rows, three 1x1 layers) serves every step of every image of that size; the host's share of
-    # a step is: copy the previous symbols up, replay, launch the table kernel (its width depends on the image's latent range; it reads
-    # (scale, mean) straight from the net's fp32 output rows), copy the tables down, range-decode.  Graphs and their static buffers are
-    # cached on the module per (view, map size, format, weights).
+    # ---- wavefront decode.  The state of the walk lives on the device (csrc/glue.hip: hesic_joint_step -- position in the index tables, the
+    # previous group's symbols and rows, the crop / feature gathers in one block), so one five-launch step per group size (joint_step, masked
+    # conv into its slice of the feature rows, three 1x1 layers) serves every group of every image of that size.  A step is captured once as a
+    # graph, whose private pool owns its buffers, and its launches are recorded as a tape.  A view is then ONE C call
+    # (hesic_joint_decode_groups_tape): per group it replays the tape, launches the table kernel, polls the stream and range-decodes on the
+    # host.  Symbols and tables sit in pinned host memory that the kernels address themselves.  Steps, tapes and buffers are cached on the
+    # module per (view, map size, format, weights).
     def _walk_nets(self, which):
         """(masked context conv, entropy-parameter net, tag) of view ``which``; a cached walk state is current while its tag is this one
         (same format, same weights)."""
@@ -1126,8 +1116,7 @@ class HSICJoint(PairCoder, StereoCompressionModel):
             "ext": torch.zeros((yh * yw, M), dtype=cdt, device=dev) if which == 2 else None,
             "all_centre": torch.from_numpy(centre.astype(np.int64)).to(dev), "all_rows": torch.from_numpy(all_pix.astype(np.int64)).to(dev),
             "pos": torch.zeros(1, dtype=torch.int64, device=dev), "cfg": torch.zeros(4 + M, dtype=torch.int32, device=dev),
-            "cfg_pin": torch.zeros(4 + M, dtype=torch.int32).pin_memory(), "tab": None, "tab_in_graph": False,
-            "sym": torch.zeros(pmax * M, dtype=torch.int32, device=dev),
+            "cfg_pin": torch.zeros(4 + M, dtype=torch.int32).pin_memory(), "tab": None,
             "prev_centre": torch.zeros(pmax, dtype=torch.int64, device=dev),
             "crops": torch.zeros((pmax, 5, 5, M), dtype=cdt, device=dev), "feat": torch.zeros((pmax, c_feat), dtype=cdt, device=dev),
             "sym_pin": torch.zeros(pmax * M, dtype=torch.int32).pin_memory()})
@@ -1138,7 +1127,7 @@ class HSICJoint(PairCoder, StereoCompressionModel):
 
     def _wavefront_kernel(self, st, P):
         import ctypes as C
-        sym = C.c_void_p(st["sym_pin"].data_ptr()) if WAVEFRONT_ZEROCOPY else L.ptr(st["sym"])      # pinned host memory is device-addressable
+        sym = C.c_void_p(st["sym_pin"].data_ptr())                  # pinned host memory is device-addressable
         L.call("hesic_joint_step", L.ptr(st["y_flat"]), L.dt(st["y_flat"]), self.M, st["Wp"], sym, L.ptr(st["prev_centre"]), L.ptr(st["state"]),
                L.ptr(st["channels"]), L.ptr(st["all_centre"]), L.ptr(st["all_rows"]), L.ptr(st["pos"]), int(P), L.ptr(st["crops"]), L.ptr(st["par"]),
                st["c_par"], L.ptr(st["ext"]), st["e_off"], L.ptr(st["feat"]), st["c_feat"], L.stream())
@@ -1152,16 +1141,7 @@ class HSICJoint(PairCoder, StereoCompressionModel):
         feat = st["feat"][:P].view(P, st["c_feat"], 1, 1)
         Fn.conv2d_into(crops, ctx_m.weight, ctx_m.bias, feat, st["c_par"], kernel_size=5, stride=1, padding=0, mask=ctx_m.mask,
                        tap_mask=ctx_m._tap_mask, packer=ctx_m._packer)
-        sm = _seq3_hi(st["ep"], feat)                                                                      # (P, 2M, 1, 1) fp32: row p = [scales(M) | means(M)]
-        if st["tab_in_graph"]:
-            # sixth node: the group's tables, channel list / alphabet read from the device state (any image replays the same graph)
-            import ctypes as C
-            M = self.M
-            d = L.GmmDesc(1, P, M, 1, L.F32, 0, 2 * M, 0, M, float(st["bound"]), 0.0)
-            tab = st["tab"][1] if WAVEFRONT_ZEROCOPY else st["tab"][0]
-            L.call("hesic_gmm_cdf_dyn", C.byref(d), 0, L.ptr(sm), L.ptr(sm), None, L.ptr(st["channels"]), M, L.ptr(st["state"]), 1,
-                   C.c_void_p(tab.data_ptr()), L.stream())
-        return sm
+        return _seq3_hi(st["ep"], feat)                                                                    # (P, 2M, 1, 1) fp32: row p = [scales(M) | means(M)]
 
     def _wavefront_graph(self, st, P):
         ent = st["graphs"].get(P)
@@ -1181,9 +1161,8 @@ class HSICJoint(PairCoder, StereoCompressionModel):
                 out = self._wavefront_step_body(st, P)
             for k, v in keep.items():
                 st[k].copy_(v)
-            n_step = len(rec) - (1 if st["tab_in_graph"] else 0)          # the table launch (if captured) is issued by the walk itself on the tape path
             try:
-                tape = L.tape_from_calls(rec[:n_step])
+                tape = L.tape_from_calls(rec)
             except (KeyError, TypeError):
                 tape = None                                               # an entry point the tape does not know: graph replay only
             ent = st["graphs"][P] = (g, out, tape)
@@ -1191,16 +1170,9 @@ class HSICJoint(PairCoder, StereoCompressionModel):
 
     def _decode_view_graphed(self, dec, which, params, minmax, channels, extra, yh, yw, bound):
         import ctypes as C
-        import numpy as np
         dev = params.device
         st = self._wavefront_state(which, yh, yw, dev)
         M, Cn, n_tab = self.M, len(channels), 2 * minmax + 2
-        if not st["graphs"]:
-            st["tab_in_graph"], st["bound"] = bool(WAVEFRONT_TABLE_IN_GRAPH), float(bound)
-            if st["tab_in_graph"]:                              # the graphs hold the table buffer's address: sized once for the largest alphabet they take
-                rows = M * st["pmax"]
-                st["tab"] = (torch.empty((rows, _CDF_WAVE_MAX + 1), dtype=torch.int32, device=dev),
-                             torch.empty((rows, _CDF_WAVE_MAX + 1), dtype=torch.int32).pin_memory())
         for P in sorted(set(st["groups"])):                    # first use of a map size: capture (cached on the module)
             self._wavefront_graph(st, P)
         st["y_pad"].zero_()
@@ -1212,72 +1184,30 @@ class HSICJoint(PairCoder, StereoCompressionModel):
         cfg[0], cfg[1], cfg[2] = 0, Cn, int(minmax)
         cfg[4:4 + Cn] = torch.as_tensor(channels, dtype=torch.int32)
         st["cfg"].copy_(cfg, non_blocking=True)
-        ch_dev = st["channels"][:Cn]
-        pmax = st["pmax"]
-        in_graph = st["tab_in_graph"] and 2 * minmax + 1 <= _CDF_WAVE_MAX and float(bound) == st["bound"]
-        if in_graph:
-            tab_dev, tab_pin = st["tab"]
-        else:
-            # table buffers (device + pinned) kept with the state: pinning costs ~0.1 ms a call.  Not the ones a captured table launch
-            # writes: an alphabet beyond its 1024 entries (random-weight regimes) goes through launches issued per group
-            big = st.get("tab_big")
-            if big is None or big[0].shape[1] < n_tab:
-                big = st["tab_big"] = (torch.empty((M * pmax, n_tab), dtype=torch.int32, device=dev),
-                                       torch.empty((M * pmax, n_tab), dtype=torch.int32).pin_memory())
-            tab_dev, tab_pin = big
-        descs = {P: L.GmmDesc(1, P, M, 1, L.F32, 0, 2 * M, 0, M, float(bound), 0.0) for P in set(st["groups"])}
-        stream = L.stream()
-        sym_dev, sym_host = L.ptr(st["sym"]), C.c_void_p(st["sym_pin"].data_ptr())
-        tab_d, tab_h = L.ptr(tab_dev), C.c_void_p(tab_pin.data_ptr())
-        zc = WAVEFRONT_ZEROCOPY
-        if zc:                                  # same address on both sides: the copies fall away (hesic_joint_decode_groups skips them too)
-            sym_dev, tab_d = sym_host, tab_h
-        ch_p = L.ptr(ch_dev)
+        # the pinned table buffer is kept with the state (pinning costs ~0.1 ms a call) and grows with the alphabet
+        if st["tab"] is None or st["tab"].shape[1] < n_tab:
+            st["tab"] = torch.empty((M * st["pmax"], n_tab), dtype=torch.int32).pin_memory()
         groups = st["groups"]
-        if WAVEFRONT_C_LOOP:
-            # the whole walk in one C call (hesic_joint_decode_groups): per group the captured device step, the table launch, the two copies,
-            # a polled wait and the host range decoder through its C entry point -- no Python between the groups
-            n = len(groups)
-            fn, handle = dec.grid_callback()
-            outs = (C.c_void_p * n)(*[st["graphs"][P][1].data_ptr() for P in groups])
-            sizes = (C.c_int32 * n)(*groups)
-            use_tape = WAVEFRONT_TAPE and all(st["graphs"][P][2] is not None for P in set(groups))
-            try:
-                if use_tape:
-                    # recorded launches replayed one by one; the table launch is then always issued by the walk (never the captured one)
-                    tapes = (C.c_void_p * n)(*[C.addressof(st["graphs"][P][2][0]) for P in groups])
-                    lens = (C.c_int32 * n)(*[len(st["graphs"][P][2][0]) for P in groups])
-                    dsc = (L.GmmDesc * n)(*[descs[P] for P in groups])
-                    L.call("hesic_joint_decode_groups_tape", n, sizes, tapes, lens, dsc, outs, ch_p, Cn, int(minmax), tab_d, tab_h, sym_dev, sym_host,
-                           fn, handle, 1, stream)
-                else:
-                    execs = (C.c_void_p * n)(*[st["graphs"][P][0].raw_cuda_graph_exec() for P in groups])
-                    dsc = None if in_graph else (L.GmmDesc * n)(*[descs[P] for P in groups])
-                    L.call("hesic_joint_decode_groups", n, sizes, execs, dsc, outs, ch_p, Cn, int(minmax), tab_d, tab_h, sym_dev, sym_host, fn, handle,
-                           1, stream)
-            except RuntimeError as e:
-                if "range decoder failed" in str(e):
-                    raise ValueError("RangeDecoder.decode_grid: bad table") from e
-                raise
-        else:
-            # per step: copy the previous symbols up, replay, table launch, copy the tables down, wait, decode
-            call, raw = L.call, dec.decode_grid_raw
-            nprev = 0
-            for P in groups:
-                if nprev and not zc:
-                    call("hesic_memcpy_async", sym_dev, sym_host, nprev * Cn * 4, 1, stream)
-                g, sm = st["graphs"][P][:2]
-                g.replay()
-                smp = L.ptr(sm)
-                if not in_graph:
-                    call("hesic_gmm_cdf_rows", C.byref(descs[P]), 0, smp, smp, None, ch_p, Cn, int(minmax), 1, tab_d, stream)
-                if not zc:
-                    call("hesic_memcpy_async", tab_h, tab_d, Cn * P * n_tab * 4, 2, stream)
-                call("hesic_stream_synchronize", stream)
-                raw(tab_h, n_tab, P, Cn, Cn, 1, sym_host)                                            # pixel-major rows, (P, Cn) symbols into the pinned buffer
-                nprev = P
-            if not zc:
-                call("hesic_memcpy_async", sym_dev, sym_host, nprev * Cn * 4, 1, stream)
+        n = len(groups)
+        steps = [st["graphs"][P] for P in groups]              # (graph, its (scale | mean) rows, tape or None)
+        fn, handle = dec.grid_callback()
+        sizes = (C.c_int32 * n)(*groups)
+        dsc = (L.GmmDesc * n)(*[L.GmmDesc(1, P, M, 1, L.F32, 0, 2 * M, 0, M, float(bound), 0.0) for P in groups])
+        outs = (C.c_void_p * n)(*[sm.data_ptr() for _, sm, _ in steps])
+        tail = (dsc, outs, L.ptr(st["channels"][:Cn]), Cn, int(minmax), C.c_void_p(st["tab"].data_ptr()), C.c_void_p(st["sym_pin"].data_ptr()),
+                fn, handle, L.stream())
+        try:
+            if all(tape is not None for _, _, tape in steps):
+                tapes = (C.c_void_p * n)(*[C.addressof(tape[0]) for _, _, tape in steps])
+                lens = (C.c_int32 * n)(*[len(tape[0]) for _, _, tape in steps])
+                L.call("hesic_joint_decode_groups_tape", n, sizes, tapes, lens, *tail)
+            else:                                               # a step the tape cannot express (L.TAPE_IDS): the captured graphs instead
+                execs = (C.c_void_p * n)(*[g.raw_cuda_graph_exec() for g, _, _ in steps])
+                L.call("hesic_joint_decode_groups", n, sizes, execs, *tail)
+        except RuntimeError as e:
+            if "range decoder failed" in str(e):
+                raise ValueError("RangeDecoder.decode_grid: bad table") from e
+            raise
         self._wavefront_kernel(st, 0)                              # the last group's symbols
         return st["y_pad"][:, :, 2:-2, 2:-2].contiguous(memory_format=torch.channels_last)
 

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HESIC_ABI_VERSION 2   /* round 5: bumped (entry points added since v1: the tape calls, *_hilo_out, msssim, joint decode) */
+#define HESIC_ABI_VERSION 3   /* 2: entry points added since v1 (the tape calls, *_hilo_out, msssim, joint decode); 3: entry points removed, the joint decode walk takes one pinned tab and one pinned sym */
 #define HESIC_EINVAL (-1)
 
 enum { HESIC_F32 = 0, HESIC_H16 = 1, HESIC_BF16 = 1 /* historical name of HESIC_H16 */ };
@@ -299,10 +299,6 @@ int hesic_sconv2d_forward_cat_gdn(const hesic_sconv_desc* d, const void* xa, con
  * gamma_packed / beta_packed from hesic_gdn_pack_params.                                                              */
 int hesic_sconv2d_gdn_forward(const hesic_sconv_desc* d, const void* x, const float* w, const float* bias,
                               const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* stream);
-/* training form: also stores the conv output (bf16 NHWC, y's geometry) for GDN's backward */
-int hesic_sconv2d_gdn_forward_train(const hesic_sconv_desc* d, const void* x, const float* w, const float* bias,
-                                    const void* gamma_packed, const float* beta_packed, int inverse, void* y, void* y_pre,
-                                    void* stream);
 /* The two image-side MFMA kernels keep their whole weight panel in LDS.  Building that LDS image inside the kernel (scalar
  * gathers from the PyTorch layout, several dependent round trips, by every block of every launch) cost ~14 us of a ~49 us launch;
  * hesic_sconv_pack_weight_image builds it ONCE per weight update and the *_prepacked forms start with a straight copy.
@@ -449,11 +445,6 @@ int hesic_gmm_cdf(const hesic_gmm_desc* d, int b, const void* scales, const void
  * pixel-by-pixel decoder consumes them) instead of j * HW + hw.                                                                       */
 int hesic_gmm_cdf_rows(const hesic_gmm_desc* d, int b, const void* scales, const void* means, const float* weights,
                        const int32_t* channels, int n_channels, int minmax, int pixel_major, uint32_t* cdf, void* stream);
-/* The same tables with n_channels and minmax read on the device (state = {unused, n_channels, minmax}, int32; channels sized for
- * max_channels): a launch that can be captured into a HIP graph and replayed for other images (the HESIC+ wavefront step).  Alphabets
- * of more than 1024 entries are not written (the caller then uses hesic_gmm_cdf).                                                     */
-int hesic_gmm_cdf_dyn(const hesic_gmm_desc* d, int b, const void* scales, const void* means, const float* weights,
-                      const int32_t* channels, int max_channels, const int32_t* state, int pixel_major, uint32_t* cdf, void* stream);
 /* Gradients: dy (y dtype; only meaningful in noise mode), dscales/dmeans (scales dtype, same layout),
  * dweights (B,K*M) fp32 zero-filled by caller (atomic accumulate).                                   */
 int hesic_gmm_backward(const hesic_gmm_desc* d, const void* y, const void* scales, const void* means,
@@ -611,24 +602,18 @@ int hesic_joint_step(void* y_rows, int dtype, int M, int Wp, const int32_t* sym,
                      const int32_t* channels, const int64_t* all_centre, const int64_t* all_rows, int64_t* pos, int P, void* crops,
                      const void* par, int c_par, const void* ext, int e_off, void* feat, int c_feat, void* stream);
 
-/* Host-loop helpers of the decode walk: hipMemcpyAsync (kind 1 = host -> device, 2 = device -> host; pinned host memory) and
- * hipStreamSynchronize behind the same error plumbing.                                                                               */
-int hesic_memcpy_async(void* dst, const void* src, size_t bytes, int kind, void* stream);
 /* The decode walk of one view of HESIC+ (newnet1_joint.py:1190-1260 regrouped into wavefronts) as ONE call: for each of the n_groups groups
- * (group_size[g] pixels) -- copy the previous group's symbols (sym_host, pinned) to sym_dev, launch graph_exec[g] (a hipGraphExec_t: the
- * group's captured device step, whose output scale_mean[g] is [P][2M] fp32 rows), hesic_gmm_cdf(descs[g]) into tab_dev, copy the tables to
- * (rows pixel-major: hesic_gmm_cdf_rows) tab_host (pinned), wait (spin != 0: poll hipStreamQuery), and call decode(decoder, tab_host, P,
- * n_channels, n_channels, 1, 2*minmax+2, sym_host)
- * -- the signature of hesic_rc_decoder_decode_grid (libhesic_host.so).  descs == NULL: the table launch is part of graph_exec[g]
- * (hesic_gmm_cdf_dyn) and is not issued again.  sym_dev == sym_host / tab_dev == tab_host (pinned, device-addressable
- * memory used by the kernels directly) skips the respective copies.  The last group's symbols are copied up before returning; the
- * caller scatters them (hesic_joint_step with P = 0).  A decoder error or a HIP error ends the walk with a non-zero return.              */
+ * (group_size[g] pixels) -- launch graph_exec[g] (a hipGraphExec_t: the group's captured device step, whose output scale_mean[g] is [P][2M]
+ * fp32 rows), hesic_gmm_cdf_rows(descs[g]) into tab (rows pixel-major), wait (polling hipStreamQuery), and call
+ * decode(decoder, tab, P, n_channels, n_channels, 1, 2*minmax+2, sym) -- the signature of hesic_rc_decoder_decode_grid (libhesic_host.so).
+ * tab and sym are pinned, device-addressable host memory: the kernels write the tables there and read the symbols from there themselves.
+ * The caller scatters the last group's symbols (hesic_joint_step with P = 0).  A decoder error or a HIP error ends the walk with a
+ * non-zero return.                                                                                                                      */
 typedef int (*hesic_decode_grid_fn)(void* decoder, const uint32_t* cdf, int64_t n_outer, int64_t n_inner, int64_t row_step_outer,
                                     int64_t row_step_inner, int32_t stride, int32_t* symbols_out);
 int hesic_joint_decode_groups(int n_groups, const int32_t* group_size, void* const* graph_exec, const hesic_gmm_desc* descs,
-                              void* const* scale_mean, const int32_t* channels, int n_channels, int minmax, uint32_t* tab_dev,
-                              uint32_t* tab_host, int32_t* sym_dev, int32_t* sym_host, hesic_decode_grid_fn decode, void* decoder, int spin,
-                              void* stream);
+                              void* const* scale_mean, const int32_t* channels, int n_channels, int minmax, uint32_t* tab, int32_t* sym,
+                              hesic_decode_grid_fn decode, void* decoder, void* stream);
 /* The same walk with each group's device step given as a TAPE of recorded launches instead of a graph: the entry point (HESIC_TAPE_*) and
  * its arguments as 64-bit words, the trailing stream argument left out (supplied at replay).  Back-to-back launches of a dependent chain
  * of small kernels start closer together than the nodes of a captured graph (ROCm 7.2).                                                */
@@ -636,9 +621,7 @@ enum { HESIC_TAPE_JOINT_STEP = 0, HESIC_TAPE_CONV2D_FORWARD = 1, HESIC_TAPE_CONV
 typedef struct { int32_t fn, nargs; uint64_t a[20]; } hesic_tape_call;
 int hesic_joint_decode_groups_tape(int n_groups, const int32_t* group_size, const hesic_tape_call* const* tapes, const int32_t* tape_len,
                                    const hesic_gmm_desc* descs, void* const* scale_mean, const int32_t* channels, int n_channels, int minmax,
-                                   uint32_t* tab_dev, uint32_t* tab_host, int32_t* sym_dev, int32_t* sym_host, hesic_decode_grid_fn decode,
-                                   void* decoder, int spin, void* stream);
-int hesic_stream_synchronize(void* stream);
+                                   uint32_t* tab, int32_t* sym, hesic_decode_grid_fn decode, void* decoder, void* stream);
 
 /* Measurement aid, not part of the path (bench.py `roofline.power_state`): a register-only loop of independent 32x32x16 MFMAs on the library's
  * 16-bit format over the whole chip -- the rate the matrix pipe sustains under the board's power management for operands of the kind `src_64k`

@@ -120,7 +120,7 @@ def test_abi_header_bindings_exports(fmt):
     for s in declared:
         assert f" T {s}\n" in exported, s
     lib = L.lib(torch.float16 if fmt == "f16" else torch.bfloat16)      # binds every signature, the new ones included
-    assert lib.hesic_abi_version() == 2
+    assert lib.hesic_abi_version() == 3
 
 
 def _host_ptr(offset=0):

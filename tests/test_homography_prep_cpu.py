@@ -24,7 +24,7 @@ def test_abi_header_bindings_exports(fmt):
     assert not set(declared) & set(L.declared_symbols())                # a header of its own: include/hesic_hip.h does not list it
     text = open(L.header_path("hesic_homography_prep.h")).read()
     assert f"#define HESIC_PREP_U8 {L.PREP_U8} " in text and f"#define HESIC_PREP_F32 {L.PREP_F32} " in text
-    assert "#define HESIC_ABI_VERSION 2" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 2
+    assert "#define HESIC_ABI_VERSION 3" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 3
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in declared:
         assert f" T {s}\n" in exported, s

@@ -26,7 +26,7 @@ def test_abi_header_bindings_exports(fmt):
     text = open(L.header_path("hesic_homography_train.h")).read()
     assert f"#define HESIC_HTRAIN_MAX_BLOCKS {L.HTRAIN_MAX_BLOCKS}\n" in text
     assert f"#define HESIC_HTRAIN_PARTIAL_WIDTH {L.HTRAIN_PARTIAL_WIDTH}\n" in text
-    assert "#define HESIC_ABI_VERSION 2" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 2
+    assert "#define HESIC_ABI_VERSION 3" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 3
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in declared:
         assert f" T {s}\n" in exported, s

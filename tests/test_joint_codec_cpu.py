@@ -148,7 +148,7 @@ def test_both_libraries_export_the_new_symbols(fmt):
     exported = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
     assert not [s for s in NEW_SYMBOLS if f" T {s}\n" not in exported]
     assert set(declared) == set(L._CODEC_SIGS)
-    assert L.lib().hesic_abi_version() == 2
+    assert L.lib().hesic_abi_version() == 3
 
 
 def test_new_entry_points_validate_their_arguments():

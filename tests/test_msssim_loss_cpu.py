@@ -89,7 +89,7 @@ def test_both_libraries_export_the_backward_entry_point(fmt):
     assert declared == ["hesic_ssim_scale_backward"] and set(declared) == set(L._MSSSIM_LOSS_SIGS)
     assert '#include "hesic_msssim_loss.h"' in open(L.header_path("hesic_hip.h")).read()
     l = L.lib(torch.float16 if fmt == "f16" else torch.bfloat16)
-    assert l.hesic_abi_version() == 2
+    assert l.hesic_abi_version() == 3
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     assert " T hesic_ssim_scale_backward\n" in exported
     assert l.hesic_ssim_scale_backward(None, None, None, None, 1, 3, 176, 176, 1.0, None, None, None, 5, 0, None, None, None, None) == -1

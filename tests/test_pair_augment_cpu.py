@@ -210,7 +210,7 @@ def test_abi_header_bindings_exports(fmt):
     declared = L.declared_symbols("hesic_pair_augment.h")
     assert declared == ["hesic_pair_batch_gather_aug"] and set(declared) == set(L._PAIR_AUGMENT_SIGS)
     assert L._PAIR_AUGMENT_SIGS["hesic_pair_batch_gather_aug"] == L._PAIR_BATCH_SIGS["hesic_pair_batch_gather"]        # the same arguments
-    assert not set(declared) & set(L.declared_symbols()) and L.ABI_VERSION == 2
+    assert not set(declared) & set(L.declared_symbols()) and L.ABI_VERSION == 3
     text = open(L.header_path("hesic_pair_augment.h")).read()
     for name, bit in (("HFLIP", L.PAIR_HFLIP), ("VFLIP", L.PAIR_VFLIP), ("SWAP", L.PAIR_SWAP)):
         assert f"#define HESIC_PAIR_{name} {bit}" in text and pair_cache.AUGMENT_BITS[name.lower()] == bit

@@ -223,7 +223,7 @@ def test_abi_header_bindings_exports(fmt):
     assert set(declared) == set(L._PAIR_BATCH_SIGS)
     assert not set(declared) & set(L.declared_symbols())                # a header of its own: include/hesic_hip.h does not list it
     assert "hesic_pair_batch.h" not in open(L.header_path("hesic_hip.h")).read()
-    assert "#define HESIC_ABI_VERSION 2" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 2
+    assert "#define HESIC_ABI_VERSION 3" in open(L.header_path("hesic_hip.h")).read() and L.ABI_VERSION == 3
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in declared:
         assert f" T {s}\n" in exported, s

@@ -35,7 +35,7 @@ def test_header_declares_what_the_table_binds():
 def test_both_libraries_export_and_check_the_entry_points(fmt):
     L = _lib()
     l = L.lib(torch.float16 if fmt == "f16" else torch.bfloat16)
-    assert l.hesic_abi_version() == 2
+    assert l.hesic_abi_version() == 3
     exported = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH_F16 if fmt == "f16" else L.LIB_PATH], text=True)
     for s in L._TRAIN_CTL_SIGS:
         assert f" T {s}\n" in exported, s
