@@ -392,6 +392,21 @@ _RANS_SIGS = {
                            _vp], _i32),
 }
 RANS_MAX_ROW = 512              # HESIC_RANS_MAX_ROW
+
+# include/hesic_homography_refine.h: photometric Gauss-Newton / Levenberg-Marquardt refinement of a pair's homography on a grey pyramid
+# (functional.homography_refine, homography.refine_h_matrix, ``codec encode --refine-homography``), in both libraries
+_f64 = C.c_double
+_HOMOGRAPHY_REFINE_SIGS = {
+    "hesic_hrefine_levels": ([_i32, _i32, _i32], _i32),
+    "hesic_hrefine_blocks": ([_i32, _i32], _i32),
+    "hesic_hrefine_pyramid_elems": ([_i32, _i32, _i32, _i32], _i64),
+    "hesic_homography_refine_ws_bytes": ([_i32, _i32, _i32, _i32], _i64),
+    "hesic_hrefine_pyramid": ([_vp, _P(_i64), _vp, _P(_i64), _i32, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
+    "hesic_hrefine_normal_eq": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _f64, _vp, _vp], _i32),
+    "hesic_homography_refine": ([_vp, _P(_i64), _vp, _P(_i64), _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f64, _f64, _vp, _i64, _vp, _vp, _vp],
+                                _i32),
+}
+HREFINE_MAX_LEVELS, HREFINE_MIN_SIDE, HREFINE_SUMS, HREFINE_INFO = 6, 16, 46, 8      # HESIC_HREFINE_* of that header
 RANS_OVERFLOW, RANS_BAD_TABLE, RANS_BAD_ESCAPE, RANS_BAD_STREAM = 1, 2, 4, 8
 
 _libs = {}                      # torch 16-bit dtype -> CDLL
@@ -418,6 +433,7 @@ HEADERS = {
     "hesic_pair_metrics.h": _PAIR_METRICS_SIGS,
     "hesic_en_train.h": _EN_TRAIN_SIGS,
     "hesic_rans.h": _RANS_SIGS,
+    "hesic_homography_refine.h": _HOMOGRAPHY_REFINE_SIGS,
 }
 
 

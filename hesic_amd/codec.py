@@ -1,6 +1,7 @@
 """``python -m hesic_amd.codec``: code a stereo folder to ``.hsd`` blobs and back, on the GPU.
 
     encode ROOT OUT [--split test] [--batch 8] [--checkpoint PATH] [--model hesic|joint] [--homography sidecar|net] [--homography-checkpoint PATH]
+                    [--refine-homography [--refine-levels 3] [--refine-iters 10] [--refine-huber DELTA]]
                                                                       ROOT/<split>/{left,right}/ + ROOT/<split>/H/<stem>.npy
                                                                       (the sidecars ``python -m hesic_amd.stereo_h`` writes)
                                                                       -> OUT/<stem>.hsd + OUT/<stem>.json, one JSON line of totals
@@ -17,6 +18,12 @@ deterministic synthetic weights are used (both sides must use the same weights a
 (``homography.h_matrix_from_pair``: the centre window of the unpadded images, on the device): no sidecars are needed and no pair is skipped.
 ``--homography-checkpoint`` names the net's weights (a ``homo_best.pth.tar`` or what ``python -m hesic_amd.homography_train`` writes); without
 it the deterministic synthetic weights.  The decoder reads the matrix from ``<stem>.json`` either way.
+
+``--refine-homography`` refines the matrix -- the sidecar's or the net's -- photometrically on the unpadded originals before it is used
+(``homography.refine_h_matrix``: Gauss-Newton / Levenberg-Marquardt on the grey residual, ``--refine-levels`` pyramid levels of
+``--refine-iters`` candidates, ``--refine-huber`` for a robust weight).  ``<stem>.json`` then carries the refined matrix with
+``"h_refined": true`` and the pair's mean squared grey residual before and after (``photometric_before``, ``photometric_after``; equal where
+the refinement kept the input).  Off by default; ``decode`` needs no option.
 """
 from __future__ import annotations
 
@@ -87,9 +94,10 @@ def quantise(x):
     return (x.float().clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
 
 
-def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, log=print, homography_net=None, z_coder="host"):
+def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, log=print, homography_net=None, z_coder="host", refine=None):
     """``homography_net=None``: the matrices come from the sidecars; a ``homography.Net``: from the net, for every pair.  ``z_coder``: who
-    codes the z strings (``compress_batch``); the files are the same bytes either way."""
+    codes the z strings (``compress_batch``); the files are the same bytes either way.  ``refine``: None, or the keyword arguments of
+    ``homography.refine_h_matrix`` (``levels``, ``iters``, ``huber``) to refine every matrix on the unpadded pair first."""
     from . import homography
     from .models import pad_to_multiple
     from .stereo_h import _image_size
@@ -116,10 +124,16 @@ def encode_folder(net, root, out, split="test", batch=8, channels_per_stream=8, 
             else:
                 Hs = [np.load(hp).astype(np.float64).reshape(3, 3) for _, _, _, hp in chunk]
                 Hm = torch.from_numpy(np.stack(Hs)).float().cuda()
+            extra = [{}] * len(chunk)
+            if refine is not None:
+                Hm, info = homography.refine_h_matrix(x1[..., :h, :w], x2[..., :h, :w], Hm, **refine)
+                Hs = list(Hm.double().cpu().numpy())
+                extra = [{"h_refined": True, "photometric_before": b, "photometric_after": a}
+                         for b, a in zip(info["cost_before"].cpu().tolist(), info["cost_after"].cpu().tolist())]
             enc = net.compress_batch(x1, x2, Hm, channels_per_stream=channels_per_stream, z_coder=z_coder)
-            for (stem, _, _, _), blob, Hn in zip(chunk, enc["blobs"], Hs):
+            for (stem, _, _, _), blob, Hn, ex in zip(chunk, enc["blobs"], Hs, extra):
                 (out / (stem + ".hsd")).write_bytes(blob)
-                (out / (stem + ".json")).write_text(json.dumps({"height": h, "width": w, "h_matrix": Hn.reshape(-1).tolist()}))
+                (out / (stem + ".json")).write_text(json.dumps({"height": h, "width": w, "h_matrix": Hn.reshape(-1).tolist(), **ex}))
                 n += 1
                 nbytes += len(blob)
                 bpp_sum += len(blob) * 8 / (2 * h * w)               # against the ORIGINAL pixels of the two views
@@ -170,6 +184,11 @@ def main(argv=None):
     e.add_argument("--homography", choices=("sidecar", "net"), default="sidecar",
                    help="sidecar: ROOT/<split>/H/<stem>.npy (default); net: HomographyNet on every pair (no sidecars needed)")
     e.add_argument("--homography-checkpoint", default=None, help="HomographyNet weights for --homography net (default: synthetic weights)")
+    e.add_argument("--refine-homography", action="store_true",
+                   help="refine every matrix photometrically on the unpadded pair before coding (homography.refine_h_matrix); off by default")
+    e.add_argument("--refine-levels", type=int, default=3, help="pyramid levels of --refine-homography")
+    e.add_argument("--refine-iters", type=int, default=10, help="candidates per level of --refine-homography")
+    e.add_argument("--refine-huber", type=float, default=None, help="Huber threshold of --refine-homography in grey levels of [0, 1] (default: plain L2)")
     d = sub.add_parser("decode", help="OUT/<stem>.hsd -> RECON/<stem>_{left,right}.png")
     d.add_argument("out")
     d.add_argument("recon")
@@ -190,8 +209,11 @@ def main(argv=None):
     if a.cmd == "encode":
         if a.homography_checkpoint and a.homography != "net":
             p.error("--homography-checkpoint needs --homography net")
+        if not a.refine_homography and (a.refine_levels != 3 or a.refine_iters != 10 or a.refine_huber is not None):
+            p.error("--refine-levels, --refine-iters and --refine-huber need --refine-homography")
         hnet = load_homography_net(a.homography_checkpoint) if a.homography == "net" else None
-        encode_folder(net, a.root, a.out, a.split, a.batch, a.channels_per_stream, homography_net=hnet, z_coder=a.z_coder)
+        refine = {"levels": a.refine_levels, "iters": a.refine_iters, "huber": a.refine_huber} if a.refine_homography else None
+        encode_folder(net, a.root, a.out, a.split, a.batch, a.channels_per_stream, homography_net=hnet, z_coder=a.z_coder, refine=refine)
     else:
         decode_folder(net, a.out, a.recon, a.batch, z_coder=a.z_coder)
     return 0

@@ -1999,6 +1999,63 @@ def h_from_delta(corners, delta, ratio_a, ratio_b, subtract_origin):
     return _apply(_HFromDeltaFn, corners, delta, float(ratio_a), float(ratio_b), int(subtract_origin))
 
 
+# include/hesic_homography_refine.h: photometric refinement of a pair's homography (homography.refine_h_matrix checks the arguments)
+def homography_refine_levels(H, W, levels):
+    """Pyramid levels a ``levels``-level refinement of H x W images actually uses (0: the image is below 16 pixels on a side)."""
+    n = L.lib().hesic_hrefine_levels(int(H), int(W), int(levels))
+    if n < 0:
+        raise ValueError(f"homography_refine: levels must lie in [1, {L.HREFINE_MAX_LEVELS}], got {levels}")
+    return n
+
+
+def _strides4(t):
+    return (C.c_int64 * 4)(*t.stride())
+
+
+def homography_refine_pyramid(x1, x2, levels):
+    """The grey pyramid of both views in one launch: x1, x2 fp32 (B,C,H,W) of one shape, C in {1,3}, any non-negative strides.  Returns the
+    flat fp32 buffer and its levels as views ``[(2, B, H_l, W_l)]`` (view 0: x1)."""
+    L.require_cuda(x1, x2)
+    B, Cc, H, W = x1.shape
+    n = homography_refine_levels(H, W, levels)
+    pyr = torch.empty(L.lib().hesic_hrefine_pyramid_elems(B, H, W, n), dtype=torch.float32, device=x1.device)
+    L.call("hesic_hrefine_pyramid", L.ptr(x1), _strides4(x1), L.ptr(x2), _strides4(x2), B, Cc, H, W, n, L.ptr(pyr), L.stream())
+    views, off = [], 0
+    for _ in range(n):
+        views.append(pyr[off:off + 2 * B * H * W].view(2, B, H, W))
+        off += 2 * B * H * W
+        H, W = H // 2, W // 2
+    return pyr, views
+
+
+def homography_refine_normal_eq(pyr, shape, levels, level, A, huber=None):
+    """The per-block sums of one candidate per pair on ``level`` of a pyramid built for ``shape`` = (B, H, W) with ``levels`` used levels:
+    ``A`` (B,3,3) fp64 in that level's coordinates -> (B, nblk, 46) fp64 (see the header for the 46 sums)."""
+    L.require_cuda(pyr, A)
+    B, H, W = shape
+    A = A.contiguous()
+    nblk = L.lib().hesic_hrefine_blocks(H >> level, W >> level)
+    partials = torch.empty((B, nblk, L.HREFINE_SUMS), dtype=torch.float64, device=pyr.device)
+    L.call("hesic_hrefine_normal_eq", L.ptr(pyr), B, H, W, int(levels), int(level), L.ptr(A), 9, float(huber or 0.0), L.ptr(partials), L.stream())
+    return partials
+
+
+def homography_refine(x1, x2, h, levels=3, iters=10, huber=None, min_overlap=0.25):
+    """x1, x2 fp32 (B,C,H,W), ``h`` (B,3,3) fp32 contiguous -> (h_refined (B,3,3) fp32, info (B,8) fp64: cost_before, cost_after, accepted,
+    rejected, valid_share, levels_used, refined, 0).  Nothing is read back; the call can be captured into a graph."""
+    L.require_cuda(x1, x2, h)
+    B, Cc, H, W = x1.shape
+    nbytes = L.lib().hesic_homography_refine_ws_bytes(B, H, W, int(levels))
+    if nbytes < 0:
+        raise ValueError(f"homography_refine: levels must lie in [1, {L.HREFINE_MAX_LEVELS}], got {levels}")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x1.device)
+    h_out = torch.empty((B, 3, 3), dtype=torch.float32, device=x1.device)
+    info = torch.empty((B, L.HREFINE_INFO), dtype=torch.float64, device=x1.device)
+    L.call("hesic_homography_refine", L.ptr(x1), _strides4(x1), L.ptr(x2), _strides4(x2), B, Cc, H, W, L.ptr(h), int(levels), int(iters),
+           float(huber or 0.0), float(min_overlap), L.ptr(ws), nbytes, L.ptr(h_out), L.ptr(info), L.stream())
+    return h_out, info
+
+
 # The host path the descriptor-batch entries share (homonet_prepare_items, homonet_synth, both pair gathers): the items as a structured array,
 # the per-item checks, a device, the outputs, the upload; each wrapper below is these plus its own launch line.
 def _items_array(name, dtype_name, dtype, items):

@@ -41,6 +41,7 @@ from . import geometry
 from .compressai.models.utils import HipConv2d
 
 __all__ = ["Net", "Block", "Flatten", "max_pool2", "get_perspective_transform", "h_matrix_from_delta", "h_matrix", "photometric_loss", "corner_error",
+           "refine_h_matrix",
            "window_origins", "draw_deltas", "prepare_inputs", "h_matrix_from_pair", "load_checkpoint", "checkpoint_state_dict", "net_state_dict"]
 
 
@@ -233,6 +234,58 @@ def corner_error(delta_hat, delta):
     """Mean corner error per pair: the mean over the four corners of ``||delta_hat_k - delta_k||_2``, in pixels of the frame the deltas are
     measured in.  (B,4,2) twice -> (B,) fp32.  ``delta_hat = 0`` gives the error of predicting the identity, the figure to beat."""
     return (delta_hat.float() - delta.float()).square().sum(-1).sqrt().mean(-1)
+
+
+def refine_h_matrix(x1, x2, h_matrix, *, levels=3, iters=10, huber=None, min_overlap=0.25, align_corners=None):
+    """Refine ``h_matrix`` photometrically: Gauss-Newton with Levenberg-Marquardt damping on ``grey(x1)(H^-1 p) - grey(x2)(p)``, coarse to
+    fine over ``levels`` pyramid levels with ``iters`` candidates after each level's first (include/hesic_homography_refine.h).
+
+    ``x1``, ``x2``: (B,C,H,W) fp32 of one shape, C = 1 or 3, any non-negative strides (un-padded views are fine), at least 16 pixels on a
+    side; ``h_matrix``: (B,3,3) or (1,3,3), x1 pixel -> x2 pixel, what ``HSIC.forward`` takes.  ``huber``: None for plain least squares, or
+    the residual (in grey levels of the input's scale) above which a pixel's weight falls as ``huber / |r|``.  A candidate that keeps fewer
+    than ``min_overlap`` of the level's pixels valid is rejected.
+
+    Returns ``(h_refined, info)``: (B,3,3) fp32 and a dict of device tensors that this function never reads back -- ``cost_before`` /
+    ``cost_after`` (mean squared grey residual over the valid pixels of level 0, fp64), ``accepted`` / ``rejected`` (int32 candidate counts),
+    ``valid_share`` (fp64) and ``levels_used`` (int32).  The result is never worse than the input by that measure: where no candidate was
+    accepted or level 0's final cost is not below ``cost_before`` -- no overlap, a singular matrix, an ``x2`` without contrast (a constant
+    view says nothing about geometry: such a level does nothing), ``iters=0`` -- the pair's input comes back
+    bit for bit with ``cost_after == cost_before``.  Deterministic, free of host synchronisation, and capturable into a graph.
+
+    This is a refiner, not an estimator: its basin is a few texture correlation lengths at the coarsest level (start it from the SURF + RANSAC
+    sidecar or from HomographyNet).  Only ``align_corners=True`` sampling is implemented."""
+    for t in (x1, x2, h_matrix):
+        if not torch.is_tensor(t):
+            raise TypeError(f"refine_h_matrix: tensors expected, got {type(t).__name__}")
+    ac = geometry.DEFAULT_ALIGN_CORNERS if align_corners is None else bool(align_corners)
+    if not ac:
+        raise NotImplementedError("refine_h_matrix: only align_corners=True sampling is implemented; the legacy align_corners=False "
+                                  "convention (geometry.use_reference_era_warp, HESIC_WARP_ALIGN_CORNERS=0) is out of scope")
+    if x1.dim() != 4 or x1.shape != x2.shape or x1.shape[1] not in (1, 3):
+        raise RuntimeError(f"refine_h_matrix: x1 and x2 must be (B, 1 or 3, H, W) tensors of one shape, got {tuple(x1.shape)} and {tuple(x2.shape)}")
+    B, _, H, W = x1.shape
+    if B == 0:
+        raise RuntimeError("refine_h_matrix: empty batch")
+    if h_matrix.dim() != 3 or h_matrix.shape[-2:] != (3, 3) or h_matrix.shape[0] not in (1, B):
+        raise RuntimeError(f"refine_h_matrix: h_matrix must be (B, 3, 3) (or (1, 3, 3)), got {tuple(h_matrix.shape)}")
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or h_matrix.dtype != torch.float32:
+        raise TypeError(f"refine_h_matrix: float32 images and matrix, got {x1.dtype}, {x2.dtype}, {h_matrix.dtype}")
+    if min(H, W) < L.HREFINE_MIN_SIDE:
+        raise RuntimeError(f"refine_h_matrix: images must be at least {L.HREFINE_MIN_SIDE} pixels on a side, got {H}x{W}")
+    if not 1 <= int(levels) <= L.HREFINE_MAX_LEVELS or int(iters) < 0:
+        raise ValueError(f"refine_h_matrix: levels in [1, {L.HREFINE_MAX_LEVELS}] and iters >= 0, got levels={levels}, iters={iters}")
+    if huber is not None and not float(huber) > 0.0:
+        raise ValueError(f"refine_h_matrix: huber is None or positive, got {huber}")
+    if not 0.0 <= float(min_overlap) <= 1.0:
+        raise ValueError(f"refine_h_matrix: min_overlap in [0, 1], got {min_overlap}")
+    if any(s < 0 for s in x1.stride() + x2.stride()):
+        raise ValueError("refine_h_matrix: negative strides are not supported")
+    L.require_cuda(x1, x2, h_matrix)
+    h = h_matrix.detach().expand(B, 3, 3).contiguous()
+    out, rec = Fn.homography_refine(x1.detach(), x2.detach(), h, int(levels), int(iters), huber, float(min_overlap))
+    info = {"cost_before": rec[:, 0], "cost_after": rec[:, 1], "accepted": rec[:, 2].to(torch.int32), "rejected": rec[:, 3].to(torch.int32),
+            "valid_share": rec[:, 4], "levels_used": rec[:, 5].to(torch.int32)}
+    return out, info
 
 
 def h_matrix(net, homo_img1, homo_img2, homo_corners, img_h, img_w, pic_size=256):

@@ -187,7 +187,7 @@ def _image_size(path):
 
 
 def write_sidecars(root, splits=("train", "test"), batch=8, overwrite=False, estimator=None, seed=0, log=print, upright=True,
-                   extended=False):
+                   extended=False, refine=None):
     """Write ``root/<split>/H/<stem>.npy`` (fp64, the full images' H) for every pair of the stereo folder that has none (all with
     ``overwrite``).  Pairs are grouped by size from their file headers and estimated ``batch`` at a time; only the pairs of the current
     batch are decoded (with the loader's reader), so memory does not grow with the folder.  The RANSAC pair number of a pair is its
@@ -195,6 +195,10 @@ def write_sidecars(root, splits=("train", "test"), batch=8, overwrite=False, est
     pair gets no file (the loader then yields ``(img1, img2)`` for it, as the reference does on a RANSAC failure).
     ``estimator(x1, x2, pair_ids) -> (H, valid)`` on (B, 3, H, W) uint8 CPU tensors replaces the GPU estimate; ``upright`` /
     ``extended`` select the descriptor of the GPU estimate as in ``estimate_homography``.
+    ``refine``: None (default), or a dict of keyword arguments of ``homography.refine_h_matrix`` (``levels``, ``iters``, ``huber``,
+    ``min_overlap``; ``{}`` for its defaults): every estimate is then refined photometrically on the pair's images (fp32 in [0, 1], on the
+    GPU) before it is written, so whatever reads the sidecars -- the trainers, ``eval_folder``, ``codec encode`` -- gets the refined matrix.
+    A pair the refiner cannot improve keeps its estimate; an invalid pair still gets no file.
     Returns (written, invalid, skipped)."""
     from .compressai.datasets import _read_rgb
     import glob
@@ -231,6 +235,10 @@ def write_sidecars(root, splits=("train", "test"), batch=8, overwrite=False, est
                 else:
                     Hd, vd, _ = estimate_homography(x1.cuda(), x2.cuda(), seed=seed, pair_ids=ids, upright=upright, extended=extended)
                     Hs, ok = Hd.cpu().numpy(), vd.cpu().tolist()
+                if refine is not None:
+                    from . import homography
+                    Hin = torch.from_numpy(np.asarray(Hs, dtype=np.float32).reshape(-1, 3, 3)).cuda()
+                    Hs = homography.refine_h_matrix(x1.cuda().float() / 255.0, x2.cuda().float() / 255.0, Hin, **refine)[0].cpu().numpy()
                 hdir.mkdir(exist_ok=True)
                 for (_, stem, _, _), Hm, v in zip(chunk, Hs, ok):
                     if not v:
@@ -255,11 +263,14 @@ def main(argv=None):
     p.add_argument("--oriented", action="store_true",
                    help="oriented SURF (rotation-invariant; the reference's SURF_create() default) instead of upright U-SURF")
     p.add_argument("--extended", action="store_true", help="128-d descriptors instead of 64-d")
+    p.add_argument("--refine", action="store_true",
+                   help="refine every estimate photometrically before it is written (homography.refine_h_matrix, its defaults); off by default")
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
         print("stereo_h: needs a ROCm device (the estimator has no CPU path)", file=sys.stderr)
         return 2
-    write_sidecars(a.root, a.split, a.batch, a.overwrite, seed=a.seed, upright=not a.oriented, extended=a.extended)
+    write_sidecars(a.root, a.split, a.batch, a.overwrite, seed=a.seed, upright=not a.oriented, extended=a.extended,
+                   refine={} if a.refine else None)
     return 0
 
 
